@@ -12,7 +12,14 @@ RMSpropAsync, advance.  Units = envs_per_gpu * t_max * world env-steps per
 step.  Inputs are synthetic 210x160x3 RGB frame pairs, rewards and terminal
 flags pre-generated in HBM (a pool of `--pool` steps, cycled).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps, writes the last step's
+outputs if `--dump-outputs DIR` is given and prints the result line (metric,
+value, unit, ms_per_step, config).  Everything else the bench measures or
+checks -- the HBM copy peak, the per-window median, the window timeline, the
+per-kernel roofline, the CPU baseline legs, the secondary workload, the
+finite-parameter and replica checks -- runs only with `--full`.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
         --gpus N > 1 without WORLD_SIZE in the environment: this process starts
         N ranks itself (one child process per GPU, like the reference's
         run_async, async.py:68-90), touches no GPU, forwards rank 0's line.
@@ -91,6 +98,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline: HBM copy "
+                         "peak, per-window median, window timeline, per-kernel roofline, CPU baseline, secondary "
+                         "workload, finite parameters / identical replicas (the options below that size them "
+                         "have no effect without it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (parameters, RMSProp statistics, "
+                         "gradient, the window's logits / probs / values / actions; c5: a seeded sample of the "
+                         "stacks) as DIR/<name>.npy in float32 (rank 0's)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c4",
                     help="BASELINE.json configs: c4 FF 512 envs per GPU (default: 4096 over 8 GPUs, the north-star "
                          "target's config), c2 FF 256 envs, c3 LSTM 1024 envs A=6, c5 phi stress 16384 frame pairs")
@@ -142,6 +158,21 @@ def _free_port() -> int:
         return s.getsockname()[1]
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, tensors):
+    """--dump-outputs: each tensor as dirname/<name>.npy in float32 (the
+    kernels' outputs are f32, int32 actions or u8 planes: all exact in f32)."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in tensors.items()}
+    total = sum(x.nbytes for x in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    for k, x in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(x))
+
+
 def launch_ranks(n: int) -> int:
     """`--gpus N` (N > 1) run as a plain `python bench.py`: start the N rank
     processes here, one per GPU (RANK = LOCAL_RANK = r, WORLD_SIZE = N,
@@ -190,6 +221,11 @@ def launch_ranks(n: int) -> int:
     if rc:
         print(f"bench.py: a rank failed (status {rc})", file=sys.stderr)
     return 0 if rc == 0 else (rc if rc > 0 else 1)
+
+
+# result-line entries that only a --full run measures or checks
+FULL_ONLY_KEYS = ("replicas_identical", "windows", "timeline", "hbm_copy_peak", "roofline", "kernels",
+                  "cpu_baseline", "params_finite", "secondary")
 
 
 CONV_SLAB_FLOATS = 12336                    # conv_slab.hpp SLAB: one conv_bwd workgroup's partial gradient
@@ -484,6 +520,11 @@ def bench_phi(a, world, rank, dev, n_default, copy_peak=None):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and a.dump_outputs:
+        # the stacks the last step wrote: all of them up to 512 pairs (57.8 MB as f32), else a fixed seeded sample
+        idx = np.arange(n) if n <= 512 else np.sort(np.random.default_rng(0).choice(n, 512, replace=False))
+        sel = torch.from_numpy(idx).to(dev)
+        dump_outputs(a.dump_outputs, {"stacks": stacks[it[0] & 1][sel], "stack_index": sel})
     if rank == 0:
         work = n * PHI_STACK_BYTES_PER_PAIR
         ach = work / (us * 1e-6) / 1e9
@@ -502,6 +543,9 @@ def bench_phi(a, world, rank, dev, n_default, copy_peak=None):
                             "frac_measured_peak": round(ach / copy_peak["GB/s"], 4) if copy_peak else None},
                "hbm_copy_peak": copy_peak,
                "cpu_baseline": None}
+        if not a.full:   # a plain run: the headline only
+            for k in FULL_ONLY_KEYS:
+                out.pop(k, None)
         print(json.dumps(out))
     if dist.is_initialized():
         dist.destroy_process_group()
@@ -609,7 +653,7 @@ def timed_region_diag(a, window, stream):
 
 def main(a):
     mp_ctx = None
-    if a.cpu_seconds > 0 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+    if a.full and a.cpu_seconds > 0 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # CPU baseline leg (ii) workers are forked by a forkserver started
         # here, before anything touches the GPU (no worker is a fork of a GPU
         # process); it preloads the oracle's CPU baseline module
@@ -629,7 +673,7 @@ def main(a):
     pkg = _import_pkg()
     A3C, RMSpropAsync, GradientClipping = pkg.A3C, pkg.RMSpropAsync, pkg.GradientClipping
     from asyncrl_amd._lib import LEARN_CONV
-    copy_peak = measure_copy_peak(dev) if (rank == 0 and a.copy_peak) else None
+    copy_peak = measure_copy_peak(dev) if (a.full and rank == 0 and a.copy_peak) else None
     w_arch, w_envs, w_A = WORKLOADS[a.workload]
     if w_arch == "phi":
         return bench_phi(a, world, rank, dev, w_envs, copy_peak)
@@ -726,13 +770,22 @@ def main(a):
     value = units / elapsed
     ms_step = 1e3 * elapsed / a.steps
 
-    diag = timed_region_diag(a, window, stream) if a.timed_diag > 0 else None
+    if rank == 0 and a.dump_outputs:
+        # what the last timed window left: the updated parameters and RMSProp statistics, the gradient it
+        # applied, and its T + 1 steps' policy / value outputs and sampled actions
+        nb = model.net.buffer
+        dump_outputs(a.dump_outputs, {
+            "params": model.net.params, "rmsprop_ms": model.net.ms, "grads": model.net.grads,
+            "logits": nb("logits", torch.float32, (T + 1, N, A)), "probs": nb("probs", torch.float32, (T + 1, N, A)),
+            "v": nb("v", torch.float32, (T + 1, N)), "actions": nb("actions", torch.int32, (T + 1, N))})
+
+    diag = timed_region_diag(a, window, stream) if (a.full and a.timed_diag > 0) else None
 
     # per-window distribution (median over >= 100 windows): more
     # windows after the timed region, each between two HIP events on the bench
     # stream (which every part of a window, collectives included, joins)
     windows = None
-    if a.median_windows > 0:
+    if a.full and a.median_windows > 0:
         M = a.median_windows
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(M + 1)]
         with torch.cuda.stream(stream):
@@ -752,9 +805,9 @@ def main(a):
                    "p90_ms": round(float(q[2]), 4), "median_env_steps_per_s": round(N * T * world / (med * 1e-3), 1),
                    "note": "HIP events per window on the bench stream; median = max over ranks of each rank's "
                            "median, p10 / p90 rank 0's"}
-    finite = bool(torch.isfinite(model.net.params).all())
+    finite = bool(torch.isfinite(model.net.params).all()) if a.full else None
     replicas = None
-    if collectives:   # every rank applied the same update to the same reduced gradient (distributed.py)
+    if a.full and collectives:   # every rank applied the same update to the same reduced gradient (distributed.py)
         from asyncrl_amd.distributed import replicas_identical
         replicas = bool(replicas_identical(model.net.params) and replicas_identical(model.net.ms))
 
@@ -766,7 +819,7 @@ def main(a):
     # them (the collectives need all ranks); rank 0 reports its own.
     timeline = None
     net = model.net
-    if a.stamp_windows > 0 and not use_graph and n_groups == 1 and not nat:
+    if a.full and a.stamp_windows > 0 and not use_graph and n_groups == 1 and not nat:
         from asyncrl_amd._lib import STAGE_NAMES
 
         def stamped(n_win, period=0):
@@ -833,7 +886,7 @@ def main(a):
     # on the bench stream ("standalone_us", beside it).  The stage with the
     # largest in-window share is the "roofline" kernel.
     roof, kernels = None, None
-    if rank == 0:
+    if a.full and rank == 0:
         S = N * T
 
         def timed(fn):
@@ -992,7 +1045,7 @@ def main(a):
                 k["moved_basis"]["frac_measured_peak"] = round(ach / copy_peak["GB/s"], 4)
 
     cpu = None
-    if rank == 0 and world == 1 and a.cpu_seconds > 0 and arch == "ff":
+    if a.full and rank == 0 and world == 1 and a.cpu_seconds > 0 and arch == "ff":
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import cpu_baseline  # noqa: E402  (oracle/, CPU baseline leg only)
         cpu = cpu_baseline.run(seconds=a.cpu_seconds, t_max=T, n_actions=4)        # leg (i): 1 process, 1 core
@@ -1010,7 +1063,7 @@ def main(a):
     secondary = None
     sec = a.secondary if a.secondary != "auto" else ("c3" if (a.workload == "c4" and world == 1 and arch == "ff")
                                                     else "none")
-    if world == 1 and sec not in ("", "none"):   # (the headline's buffers stay: 288 GB of HBM)
+    if a.full and world == 1 and sec not in ("", "none"):   # (the headline's buffers stay: 288 GB of HBM)
         secondary = [secondary_line(a, pkg, dev, w.strip()) for w in sec.split(",") if w.strip()]
 
     if rank == 0:
@@ -1037,6 +1090,9 @@ def main(a):
             "roofline": roof, "kernels": kernels, "cpu_baseline": cpu, "params_finite": finite,
             "secondary": secondary,
         }
+        if not a.full:   # a plain run: the headline only
+            for k in FULL_ONLY_KEYS:
+                out.pop(k, None)
         print(json.dumps(out), flush=True)
     if collectives:
         dist.destroy_process_group()

@@ -6,6 +6,7 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 mkdir -p gpurun_out/ab
+set -- "$1" "$2" "--full $3" "${4:-3}"   # the per-stage times printed below are part of a --full line
 for r in $(seq 1 ${4:-3}); do
   for v in A B; do
     root=$1; [ $v = B ] && root=$2

@@ -11,7 +11,7 @@ tag=$(echo "$3" | tr -dc 'a-z0-9')
 for r in $(seq 1 ${4:-3}); do
   for v in A B; do
     e=$1; [ $v = B ] && e=$2
-    env $e timeout -k 10 200 python -u bench.py $3 --steps 100 --warmup 10 --cpu-seconds 0 --kernel-reps 5 --copy-peak 0 > $O/$tag$v$r.log 2>&1
+    env $e timeout -k 10 200 python -u bench.py --full $3 --steps 100 --warmup 10 --cpu-seconds 0 --kernel-reps 5 --copy-peak 0 > $O/$tag$v$r.log 2>&1
     rc=$?; [ $rc -ne 0 ] && { tail -n 5 $O/$tag$v$r.log; exit $rc; }
     python -c "
 import json; d=json.loads(open('$O/$tag$v$r.log').read().strip().splitlines()[-1])

@@ -13,12 +13,12 @@ O=gpurun_out/$TAG
 mkdir -p $O
 step() { echo "== $1 rc=$2"; [ "$2" -eq 0 ] || exit "$2"; }
 for w in $WL; do
-  timeout -k 10 300 python -u bench.py --workload $w --steps 30 --warmup 5 --cpu-seconds 0 > $O/bench_$w.log 2>&1
+  timeout -k 10 300 python -u bench.py --full --workload $w --steps 30 --warmup 5 --cpu-seconds 0 > $O/bench_$w.log 2>&1
   step bench_$w $?
   tail -n 1 $O/bench_$w.log
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -o run -- python bench.py --workload $w --steps 10 --warmup 3 --cpu-seconds 0 --kernel-reps 10 --secondary none > $O/prof_$w.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -o run -- python bench.py --full --workload $w --steps 10 --warmup 3 --cpu-seconds 0 --kernel-reps 10 --secondary none > $O/prof_$w.log 2>&1
   step prof_$w $?
-  B="python bench.py --workload $w --steps 3 --warmup 2 --cpu-seconds 0 --no-graph --kernel-reps 3 --secondary none"
+  B="python bench.py --full --workload $w --steps 3 --warmup 2 --cpu-seconds 0 --no-graph --kernel-reps 3 --secondary none"
   timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_$w -o fetch -- $B > $O/pmc_fetch_$w.log 2>&1
   step fetch_$w $?
   timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_$w -o write -- $B > $O/pmc_write_$w.log 2>&1

@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=$1
 shift
-B="python bench.py --steps 3 --warmup 2 --cpu-seconds 0 --no-graph --kernel-reps 3"
+B="python bench.py --full --steps 3 --warmup 2 --cpu-seconds 0 --no-graph --kernel-reps 3"
 for v in asyncrl_amd "$@"; do
   lib=$PWD/async-rl_amd/csrc/$v/libasyncrl_hip.so
   [ "$v" = asyncrl_amd ] && lib=$PWD/async-rl_amd/asyncrl_amd/libasyncrl_hip.so

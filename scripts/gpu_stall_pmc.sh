@@ -12,7 +12,7 @@ O=gpurun_out/$TAG
 mkdir -p $O
 timeout -s KILL 60 rocprofv3 --list-avail > $O/list_avail.txt 2>&1 || echo "list-avail rc=$?" >> $O/status
 for w in $WL; do
-  B="python bench.py --workload $w --steps 3 --warmup 2 --cpu-seconds 0 --no-graph --kernel-reps 3 --secondary none"
+  B="python bench.py --full --workload $w --steps 3 --warmup 2 --cpu-seconds 0 --no-graph --kernel-reps 3 --secondary none"
   timeout -s KILL 120 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/mfma_$w -o mfma -- $B > $O/mfma_$w.log 2>&1
   rc=$?; echo "== mfma $w rc=$rc" >> $O/status; [ $rc -eq 0 ] || exit $rc
   python scripts/mfma_util.py $O/mfma_$w/*counter_collection.csv --json $O/mfma_util_$w.json > $O/mfma_util_$w.txt 2>&1

@@ -5,7 +5,7 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
-TAG=$1; ARGS=$2; REPS=$3; shift 3
+TAG=$1; ARGS="--full $2"; REPS=$3; shift 3
 O=gpurun_out/$TAG
 mkdir -p $O
 for r in $(seq 1 $REPS); do

@@ -6,7 +6,7 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 mkdir -p gpurun_out/var
-ARGS=${1:-"--steps 30 --warmup 5"}
+ARGS="--full ${1:---steps 30 --warmup 5}"
 for r in $(seq 1 ${2:-1}); do
   LIBS="async-rl_amd/asyncrl_amd/libasyncrl_hip.so"
   if [ -n "$3" ]; then

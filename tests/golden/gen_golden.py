@@ -490,8 +490,27 @@ def gen_checkpoint():
     subprocess.check_call(["/opt/conda/bin/python3.9", "-c", code, src, dst])
 
 
+def gen_checkpoint_head():
+    """breakout_ff_head.h5: the trained checkpoint's HDF5 file written again
+    with its own storage (every dataset's chunk shape, gzip level and the
+    file's library bounds as Chainer's save_hdf5 left them), with the FC
+    weight 0/2/W cut to its first 64 of 256 rows so the file stays small."""
+    src = os.path.join(REF, "trained_model/breakout_ff/80000000_finish.h5")
+    dst = os.path.join(HERE, "breakout_ff_head.h5")
+    code = ("import h5py, sys\n"
+            "f = h5py.File(sys.argv[1], 'r')\n"
+            "g = h5py.File(sys.argv[2], 'w', libver=f.libver)\n"
+            "def put(n, o):\n"
+            "    if isinstance(o, h5py.Dataset):\n"
+            "        g.create_dataset(n, data=o[:64] if n == '0/2/W' else o[()], chunks=o.chunks,\n"
+            "                         compression=o.compression, compression_opts=o.compression_opts)\n"
+            "f.visititems(put)\n"
+            "g.close()\n")
+    subprocess.check_call(["/opt/conda/bin/python3.9", "-c", code, src, dst])
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1:            # e.g. gen_golden.py gen_ale_env
+    if len(sys.argv) > 1:           # e.g. gen_golden.py gen_ale_env
         for name in sys.argv[1:]:
             globals()[name]()
         sys.exit(0)
@@ -501,5 +520,6 @@ if __name__ == "__main__":
     gen_dqn_phi()
     gen_rmsprop()
     gen_checkpoint()
+    gen_checkpoint_head()
     for f in sorted(os.listdir(HERE)):
         print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -21,8 +21,8 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 BENCH = os.path.join(ROOT, "bench.py")
-SMALL = ["--workload", "c2", "--steps", "10", "--warmup", "3", "--cpu-seconds", "0", "--kernel-reps", "3", "--secondary", "none",
-         "--median-windows", "20", "--copy-peak", "0"]
+SMALL = ["--full", "--workload", "c2", "--steps", "10", "--warmup", "3", "--cpu-seconds", "0", "--kernel-reps", "3",
+         "--secondary", "none", "--median-windows", "20", "--copy-peak", "0"]
 
 
 def _env(**kw):
@@ -70,7 +70,7 @@ def test_bench_window_timeline(gpu):
     with the measured copy peak on, no HBM stage exceeds the spec or the
     measured peak, and no MFMA stage exceeds the ceiling of the instructions it
     issues (frac, frac_issued <= 1)."""
-    args = ["--steps", "10", "--warmup", "3", "--cpu-seconds", "0", "--kernel-reps", "3", "--secondary", "none",
+    args = ["--full", "--steps", "10", "--warmup", "3", "--cpu-seconds", "0", "--kernel-reps", "3", "--secondary", "none",
             "--median-windows", "40", "--stamp-windows", "40"]
     r = subprocess.run([sys.executable, BENCH, "--gpus", "1"] + args, capture_output=True, text=True, timeout=300,
                        env=_env())
@@ -111,6 +111,34 @@ def test_bench_secondary_workload(gpu):
     (sec,) = d["secondary"]
     assert sec["workload"].startswith("c2") and sec["steps"] == 10 and sec["params_finite"], sec
     assert sec["value"] > 0 and sec["median_window_ms"] > 0
+
+
+def test_bench_plain_run_dumps_outputs(gpu, tmp_path):
+    """A plain run (no --full) prints the headline only -- the timed steps as
+    asked, none of the --full measurements -- and --dump-outputs writes the
+    last timed window's results as float32 .npy files."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--workload", "c2", "--envs-per-gpu", "64", "--pool", "2",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=300, env=_env())
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["unit"] == "env-steps/s" and d["dtype"] == "f32", d
+    assert d["higher_is_better"] is True and d["metric"].startswith("env-steps/sec"), d
+    assert abs(d["value"] - 64 * 5 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"], d
+    for k in ("windows", "timeline", "kernels", "roofline", "hbm_copy_peak", "cpu_baseline", "secondary"):
+        assert k not in d, k
+    shapes = {"params": None, "rmsprop_ms": None, "grads": None, "logits": (6, 64, 4), "probs": (6, 64, 4),
+              "v": (6, 64), "actions": (6, 64)}
+    assert sorted(p.name for p in out.iterdir()) == sorted(k + ".npy" for k in shapes)
+    got = {k: np.load(out / (k + ".npy")) for k in shapes}
+    flat = got["params"].shape                                     # the flat parameter vector (padded)
+    assert len(flat) == 1 and flat[0] >= 677429, flat
+    for k, shp in shapes.items():
+        assert got[k].dtype == np.float32 and got[k].shape == (shp or flat) and np.isfinite(got[k]).all(), k
+    assert np.abs(got["probs"].sum(-1) - 1).max() < 1e-5
+    assert ((got["actions"] >= 0) & (got["actions"] < 4)).all() and got["rmsprop_ms"].max() > 0
 
 
 def test_bench_gpus_mismatch_fails(gpu):
