@@ -62,6 +62,7 @@ SIGNATURES = {
     "arl_observe_states": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p]),
     "arl_truncate_window": (c_int, [c_void_p, c_int, c_void_p]),
     "arl_net_set_loss": (c_int, [c_void_p, c_double, c_int]),
+    "arl_net_set_weight_decay": (c_int, [c_void_p, c_double]),
     "arl_net_set_norm_fold": (c_int, [c_void_p, c_int]),
     "arl_net_set_returns_fusion": (c_int, [c_void_p, c_int, c_double, c_double, c_double, c_int]),
     "arl_reset_state": (c_int, [c_void_p, c_i64, c_i64, c_void_p]),
@@ -86,6 +87,8 @@ SIGNATURES = {
     "arl_forward_states": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_void_p]),
     "arl_rmsprop": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_double, c_double, c_double, c_double,
                             c_void_p, c_void_p]),
+    "arl_rmsprop_wd": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_double, c_double, c_double, c_double,
+                               c_void_p, c_double, c_void_p]),
     "arl_policy": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_u64, c_void_p,
                            c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_void_p]),

@@ -278,6 +278,12 @@ class DeviceNet:
     def set_loss(self, pi_loss_coef: float = 1.0, keep_loss_scale_same: bool = False):
         check(lib.arl_net_set_loss(self._h, pi_loss_coef, int(keep_loss_scale_same)), "arl_net_set_loss")
 
+    def set_weight_decay(self, rate: float = 0.0):
+        """NonbiasWeightDecay(rate) inside the update kernel (arl_net_set_weight_decay):
+        after the clip, g += rate * p for every non-bias parameter; 0 = off.
+        A captured window keeps the rate it was captured with."""
+        check(lib.arl_net_set_weight_decay(self._h, float(rate)), "arl_net_set_weight_decay")
+
     def reset_state(self, e0: int = 0, n: int | None = None, stream=None):
         """LSTM: the pi_and_v recurrent state of rows [e0, e0 + n) -> None (arl_reset_state)."""
         n = self.n_envs - e0 if n is None else n

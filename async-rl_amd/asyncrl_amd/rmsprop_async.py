@@ -1,11 +1,13 @@
-"""RMSpropAsync + GradientClipping, mirroring rmsprop_async.py:7-38 and the
-Chainer hook used at a3c_ale.py:224-226.
+"""RMSpropAsync + GradientClipping + NonbiasWeightDecay, mirroring
+rmsprop_async.py:7-38, the Chainer hook used at a3c_ale.py:224-226 and
+nonbias_weight_decay.py (a3c_ale.py:227-228, --weight-decay).
 
 The reference's update is `ms = alpha*ms + (1-alpha)*g*g; p -= lr*g/sqrt(ms+eps)`
 (eps OUTSIDE the sqrt) per parameter array, CPU or a dormant CuPy
 ElementwiseKernel.  Here it is one fused HIP kernel over the flat parameter
 buffer (plus a norm pass when a GradientClipping hook is installed), bitwise
-equal to update_one_cpu's f32 arithmetic.
+equal to update_one_cpu's f32 arithmetic.  A NonbiasWeightDecay hook is
+folded into that kernel (g += rate * p after the clip, biases skipped).
 """
 from __future__ import annotations
 
@@ -22,6 +24,17 @@ class GradientClipping:
 
     def __init__(self, threshold: float):
         self.threshold = float(threshold)
+
+
+class NonbiasWeightDecay:
+    """nonbias_weight_decay.NonbiasWeightDecay(rate) (a3c_ale.py:227-228):
+    g += rate * p for every parameter that is not a bias, run after the
+    clip.  The update kernel does it (arl_net_set_weight_decay)."""
+
+    name = "NonbiasWeightDecay"
+
+    def __init__(self, rate: float):
+        self.rate = float(rate)
 
 
 class RMSpropAsync:
@@ -48,6 +61,18 @@ class RMSpropAsync:
         return self
 
     def add_hook(self, hook):
+        """GradientClipping, NonbiasWeightDecay or both in the reference's
+        order (a3c_ale.py:226-228: clip, then decay).  Chainer runs hooks in
+        insertion order; the fused update clips by the norm of the gradient
+        before the decay, so a clip added after a decay is refused."""
+        if not isinstance(hook, (GradientClipping, NonbiasWeightDecay)):
+            raise TypeError(f"RMSpropAsync.add_hook: unsupported hook {type(hook).__name__} "
+                            "(GradientClipping, NonbiasWeightDecay)")
+        if any(type(h) is type(hook) for h in self.hooks):
+            raise ValueError(f"RMSpropAsync.add_hook: a {hook.name} hook is already installed")
+        if isinstance(hook, GradientClipping) and self.hooks:
+            raise ValueError("RMSpropAsync.add_hook: GradientClipping after NonbiasWeightDecay would clip the "
+                             "decayed gradient; add the clip first (a3c_ale.py:226-228)")
         self.hooks.append(hook)
 
     @property
@@ -57,13 +82,24 @@ class RMSpropAsync:
                 return h.threshold
         return 0.0
 
+    @property
+    def weight_decay(self) -> float:
+        for h in self.hooks:
+            if isinstance(h, NonbiasWeightDecay):
+                return h.rate
+        return 0.0
+
     def update_args(self) -> dict:
         """The arguments of one update (net.optimize's, without the stream),
-        counting it (Chainer's Optimizer.t)."""
+        counting it (Chainer's Optimizer.t).  The NonbiasWeightDecay rate
+        (0 without the hook) goes to the bound model's net here, so every
+        update path -- update, A3C.run_window, A3C.act -- launches with it."""
         if self.anneal_total_steps > 0 and self.n_total_envs <= 0:
             # global_t per window = (window start + t_max) * n_total_envs: with 0
             # envs it never moves and the anneal would silently keep lr fixed
             raise ValueError("anneal_total_steps > 0 needs n_total_envs > 0 (envs over all ranks)")
+        if self.target is not None:
+            self.target.net.set_weight_decay(self.weight_decay)
         self.t += 1
         return dict(lr0=self.lr, total_steps=self.anneal_total_steps, n_total=self.n_total_envs, alpha=self.alpha,
                     eps=self.eps, clip=self.clip_threshold)
@@ -74,15 +110,24 @@ class RMSpropAsync:
         also end the lockstep window (arl_optimize_advance)."""
         self.target.net.optimize(stream=stream, advance=advance_window, **self.update_args())
 
-    def update_arrays(self, param: torch.Tensor, ms: torch.Tensor, grad: torch.Tensor, stream=None):
+    def update_arrays(self, param: torch.Tensor, ms: torch.Tensor, grad: torch.Tensor, stream=None,
+                      nonbias: bool = False):
         """update_one on explicit flat f32 device tensors (the drop-in for
-        RMSpropAsync.update_one_cpu / update_one_gpu on one array)."""
+        RMSpropAsync.update_one_cpu / update_one_gpu on one array).  nonbias:
+        the array is not a bias, so an installed NonbiasWeightDecay hook
+        applies to it (arl_rmsprop_wd)."""
         clip = self.clip_threshold
         if clip > 0 and self._scratch is None:
             self._scratch = torch.zeros(1024, dtype=torch.float64, device=param.device)
-        check(lib.arl_rmsprop(ptr(param), ptr(ms), ptr(grad), param.numel(), self.lr, self.alpha, self.eps,
-                              clip, ptr(self._scratch) if clip > 0 else None, stream_handle(stream)),
-              "arl_rmsprop")
+        rate = self.weight_decay if nonbias else 0.0
+        if rate > 0:
+            check(lib.arl_rmsprop_wd(ptr(param), ptr(ms), ptr(grad), param.numel(), self.lr, self.alpha, self.eps,
+                                     clip, ptr(self._scratch) if clip > 0 else None, rate, stream_handle(stream)),
+                  "arl_rmsprop_wd")
+        else:
+            check(lib.arl_rmsprop(ptr(param), ptr(ms), ptr(grad), param.numel(), self.lr, self.alpha, self.eps,
+                                  clip, ptr(self._scratch) if clip > 0 else None, stream_handle(stream)),
+                  "arl_rmsprop")
         # the kernel wrote `param` behind torch's back: a net whose params it aliases rebuilds its
         # derived FC planes before the next forward
         for net in nets_aliasing(param):

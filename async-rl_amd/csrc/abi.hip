@@ -1,6 +1,7 @@
 // C ABI of libasyncrl_hip.so (declared in include/asyncrl_hip.h).
 // Argument validation lives here; kernels assume validated shapes.
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -32,6 +33,8 @@ int hip_status(hipError_t e, const char* what) {
 }
 bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+// a weight-decay rate the update can take: >= 0 (not NaN) and finite as f32
+bool decay_rate_ok(double rate) { return rate >= 0.0 && rate <= (double)FLT_MAX; }
 }  // namespace
 
 extern "C" {
@@ -363,6 +366,13 @@ int arl_net_set_loss(arl_net* h, double pi_loss_coef, int keep_loss_scale_same) 
   return ARL_OK;
 }
 
+int arl_net_set_weight_decay(arl_net* h, double rate) {
+  if (!h) return fail(ARL_EINVAL, "null net");
+  if (!decay_rate_ok(rate)) return fail(ARL_EINVAL, "set_weight_decay: rate must be finite and >= 0");
+  h->net.decay.rate = (float)rate;
+  return ARL_OK;
+}
+
 int arl_act(arl_net* h, int t, void* s) {
   NEED_BOUND(h);
   if (t < 0 || t > h->net.T) return fail(ARL_EINVAL, "act: t out of [0, t_max]");
@@ -580,8 +590,9 @@ int arl_reset_state(arl_net* h, int64_t e0, int64_t n, void* s) {
   return hip_status(arl::net_reset_state(h->net, (int)e0, (int)n, S(s)), "reset_state");
 }
 
-int arl_rmsprop(float* p, float* ms, const float* g, int64_t n, double lr, double alpha, double eps, double clip,
-                double* parts, void* s) {
+// wd: null, or the decay of the whole array (no bias ranges)
+static int rmsprop_array(float* p, float* ms, const float* g, int64_t n, double lr, double alpha, double eps,
+                         double clip, double* parts, const arl::DecayArgs* wd, void* s) {
   if (n < 0 || (n > 0 && (!p || !ms || !g))) return fail(ARL_EINVAL, "rmsprop: null pointer / n < 0");
   if (!aligned(p, 16) || !aligned(ms, 16) || !aligned(g, 16)) return fail(ARL_EINVAL, "rmsprop: 16-byte alignment");
   if (clip > 0 && !parts) return fail(ARL_EINVAL, "rmsprop: clip needs norm_partials scratch");
@@ -590,8 +601,22 @@ int arl_rmsprop(float* p, float* ms, const float* g, int64_t n, double lr, doubl
   if (clip > 0) e = arl::launch_grad_sqnorm(g, n, parts, blocks, S(s));
   if (e == hipSuccess)
     e = arl::launch_rmsprop(p, ms, g, n, lr, alpha, eps, clip > 0 ? parts : nullptr, blocks, (float)clip, nullptr, 0,
-                            0, 0, S(s));
+                            0, 0, S(s), nullptr, wd);
   return hip_status(e, "rmsprop");
+}
+
+int arl_rmsprop(float* p, float* ms, const float* g, int64_t n, double lr, double alpha, double eps, double clip,
+                double* parts, void* s) {
+  return rmsprop_array(p, ms, g, n, lr, alpha, eps, clip, parts, nullptr, s);
+}
+
+int arl_rmsprop_wd(float* p, float* ms, const float* g, int64_t n, double lr, double alpha, double eps, double clip,
+                   double* parts, double weight_decay, void* s) {
+  if (!decay_rate_ok(weight_decay))
+    return fail(ARL_EINVAL, "rmsprop_wd: weight_decay must be finite and >= 0");
+  arl::DecayArgs wd{};
+  wd.rate = (float)weight_decay;
+  return rmsprop_array(p, ms, g, n, lr, alpha, eps, clip, parts, &wd, s);
 }
 
 int arl_policy(const float* hh, int64_t n, const float* Wpi, const float* bpi, const float* Wv, const float* bv,

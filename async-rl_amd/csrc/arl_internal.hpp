@@ -84,6 +84,16 @@ hipError_t launch_max_luminance(const uint8_t* cur, const uint8_t* prev, uint8_t
 hipError_t launch_dqn_phi(const uint8_t* in, float* out, int64_t count, hipStream_t s);
 
 // ---------------------------------------------------------------- network
+// NonbiasWeightDecay folded into the update (optim.hip): g += rate * p after the clip, except inside the
+// bias tensors' float ranges [begin[k], end[k]) of the flat layout (k < n_bias; net_init builds them from
+// the parameter names).  n_bias == 0: every element decays (one array, arl_rmsprop_wd).
+constexpr int DECAY_MAX_BIAS = 8;
+struct DecayArgs {
+  float rate;               // f32(rate), as the Python float meets the f32 arrays; 0: no decay
+  int n_bias;
+  int64_t begin[DECAY_MAX_BIAS], end[DECAY_MAX_BIAS];
+};
+
 struct ParamInfo {
   std::string name;   // Chainer namedparam / HDF5 path, e.g. "0/0/W"
   int64_t offset;     // floats into the flat buffer (64-float aligned)
@@ -113,6 +123,9 @@ struct Net {
   // loss options (a3c.py:110-121): pi_loss_coef, keep_loss_scale_same (arl_net_set_loss)
   float pi_coef = 1.f;
   int keep_scale = 0;
+  // NonbiasWeightDecay of the update: the rate (arl_net_set_weight_decay; 0 = the hook is not installed)
+  // and the bias tensors it skips, from the names in `params` (net_init)
+  DecayArgs decay{};
   int64_t eval_draws = 0;  // sampling forward_states calls so far (Philox stream 1 counter)
   // clip norm folded into the learner's conv reduce (arl_net_set_norm_fold; only valid when
   // nothing changes the gradient between arl_learn and the update, e.g. no all-reduce):
@@ -373,7 +386,7 @@ constexpr int NORM_MAX_PARTS = 1000, NORM_SCRATCH = 1024;
 hipError_t launch_rmsprop(float* p, float* ms, const float* g, int64_t n, double lr, double alpha, double eps,
                           const double* norm_sq, int nparts, float clip, const int64_t* ctl,
                           int64_t total_steps, int64_t n_total, int t_max, hipStream_t s,
-                          const AdvanceArgs* adv = nullptr);
+                          const AdvanceArgs* adv = nullptr, const DecayArgs* wd = nullptr);
 hipError_t launch_grad_sqnorm(const float* g, int64_t n, double* partials, int blocks, hipStream_t s);
 hipError_t launch_stream_copy(const void* src, void* dst, int64_t bytes, int blocks, int mode, hipStream_t s);
 hipError_t launch_policy(const float* h, int64_t n, const float* Wpi, const float* bpi, const float* Wv,

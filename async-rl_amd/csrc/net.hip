@@ -210,6 +210,15 @@ bool net_init(Net& net, int arch, int n_actions, int n_envs, int t_max, int env_
     net.o_vb = add("3/0/b", 1);
   }
   net.param_floats = off;
+  // the tensors NonbiasWeightDecay skips (nonbias_weight_decay.py:22: name == 'b' or name.endswith('/b'))
+  net.decay = DecayArgs{};
+  for (const ParamInfo& pi : net.params) {
+    const std::string& nm = pi.name;
+    if (nm != "b" && (nm.size() < 2 || nm.compare(nm.size() - 2, 2, "/b") != 0)) continue;
+    if (net.decay.n_bias == DECAY_MAX_BIAS) { err = "more bias tensors than DECAY_MAX_BIAS"; return false; }
+    net.decay.begin[net.decay.n_bias] = pi.offset;
+    net.decay.end[net.decay.n_bias++] = pi.offset + pi.numel;
+  }
   // ---- workspace
   const int64_t n = n_envs, T = t_max, T1 = T + 1, S = T * n, A = n_actions;
   net.norm_blocks = 256;
@@ -696,7 +705,7 @@ hipError_t net_optimize(Net& net, double lr0, int64_t total_steps, int64_t n_tot
   if (planes != nullptr) net.planes_gen = net.param_gen;
   ARL_TRY(launch_rmsprop(net.p, net.ms, net.g, net.param_floats, lr0, alpha, eps, do_clip ? parts : nullptr,
                          folded ? conv_norm_parts(net.norm_rest_blocks) : net.norm_blocks, clip, total_steps > 0 ? net.at<int64_t>(net.w_ctl) : nullptr, total_steps,
-                         n_total, net.T, s, &adv));
+                         n_total, net.T, s, &adv, &net.decay));
   ARL_TRY(stamp(net, STAGE_RMSPROP, s));
   return advance && !fused ? net_advance(net, s) : hipSuccess;
 }

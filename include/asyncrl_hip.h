@@ -183,6 +183,23 @@ int arl_truncate_window(arl_net* net, int t_len, void* stream);
  * Host state of the handle, read when arl_learn launches (defaults 1, 0). */
 int arl_net_set_loss(arl_net* net, double pi_loss_coef, int keep_loss_scale_same);
 
+/* NonbiasWeightDecay(rate) (a3c_ale.py:204,227-228, nonbias_weight_decay.py),
+ * the hook the reference adds after GradientClipping: per update, after the
+ * clip (whose norm is the norm of the gradient BEFORE the decay) and before
+ * update_one, g += rate * p -- t = f32(f32(rate) * p), g = f32(g + t), two
+ * roundings -- for every parameter whose name is not 'b' and does not end in
+ * '/b'.  The update kernel does it on the p / g it holds in registers (no
+ * extra byte moved); the bias tensors come from the names arl_net_param_info
+ * serves.  Every architecture and flag, the Nature head included.
+ * Host state of the handle, like arl_net_set_loss (works on an unbound handle),
+ * read when arl_optimize / arl_optimize_advance / arl_run_window launches the
+ * update; default 0 = no hook: the decay-free kernel runs (a rate whose f32
+ * value is 0 does too).  rate < 0 or not finite (as f32): ARL_EINVAL.  The
+ * rate is a kernel argument, so a captured graph keeps the rate it was
+ * captured with (as it keeps lr0): changing it needs a re-capture.
+ * arl_run_stage(ARL_STAGE_RMSPROP) stays the decay-free timing form. */
+int arl_net_set_weight_decay(arl_net* net, double rate);
+
 /* GradientClipping's squared norm (a3c_ale.py:226) folded into arl_learn:
  * with on != 0, arl_learn's conv slab reduce also leaves the f64 partial
  * sums of squares of the whole gradient (the conv tensors it writes, and the
@@ -352,6 +369,14 @@ int arl_reset_state(arl_net* net, int64_t e0, int64_t n, void* stream);
  * pass's per-block partials. */
 int arl_rmsprop(float* param, float* ms, const float* grad, int64_t n, double lr, double alpha, double eps,
                 double clip, double* norm_partials, void* stream);
+
+/* arl_rmsprop with NonbiasWeightDecay(weight_decay) on the whole array: after
+ * the clip (norm of grad as given), g' = f32(g + f32(f32(weight_decay) *
+ * param)) feeds update_one; grad itself is not written.  The reference's hook
+ * loops over the arrays and skips the biases: pass 0 for a bias array (that is
+ * arl_rmsprop).  weight_decay < 0 or not finite: ARL_EINVAL. */
+int arl_rmsprop_wd(float* param, float* ms, const float* grad, int64_t n, double lr, double alpha, double eps,
+                   double clip, double* norm_partials, double weight_decay, void* stream);
 
 /* SoftmaxPolicyOutput (policy_output.py:32-61) + FCSoftmaxPolicy / FCVFunction
  * heads (policy.py:53-58, v_function.py:29-34) for h: (n, 256) f32.  Samples
