@@ -96,6 +96,9 @@ SIGNATURES = {
                                      c_int, c_double, c_double, c_double, c_double, c_int, c_int, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
     "arl_stream_copy": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p]),
+    "arl_net_set_episode_stats": (c_int, [c_void_p, c_int]),
+    "arl_episode_stats_reset": (c_int, [c_void_p, c_void_p]),
+    "arl_episode_stats": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
@@ -119,6 +122,10 @@ ACT_AFTER_CONV = 8
 ENV_GROUP_ALIGN = 32   # arl_observe_envs / arl_act_envs: e0 % ENV_GROUP_ALIGN == 0
 LEARN_RETURNS, LEARN_TRUNK, LEARN_CONV = range(3)
 POOL_FRAMES, POOL_REWARDS, POOL_DONES = range(3)   # arl_net_set_pool kinds
+EPISODE_LOG = 8        # ARL_EPISODE_LOG: episodes per env the device-side episode log keeps
+# the 8 doubles of arl_episode_stats, in order
+EPISODE_STAT_FIELDS = ("episodes", "return_sum", "return_sumsq", "return_min", "return_max", "length_sum", "steps",
+                       "reward_sum")
 # window timeline stages (arl_stamps_*): arl_run_stage's 1..11, then the stamp-only ones
 STAGE_NAMES = {1: "conv_fwd", 2: "fc_fwd", 3: "policy", 4: "fc_bwd", 5: "conv_bwd", 6: "returns", 7: "conv_reduce",
                8: "grad_sqnorm", 9: "lstm_gates", 10: "lstm_bptt", 11: "lstm_wgrad", 12: "phi", 13: "rmsprop",

@@ -42,12 +42,14 @@ import os
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from ._lib import (ACT_AFTER_CONV, ACT_CONV_ONLY, ARCH_FF, ARCH_FF_NATURE, ARCH_LSTM, ARCH_RGB, ARCH_STACK,
                    ARCH_STATES, LEARN_CONV, RESIZE_SCALAR)
 from .dqn_phi import dqn_phi as _device_dqn_phi
-from .distributed import allreduce_grads, dist_initialized, world_info
-from .net import DeviceNet, init_like_torch
+from .distributed import (allreduce_grads, dist_initialized, gather_episode_stats, merge_episode_stats,
+                          world_info)
+from .net import DeviceNet, episode_stats_dict, init_like_torch
 from . import serializers
 from .policy_output import SoftmaxPolicyOutput
 
@@ -268,6 +270,19 @@ class A3C:
 
     def sync_parameters(self):
         """a3c.py:63-65 -- a no-op: actors read the device parameters."""
+
+    def episode_stats(self, clear: bool = False, reduce: bool = True, stream=None) -> dict:
+        """The learning curve of train_loop (a3c_ale.py:95-96,114-124) from the
+        device-side episode statistics (net.set_episode_stats() first): one
+        reduce launch and one 64-byte copy, no per-step host work.  With an
+        initialised process group and reduce=True every rank's 8 values are
+        gathered and merged (merge_episode_stats), so all ranks return the
+        statistics of all envs; every rank must call it."""
+        v = self.net.episode_stats_raw(clear, stream)
+        if reduce and dist_initialized():
+            dev = self.net.device if dist.get_backend(self.pg) == "nccl" else "cpu"
+            v = merge_episode_stats(gather_episode_stats(torch.as_tensor(v, dtype=torch.float64, device=dev), self.pg))
+        return episode_stats_dict(v)
 
     # ------------------------------------------------------------ window pieces
     def _overlap_allreduce(self) -> bool:

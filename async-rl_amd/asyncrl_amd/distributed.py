@@ -46,6 +46,33 @@ def allreduce_grads(grads: torch.Tensor, group=None, async_op: bool = False, for
     return None
 
 
+def merge_episode_stats(vectors):
+    """Merge the 8 doubles of arl_episode_stats of several ranks, in rank
+    order: [episodes, return_sum, return_sumsq, return_min, return_max,
+    length_sum, steps, reward_sum] -- SUM for the counts and sums, MIN / MAX
+    for the extrema (a rank without an episode holds +inf / -inf there, the
+    identities).  Pure host arithmetic; returns a list of 8 floats."""
+    vs = [[float(x) for x in v] for v in vectors]
+    if not vs or any(len(v) != 8 for v in vs):
+        raise ValueError("merge_episode_stats: need at least one vector of 8 values")
+    out = list(vs[0])
+    for v in vs[1:]:
+        for i in (0, 1, 2, 5, 6, 7):
+            out[i] += v[i]
+        out[3] = min(out[3], v[3])
+        out[4] = max(out[4], v[4])
+    return out
+
+
+def gather_episode_stats(v: torch.Tensor, group=None):
+    """All-gather one rank's 8 doubles (a device tensor for RCCL, a host one
+    for gloo); returns the ranks' vectors in rank order as lists."""
+    world, _ = world_info(group)
+    out = [torch.zeros_like(v) for _ in range(world)]
+    dist.all_gather(out, v, group=group)
+    return [o.cpu().tolist() for o in out]
+
+
 def replica_checksum(t: torch.Tensor) -> int:
     """Order-dependent 64-bit hash of the raw bits (equal iff bitwise equal,
     up to hash collisions)."""

@@ -36,17 +36,27 @@ import statistics
 
 import numpy as np
 
+from ._lib import EPISODE_LOG
+
 MODE_SAMPLE, MODE_GREEDY = 1, 2
 
 
 def run_episodes(model, vec_env, n_runs: int, deterministic: bool = False, max_steps: int | None = None,
-                 stream=None):
+                 stream=None, scores: str = "host"):
     """Run `n_runs` evaluation episodes over `vec_env` (a VecALE with exactly
     model.net.n_envs envs, not the training learner's: its games restart)
     with the model's lockstep workspace.  Returns
     (scores, trace): scores[k] is the raw reward sum of run k (run k = env
     k % N's (k // N)-th episode); trace holds per-step host copies of the
-    actions and done flags, (steps, N) each, for checking."""
+    actions and done flags, (steps, N) each, for checking.
+
+    scores="host" sums each step's rewards on the host.  scores="device" leaves
+    that to the device-side episode statistics (DeviceNet.set_episode_stats):
+    the loop copies only the done flags, to know when to stop, and the scores
+    are read once at the end from the episode log -- run k * N + i is log entry
+    k of env i -- so no env may need more than EPISODE_LOG episodes.  It
+    resets the net's episode statistics (the evaluation model is its own)
+    and leaves the feature switched as it found it."""
     net = model.net
     N, T = net.n_envs, net.t_max
     if vec_env.n != N:
@@ -55,9 +65,16 @@ def run_episodes(model, vec_env, n_runs: int, deterministic: bool = False, max_s
         raise ValueError("eval: n_runs must be >= 1")
     if getattr(model, "frames", "pairs") != "pairs":
         raise ValueError("eval: the model must take frame pairs (frames='pairs')")
+    if scores not in ("host", "device"):
+        raise ValueError("eval: scores must be 'host' or 'device'")
+    on_device = scores == "device"
     mode = MODE_GREEDY if deterministic else MODE_SAMPLE
     need = [len(range(i, n_runs, N)) for i in range(N)]     # episodes env i must finish
+    if on_device and max(need) > EPISODE_LOG:
+        raise ValueError(f"eval: scores='device' keeps {EPISODE_LOG} episodes per env, {n_runs} runs over {N} envs "
+                         f"need {max(need)}")
     saved = [e.treat_life_lost_as_terminal for e in vec_env.envs]
+    stats_were_on = net.episode_stats_on
     scores = np.zeros(n_runs, np.float64)
     trace_a, trace_d = [], []
     try:
@@ -70,6 +87,9 @@ def run_episodes(model, vec_env, n_runs: int, deterministic: bool = False, max_s
         pairs, r, d = vec_env.reset(stream)
         done_eps = [0] * N
         acc = np.zeros(N, np.float64)
+        if on_device:
+            net.set_episode_stats(True)
+            net.episode_stats_reset(stream)
         # slots 0..T-1 of a window, then advance: slot 0 of the next window is
         # the ring position observe(T) filled, its reset flags and LSTM carry
         # (hbuf[T] = the state after slot T-1) moved there, exactly as the
@@ -82,10 +102,16 @@ def run_episodes(model, vec_env, n_runs: int, deterministic: bool = False, max_s
             net.act(t, mode=mode, stream=stream)
             acts = net.step_outputs(t)["actions"].clone()
             pairs, r, d = vec_env.step(acts, stream)
-            hr, hd = r.cpu().numpy(), d.cpu().numpy()
+            hd = d.cpu().numpy()
             trace_a.append(acts.cpu().numpy())
             trace_d.append(hd.copy())
-            for i in range(N):
+            if on_device:                        # the observe below accumulates r on the device
+                for i in np.flatnonzero(hd):
+                    done_eps[i] += 1
+                hr = None
+            else:
+                hr = r.cpu().numpy()
+            for i in range(N if hr is not None else 0):
                 if done_eps[i] >= need[i]:
                     continue                     # this env's runs are complete: its steps are ignored
                 acc[i] += float(hr[i])
@@ -99,7 +125,17 @@ def run_episodes(model, vec_env, n_runs: int, deterministic: bool = False, max_s
             if t == T:
                 net.advance(stream)
                 t = 0
+        if on_device:
+            log = net.episode_log()
+            count, ret = log["count"].cpu().numpy(), log["ret"].cpu().numpy()
+            if int(count.max()) > EPISODE_LOG:    # an env played on past the log's depth while others finished
+                raise RuntimeError(f"eval: an env finished {int(count.max())} episodes, the episode log keeps "
+                                   f"{EPISODE_LOG}; use scores='host'")
+            for i in range(N):
+                for k in range(need[i]):
+                    scores[k * N + i] = ret[k, i]
     finally:
+        net.set_episode_stats(stats_were_on)
         for e, s in zip(vec_env.envs, saved):
             e.treat_life_lost_as_terminal = s
     return scores, {"actions": np.array(trace_a), "dones": np.array(trace_d)}

@@ -10,14 +10,15 @@ compute is in libasyncrl_hip.so.
 from __future__ import annotations
 
 import ctypes
+import math
 import weakref
 
 import numpy as np
 import torch
 
-from ._lib import (ARCH_FF, ARCH_FF_NATURE, ARCH_LSTM, ARCH_RGB, ARCH_STACK, ARCH_STATES, ENV_GROUP_ALIGN, FWD_KEEP_STATE,
-                   POOL_DONES, POOL_FRAMES, POOL_REWARDS, RESIZE_SCALAR, STAGE_HOST, STAGE_NAMES, check, lib, ptr,
-                   stream_handle)
+from ._lib import (ARCH_FF, ARCH_FF_NATURE, ARCH_LSTM, ARCH_RGB, ARCH_STACK, ARCH_STATES, ENV_GROUP_ALIGN,
+                   EPISODE_LOG, EPISODE_STAT_FIELDS, FWD_KEEP_STATE, POOL_DONES, POOL_FRAMES, POOL_REWARDS,
+                   RESIZE_SCALAR, STAGE_HOST, STAGE_NAMES, check, lib, ptr, stream_handle)
 
 
 def param_shapes(arch: int, n_actions: int):
@@ -81,6 +82,22 @@ def check_pools(pool_len: int, *pools):
     for p in pools:
         if p is not None and isinstance(p, torch.Tensor) and (p.dim() == 0 or p.shape[0] < pool_len):
             raise ValueError(f"pool_len {pool_len} exceeds a pool of shape {tuple(p.shape)}")
+
+
+def episode_stats_dict(v) -> dict:
+    """The 8 doubles of arl_episode_stats as a dict, plus what the host derives:
+    mean and mean_length (nan without an episode), stdev (sample standard
+    deviation; nan below two episodes)."""
+    d = {k: float(x) for k, x in zip(EPISODE_STAT_FIELDS, v)}
+    for k in ("episodes", "length_sum", "steps"):
+        d[k] = int(d[k])
+    n = d["episodes"]
+    nan = float("nan")
+    d["mean"] = d["return_sum"] / n if n else nan
+    d["mean_length"] = d["length_sum"] / n if n else nan
+    d["stdev"] = math.sqrt(max(d["return_sumsq"] - d["return_sum"] ** 2 / n, 0.0) / (n - 1)) if n > 1 else nan
+    return d
+
 
 class DeviceNet:
     """One arl_net handle + the device memory it borrows."""
@@ -283,6 +300,47 @@ class DeviceNet:
         after the clip, g += rate * p for every non-bias parameter; 0 = off.
         A captured window keeps the rate it was captured with."""
         check(lib.arl_net_set_weight_decay(self._h, float(rate)), "arl_net_set_weight_decay")
+
+    # ------------------------------------------------------------ episode statistics
+    episode_stats_on = False
+
+    def set_episode_stats(self, on: bool = True):
+        """Accumulate episode returns / lengths on the device while observing
+        (arl_net_set_episode_stats; a3c_ale.py:114-124 episode_r, total_r).
+        Off by default; a captured window keeps the setting it was captured with."""
+        check(lib.arl_net_set_episode_stats(self._h, int(on)), "arl_net_set_episode_stats")
+        self.episode_stats_on = bool(on)
+
+    def episode_stats_reset(self, stream=None):
+        """Zero the whole episode-statistics block (arl_episode_stats_reset)."""
+        check(lib.arl_episode_stats_reset(self._h, stream_handle(stream)), "arl_episode_stats_reset")
+
+    def episode_stats_raw(self, clear: bool = False, stream=None) -> np.ndarray:
+        """The 8 doubles of arl_episode_stats (EPISODE_STAT_FIELDS order): one
+        reduce launch and one 64-byte copy to the host, which waits for it."""
+        s = stream if stream is not None else torch.cuda.current_stream()
+        out = getattr(self, "_ep_out", None)
+        if out is None:
+            out = self._ep_out = torch.zeros(8, dtype=torch.float64, device=self.device)
+        with torch.cuda.stream(s):
+            check(lib.arl_episode_stats(self._h, ptr(out), int(clear), stream_handle(s)), "arl_episode_stats")
+            return out.cpu().numpy()
+
+    def episode_stats(self, clear: bool = False, stream=None) -> dict:
+        """Statistics of the episodes completed since the last reset (or the
+        last clear=True read): the 8 reduced values plus mean, stdev (the
+        sample standard deviation, as statistics.stdev) and mean_length."""
+        return episode_stats_dict(self.episode_stats_raw(clear, stream))
+
+    def episode_log(self) -> dict:
+        """Device views of the per-env episode log: count (n,) episodes ever
+        logged, and ret / len / step (EPISODE_LOG, n): entry k % EPISODE_LOG of
+        env i is its k-th episode's return, length and global observation index."""
+        n, L = self.n_envs, EPISODE_LOG
+        return {"count": self.buffer("ep_log_count", torch.int64, (n,)),
+                "ret": self.buffer("ep_log_ret", torch.float64, (L, n)),
+                "len": self.buffer("ep_log_len", torch.int64, (L, n)),
+                "step": self.buffer("ep_log_step", torch.int64, (L, n))}
 
     def reset_state(self, e0: int = 0, n: int | None = None, stream=None):
         """LSTM: the pi_and_v recurrent state of rows [e0, e0 + n) -> None (arl_reset_state)."""

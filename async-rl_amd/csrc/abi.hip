@@ -192,7 +192,31 @@ int arl_net_reset(arl_net* h, void* s) {
     if (e == hipSuccess) e = hipMemsetAsync(n.ws + n.w_eval_reset, 1, (size_t)n.N, S(s));
     if (e == hipSuccess) e = hipMemsetAsync(n.ws + n.w_zero, 0, arl::ZERO_ROW_FLOATS * 4, S(s));
   }
+  if (e == hipSuccess) e = arl::launch_episode_reset(n.ws + n.w_episodes, n.N, S(s));
   return hip_status(e, "net_reset");
+}
+
+static_assert(arl::EPISODE_LOG == ARL_EPISODE_LOG, "episode log depth");
+
+int arl_net_set_episode_stats(arl_net* h, int on) {
+  NEED_BOUND(h);
+  h->net.episode_stats = on != 0;
+  return ARL_OK;
+}
+
+int arl_episode_stats_reset(arl_net* h, void* s) {
+  NEED_BOUND(h);
+  arl::Net& n = h->net;
+  return hip_status(arl::launch_episode_reset(n.ws + n.w_episodes, n.N, S(s)), "episode_stats_reset");
+}
+
+int arl_episode_stats(arl_net* h, double* out8_device, int clear, void* s) {
+  NEED_BOUND(h);
+  arl::Net& n = h->net;
+  if (!n.episode_stats) return fail(ARL_ESTATE, "episode_stats: the feature is off (arl_net_set_episode_stats)");
+  if (!out8_device || !aligned(out8_device, 8)) return fail(ARL_EINVAL, "episode_stats: out8 null / not 8-byte aligned");
+  return hip_status(arl::launch_episode_reduce(n.ws + n.w_episodes, n.N, out8_device, clear ? 1 : 0, S(s)),
+                    "episode_stats");
 }
 
 int arl_net_set_pool(arl_net* h, int kind, const void* pool, int64_t bytes) {
@@ -277,6 +301,7 @@ static int ring_args(arl_net* h, int t, const uint8_t* pool, const float* reward
   a.e0 = e0;
   a.ne = ne;
   a.esize = n.layout == arl::FRAMES_STATES ? 4 : 1;
+  a.episodes = n.episode_stats ? n.ws + n.w_episodes : nullptr;
   return 0;
 }
 

@@ -66,7 +66,57 @@ struct RingArgs {
   int H = 0, W = 0;           // RGB nets: pair_pool is an image pool (pool_len, n, H, W, 3)
   int e0 = 0, ne = -1;        // env range of this launch: e0 + blockIdx.y, ne envs (-1: all n)
   int esize = 1;              // stack_ring_kernel: bytes per stack element (1 uint8 screens, 4 f32 states)
+  char* episodes = nullptr;   // episode-statistics block (EpisodeView below); null: the feature is off
 };
+
+// Device-side episode statistics (arl_net_set_episode_stats; a3c_ale.py:95-96,114-124: episode_r / total_r of
+// train_loop).  One block at the end of the workspace, 14 arrays of 8-byte elements, each starting 256-byte
+// aligned in this order: 11 per-env arrays (n) and 3 logs (EPISODE_LOG, n).  The env's bookkeeping thread of the
+// ring kernels is the only writer of column e (no atomics); all sums are f64 with explicit *_rn ops, so a NumPy
+// f64 replay in env-step order is bit-identical.
+constexpr int EPISODE_LOG = 8;
+constexpr int EP_ENV_ARRAYS = 11, EP_LOG_ARRAYS = 3;
+__host__ __device__ constexpr int64_t ep_align(int64_t b) { return (b + 255) / 256 * 256; }
+__host__ __device__ constexpr int64_t episode_block_bytes(int64_t n) {
+  return EP_ENV_ARRAYS * ep_align(n * 8) + EP_LOG_ARRAYS * ep_align(EPISODE_LOG * n * 8);
+}
+struct EpisodeView {
+  double* run_ret;      // return of the running episode
+  int64_t* run_len;     // its length so far
+  double* total;        // sum of every reward ingested (total_r)
+  int64_t* steps;       // rewards ingested
+  int64_t* count;       // episodes completed
+  double *sum, *sumsq, *mn, *mx;   // of the completed episodes' returns (count 0: mn = +inf, mx = -inf)
+  int64_t* len_sum;     // sum of their lengths
+  int64_t* log_count;   // episodes ever appended to the log (not cleared by a reduce)
+  double* log_ret;      // (EPISODE_LOG, n): entry count % EPISODE_LOG of env e = (return, length, obs index)
+  int64_t *log_len, *log_step;
+};
+__host__ __device__ inline EpisodeView episode_view(char* base, int64_t n) {
+  const int64_t se = ep_align(n * 8), sl = ep_align(EPISODE_LOG * n * 8);
+  EpisodeView v;
+  v.run_ret = reinterpret_cast<double*>(base);
+  v.run_len = reinterpret_cast<int64_t*>(base + se);
+  v.total = reinterpret_cast<double*>(base + 2 * se);
+  v.steps = reinterpret_cast<int64_t*>(base + 3 * se);
+  v.count = reinterpret_cast<int64_t*>(base + 4 * se);
+  v.sum = reinterpret_cast<double*>(base + 5 * se);
+  v.sumsq = reinterpret_cast<double*>(base + 6 * se);
+  v.mn = reinterpret_cast<double*>(base + 7 * se);
+  v.mx = reinterpret_cast<double*>(base + 8 * se);
+  v.len_sum = reinterpret_cast<int64_t*>(base + 9 * se);
+  v.log_count = reinterpret_cast<int64_t*>(base + 10 * se);
+  char* lg = base + EP_ENV_ARRAYS * se;
+  v.log_ret = reinterpret_cast<double*>(lg);
+  v.log_len = reinterpret_cast<int64_t*>(lg + sl);
+  v.log_step = reinterpret_cast<int64_t*>(lg + 2 * sl);
+  return v;
+}
+// zero the whole block of n envs (mn = +inf, mx = -inf)
+hipError_t launch_episode_reset(char* block, int n, hipStream_t s);
+// out8 = [episodes, return_sum, return_sumsq, return_min, return_max, length_sum, steps, reward_sum] over the n
+// envs in a fixed order (phi.hip episode_reduce_kernel); clear: also zero the cumulative per-env arrays
+hipError_t launch_episode_reduce(char* block, int n, double* out8, int clear, hipStream_t s);
 
 // RGB (Doom) observations, train_a3c_doom.py:21-23 / doom_env.py:47
 constexpr int RGB_MAX_W = 2048;   // staged source rows: 12 x W x 3 bytes of LDS
@@ -145,6 +195,7 @@ struct Net {
   bool fuse_returns = false, returns_done = false;
   ReturnsCfg ret{};
   int norm_rest_blocks = 64;
+  bool episode_stats = false;   // arl_net_set_episode_stats: the observations accumulate into w_episodes
   int hid;                 // width of the layer the heads read (256 NIPS / LSTM, 512 Nature)
   int env_offset;          // global id of env 0 on this rank (RNG stream)
   uint64_t seed;
@@ -162,6 +213,7 @@ struct Net {
       w_dG, w_dhn, w_dcn, w_da2, w_slab, w_norm, w_loss, w_tick, w_fcb_part = 0, w_fcb_tick = 0, w_zero = 0,
       w_a2m = 0,   // (T+1, N, 81) a2 > 0 bits (ring-frame NIPS nets; 0: none)
       w_fcplanes = 0;   // FC_PLANES_BYTES: the FC weight's bf16 split planes (NIPS nets)
+  int64_t w_episodes = 0;   // episode_block_bytes(N): the episode statistics (EpisodeView), last in the workspace
   int64_t w_a3 = 0, w_da1 = 0, w_da3 = 0;   // Nature head only (w_da1 also ARCH_STATES)
   // LSTM recurrent state of pi_and_v on explicit states (A3CLSTM.pi_and_v, a3c_ale.py:55-63):
   // h, c (n, 256), the step's outputs hn, cn, and reset flags (1 = state is None)

@@ -283,6 +283,13 @@ bool net_init(Net& net, int arch, int n_actions, int n_envs, int t_max, int env_
   net.w_eval_reset = buf("eval_reset", L ? n : 0);
   net.w_zero = buf("zero_row", L ? ZERO_ROW_FLOATS * 4 : 0);
   net.w_fcplanes = buf("fc_planes", NAT ? 0 : FC_PLANES_BYTES);
+  // episode statistics: the 14 arrays of EpisodeView, in its order (episode_view computes the same offsets)
+  net.w_episodes = wo;
+  for (const char* nm : {"ep_run_ret", "ep_run_len", "ep_total", "ep_steps", "ep_count", "ep_sum", "ep_sumsq", "ep_min",
+                         "ep_max", "ep_len_sum", "ep_log_count"})
+    buf(nm, n * 8);
+  for (const char* nm : {"ep_log_ret", "ep_log_len", "ep_log_step"}) buf(nm, (int64_t)EPISODE_LOG * n * 8);
+  if (wo - net.w_episodes != episode_block_bytes(n)) { err = "episode statistics layout"; return false; }
   net.ws_bytes = wo;
   return true;
 }

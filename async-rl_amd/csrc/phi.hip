@@ -135,6 +135,7 @@ phi_stack_kernel(const uint8_t* __restrict__ pairs, const uint8_t* __restrict__ 
 // nvalid[slot][e] = reset ? 1 : min(nvalid[prev slot][e] + 1, 4).  Also
 // ingests the reward / done that arrived with this obs (a3c.py:69-70,75):
 // rewards[t-1], dones[t-1] (t >= 1) and reset_flags[t].
+template <bool EP>   // EP: with the episode statistics (launched when a.episodes != null)
 __global__ void __launch_bounds__(256)
 phi_ring_kernel(RingArgs a) {
   __shared__ PhiShared sh;
@@ -145,7 +146,7 @@ phi_ring_kernel(RingArgs a) {
   const uint8_t* pr = a.pair_pool + (pidx * a.n + e) * (int64_t)(2 * FRAME_BYTES);
   uint8_t* dst = a.frames + ((int64_t)slot * a.n + e) * PLANE;
   phi_band(pr, pr + FRAME_BYTES, dst, blockIdx.x * BAND, a.mode, sh);
-  if (blockIdx.x == 0 && threadIdx.x == 0) ring_obs_store(a, e, k, ring_obs_load(a, e, k));
+  if (blockIdx.x == 0 && threadIdx.x == 0) ring_obs_store<EP>(a, e, k, ring_obs_load(a, e, k));
 }
 
 // ---------------------------------------------------------------- RGB (Doom)
@@ -245,6 +246,7 @@ rgb_phi_kernel(const uint8_t* __restrict__ imgs, int H, int W, float* __restrict
 // In-loop ring for RGB nets: the 3 planes of obs step k go to slot k % R
 // (frames (R, n, 3, 84, 84)); nvalid = 3 (conv input = [0, R, G, B]); the
 // reward / done / reset bookkeeping of phi_ring_kernel.
+template <bool EP>
 __global__ void __launch_bounds__(256)
 rgb_ring_kernel(RingArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t rgb_rows[];
@@ -261,11 +263,13 @@ rgb_ring_kernel(RingArgs a) {
     const bool rs = a.force_reset || d != 0;
     a.nvalid[(int64_t)slot * a.n + e] = 3;
     a.reset_flags[(int64_t)a.t * a.n + e] = rs ? 1 : 0;
+    float r = 0.f;
     if (a.t >= 1) {
-      float r = a.reward_pool ? a.reward_pool[pidx * a.n + e] : 0.f;
+      r = a.reward_pool ? a.reward_pool[pidx * a.n + e] : 0.f;
       a.rewards[(int64_t)(a.t - 1) * a.n + e] = r;
       a.dones[(int64_t)(a.t - 1) * a.n + e] = d;
     }
+    if (EP) episode_ingest(a, e, k, r, d);
   }
 }
 
@@ -275,6 +279,7 @@ rgb_ring_kernel(RingArgs a) {
 // phi_ring_kernel.  pair_pool == null: bookkeeping only (a terminal
 // observation, whose state a3c.py:72-73 never reads).  One workgroup per env,
 // 16-byte copies.
+template <bool EP>
 __global__ void __launch_bounds__(256)
 stack_ring_kernel(RingArgs a) {
   const int e = a.e0 + blockIdx.x;
@@ -295,11 +300,13 @@ stack_ring_kernel(RingArgs a) {
       a.nvalid[(int64_t)slot * a.n + e] = 4;
       a.reset_flags[(int64_t)a.t * a.n + e] = rs ? 1 : 0;
     }
+    float r = 0.f;
     if (a.t >= 1) {
-      float r = a.reward_pool ? a.reward_pool[pidx * a.n + e] : 0.f;
+      r = a.reward_pool ? a.reward_pool[pidx * a.n + e] : 0.f;
       a.rewards[(int64_t)(a.t - 1) * a.n + e] = r;
       a.dones[(int64_t)(a.t - 1) * a.n + e] = d;
     }
+    if (EP) episode_ingest(a, e, k, r, d);
   }
 }
 
@@ -334,6 +341,99 @@ __global__ void max_luminance_kernel(const uint8_t* __restrict__ cur, const uint
   gray[i] = (uint8_t)luminance(r, g, b);
 }
 
+// ---------------------------------------------------------------- episode statistics
+// arl_net_reset / arl_episode_stats_reset: the whole block of EpisodeView, one thread per env
+__global__ void __launch_bounds__(256)
+episode_reset_kernel(char* block, int n) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  const EpisodeView v = episode_view(block, n);
+  v.run_ret[e] = 0.0;
+  v.run_len[e] = 0;
+  v.total[e] = 0.0;
+  v.steps[e] = 0;
+  v.count[e] = 0;
+  v.sum[e] = 0.0;
+  v.sumsq[e] = 0.0;
+  v.mn[e] = INFINITY;
+  v.mx[e] = -INFINITY;
+  v.len_sum[e] = 0;
+  v.log_count[e] = 0;
+  for (int i = 0; i < EPISODE_LOG; ++i) {
+    v.log_ret[(int64_t)i * n + e] = 0.0;
+    v.log_len[(int64_t)i * n + e] = 0;
+    v.log_step[(int64_t)i * n + e] = 0;
+  }
+}
+
+// arl_episode_stats: one 256-thread workgroup.  Thread j accumulates envs e = j, j + 256, ... in
+// ascending order (f64 *_rn sums; counts in int64, exact), thread 0 then combines partials 0..255 in
+// order -- a fixed order a test replays bit for bit.  out8 = [episodes, return_sum, return_sumsq,
+// return_min, return_max, length_sum, steps, reward_sum].  clear: each thread also zeroes the
+// cumulative arrays it just read (not the running episode, not the log): "since the last read".
+__global__ void __launch_bounds__(256)
+episode_reduce_kernel(char* block, int n, double* __restrict__ out8, int clear) {
+  __shared__ double pd[5][256];
+  __shared__ int64_t pi[3][256];
+  const EpisodeView v = episode_view(block, n);
+  const int j = threadIdx.x;
+  double sum = 0.0, sumsq = 0.0, mn = INFINITY, mx = -INFINITY, total = 0.0;
+  int64_t cnt = 0, len = 0, steps = 0;
+  for (int e = j; e < n; e += 256) {
+    cnt += v.count[e];
+    sum = __dadd_rn(sum, v.sum[e]);
+    sumsq = __dadd_rn(sumsq, v.sumsq[e]);
+    const double a = v.mn[e], b = v.mx[e];
+    if (a < mn) mn = a;
+    if (b > mx) mx = b;
+    len += v.len_sum[e];
+    steps += v.steps[e];
+    total = __dadd_rn(total, v.total[e]);
+    if (clear) {
+      v.count[e] = 0;
+      v.sum[e] = 0.0;
+      v.sumsq[e] = 0.0;
+      v.mn[e] = INFINITY;
+      v.mx[e] = -INFINITY;
+      v.len_sum[e] = 0;
+      v.steps[e] = 0;
+      v.total[e] = 0.0;
+    }
+  }
+  pd[0][j] = sum; pd[1][j] = sumsq; pd[2][j] = mn; pd[3][j] = mx; pd[4][j] = total;
+  pi[0][j] = cnt; pi[1][j] = len; pi[2][j] = steps;
+  __syncthreads();
+  if (j != 0) return;
+  for (int q = 1; q < 256; ++q) {
+    sum = __dadd_rn(sum, pd[0][q]);
+    sumsq = __dadd_rn(sumsq, pd[1][q]);
+    if (pd[2][q] < mn) mn = pd[2][q];
+    if (pd[3][q] > mx) mx = pd[3][q];
+    total = __dadd_rn(total, pd[4][q]);
+    cnt += pi[0][q];
+    len += pi[1][q];
+    steps += pi[2][q];
+  }
+  out8[0] = (double)cnt;
+  out8[1] = sum;
+  out8[2] = sumsq;
+  out8[3] = mn;
+  out8[4] = mx;
+  out8[5] = (double)len;
+  out8[6] = (double)steps;
+  out8[7] = total;
+}
+
+hipError_t launch_episode_reset(char* block, int n, hipStream_t s) {
+  hipLaunchKernelGGL(episode_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, block, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_episode_reduce(char* block, int n, double* out8, int clear, hipStream_t s) {
+  hipLaunchKernelGGL(episode_reduce_kernel, dim3(1), dim3(256), 0, s, block, n, out8, clear);
+  return hipGetLastError();
+}
+
 hipError_t launch_max_luminance(const uint8_t* cur, const uint8_t* prev, uint8_t* gray, int64_t npix,
                                 hipStream_t s) {
   if (npix <= 0) return hipSuccess;
@@ -358,12 +458,16 @@ hipError_t launch_phi_stack(const uint8_t* pairs, const uint8_t* prev_stack, con
 }
 
 hipError_t launch_phi_ring(const RingArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(phi_ring_kernel, dim3(NBANDS, (unsigned)(a.ne < 0 ? a.n : a.ne)), dim3(256), 0, s, a);
+  const dim3 grid(NBANDS, (unsigned)(a.ne < 0 ? a.n : a.ne));
+  if (a.episodes != nullptr) hipLaunchKernelGGL(phi_ring_kernel<true>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(phi_ring_kernel<false>, grid, dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_stack_ring(const RingArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(stack_ring_kernel, dim3((unsigned)(a.ne < 0 ? a.n : a.ne)), dim3(256), 0, s, a);
+  const dim3 grid((unsigned)(a.ne < 0 ? a.n : a.ne));
+  if (a.episodes != nullptr) hipLaunchKernelGGL(stack_ring_kernel<true>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(stack_ring_kernel<false>, grid, dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
@@ -377,8 +481,9 @@ hipError_t launch_rgb_phi(const uint8_t* imgs, int64_t n, int H, int W, float* o
 }
 
 hipError_t launch_rgb_ring(const RingArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(rgb_ring_kernel, dim3(RGB_NBANDS, (unsigned)(a.ne < 0 ? a.n : a.ne)), dim3(256), rgb_lds(a.W), s,
-                     a);
+  const dim3 grid(RGB_NBANDS, (unsigned)(a.ne < 0 ? a.n : a.ne));
+  if (a.episodes != nullptr) hipLaunchKernelGGL(rgb_ring_kernel<true>, grid, dim3(256), rgb_lds(a.W), s, a);
+  else hipLaunchKernelGGL(rgb_ring_kernel<false>, grid, dim3(256), rgb_lds(a.W), s, a);
   return hipGetLastError();
 }
 

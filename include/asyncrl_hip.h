@@ -361,6 +361,55 @@ int arl_forward_states(arl_net* net, const float* states, int64_t n, int mode, v
  * [e0, e0 + n): the next forward starts from h = c = None.  No-op for FF. */
 int arl_reset_state(arl_net* net, int64_t e0, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------ episode statistics */
+
+/* Device-side episode statistics: the learning curve of train_loop
+ * (a3c_ale.py:95-96,114-124: episode_r += env.reward, printed and zeroed at every
+ * terminal; total_r) without copying a step's rewards or dones to the host.
+ * Off by default; additions to ABI 4.  While on, the thread that ingests env
+ * e's reward / done in arl_observe* / arl_observe_envs / arl_run_window also
+ * accumulates them; an observation at window slot t >= 1 carries (r, d):
+ *   run_ret[e] += r, run_len[e] += 1, total[e] += r, steps[e] += 1
+ *   d != 0, the episode is complete with return G = run_ret, length L = run_len:
+ *     count[e] += 1, sum[e] += G, sumsq[e] += G * G, len_sum[e] += L,
+ *     min[e] = min(min[e], G), max[e] = max(max[e], G);
+ *     (G, L, k) -> env e's log entry (count before) % ARL_EPISODE_LOG, where
+ *     k = control-block step + t is the global observation index;
+ *     log_count[e] += 1; run_ret[e] = 0, run_len[e] = 0.
+ * r is the raw float32 reward, never clipped, whatever clip_reward says (the
+ * reference sums env.reward; clipping happens only in the returns).  Slot 0
+ * carries no reward.  force_reset abandons the running episode (run_ret =
+ * run_len = 0 after the above) and does not count as an episode.  Observing
+ * the same slot twice counts its reward twice.
+ * All sums are float64 with unfused round-to-nearest adds / multiplies in
+ * env-step order; lengths, counts and steps are int64; one thread owns one
+ * env (no atomics), so a NumPy float64 replay is bit-identical, env-range
+ * launches on several streams and graph replays included.
+ * The arrays are the last arl_net_buffer entries of the workspace, 8-byte
+ * elements, (n_envs,) each: ep_run_ret, ep_total, ep_sum, ep_sumsq, ep_min,
+ * ep_max (f64); ep_run_len, ep_steps, ep_count, ep_len_sum, ep_log_count
+ * (int64); and the logs, (ARL_EPISODE_LOG, n_envs): ep_log_ret (f64),
+ * ep_log_len, ep_log_step (int64).  arl_net_reset zeroes the block (with
+ * count 0: min = +inf, max = -inf), whether the feature is on or not.
+ *
+ * arl_net_set_episode_stats: on / off for the observations launched (or
+ * captured) from now on.  arl_episode_stats_reset: zero the whole block.
+ * arl_episode_stats: reduce over the envs, stream-ordered behind the
+ * observations that fed it, into 8 doubles of device memory (8-byte aligned):
+ *   [episodes, return_sum, return_sumsq, return_min, return_max, length_sum,
+ *    steps, reward_sum]
+ * in a fixed order (one 256-thread workgroup: thread j sums envs j, j + 256,
+ * ... ascending, thread 0 then combines partials 0..255 in order).  clear != 0
+ * also zeroes the cumulative per-env arrays it read (ep_count, ep_sum,
+ * ep_sumsq, ep_min, ep_max, ep_len_sum, ep_steps, ep_total; not the running
+ * episode, not the log): "statistics since the last read".
+ * All three: ARL_ESTATE on an unbound net; arl_episode_stats also ARL_ESTATE
+ * while the feature is off, ARL_EINVAL for a null or misaligned out8_device. */
+#define ARL_EPISODE_LOG 8
+int arl_net_set_episode_stats(arl_net* net, int on);
+int arl_episode_stats_reset(arl_net* net, void* stream);
+int arl_episode_stats(arl_net* net, double* out8_device, int clear, void* stream);
+
 /* ------------------------------------------------------------------ granular ops */
 
 /* RMSpropAsync.update_one (rmsprop_async.py:23-38) on flat f32 arrays, with
