@@ -99,6 +99,8 @@ SIGNATURES = {
     "arl_net_set_episode_stats": (c_int, [c_void_p, c_int]),
     "arl_episode_stats_reset": (c_int, [c_void_p, c_void_p]),
     "arl_episode_stats": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "arl_net_set_window_stats": (c_int, [c_void_p, c_int]),
+    "arl_window_stats_reset": (c_int, [c_void_p, c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
@@ -126,6 +128,11 @@ EPISODE_LOG = 8        # ARL_EPISODE_LOG: episodes per env the device-side episo
 # the 8 doubles of arl_episode_stats, in order
 EPISODE_STAT_FIELDS = ("episodes", "return_sum", "return_sumsq", "return_min", "return_max", "length_sum", "steps",
                        "reward_sum")
+WINDOW_LOG = 64           # ARL_WINDOW_LOG: records the device-side window log keeps
+WINDOW_STAT_FIELDS = 17   # ARL_WINDOW_STAT_FIELDS: doubles per record, named in order:
+WINDOW_STAT_NAMES = ("window", "step", "samples", "terminals", "reward_sum", "pi_loss", "v_loss", "entropy_sum",
+                     "value_sum", "value_sumsq", "return_sum", "return_sumsq", "adv_sum", "adv_sumsq", "grad_sqnorm",
+                     "clip_scale", "lr")
 # window timeline stages (arl_stamps_*): arl_run_stage's 1..11, then the stamp-only ones
 STAGE_NAMES = {1: "conv_fwd", 2: "fc_fwd", 3: "policy", 4: "fc_bwd", 5: "conv_bwd", 6: "returns", 7: "conv_reduce",
                8: "grad_sqnorm", 9: "lstm_gates", 10: "lstm_bptt", 11: "lstm_wgrad", 12: "phi", 13: "rmsprop",

@@ -47,9 +47,9 @@ import torch.distributed as dist
 from ._lib import (ACT_AFTER_CONV, ACT_CONV_ONLY, ARCH_FF, ARCH_FF_NATURE, ARCH_LSTM, ARCH_RGB, ARCH_STACK,
                    ARCH_STATES, LEARN_CONV, RESIZE_SCALAR)
 from .dqn_phi import dqn_phi as _device_dqn_phi
-from .distributed import (allreduce_grads, dist_initialized, gather_episode_stats, merge_episode_stats,
-                          world_info)
-from .net import DeviceNet, episode_stats_dict, init_like_torch
+from .distributed import (allreduce_grads, dist_initialized, gather_episode_stats, gather_window_stats,
+                          merge_episode_stats, merge_window_stats, world_info)
+from .net import DeviceNet, episode_stats_dict, init_like_torch, window_stats_dict
 from . import serializers
 from .policy_output import SoftmaxPolicyOutput
 
@@ -283,6 +283,23 @@ class A3C:
             dev = self.net.device if dist.get_backend(self.pg) == "nccl" else "cpu"
             v = merge_episode_stats(gather_episode_stats(torch.as_tensor(v, dtype=torch.float64, device=dev), self.pg))
         return episode_stats_dict(v)
+
+    def window_stats(self, last: int = 1, reduce: bool = True, stream=None) -> list:
+        """What the reference's learner logs at every update (a3c.py:123-124,
+        136-141,161-163: losses, gradient norm, entropy, value) from the
+        device-side window log (net.set_window_stats() first): the newest
+        `last` records, oldest first, as dicts (window_stats_dict); one copy to
+        the host, no per-window host work.  With collectives and reduce=True
+        every rank's records are gathered and merged per record
+        (merge_window_stats), so all ranks return the statistics of all envs;
+        every rank must call it.  Ranks with collectives=False are independent
+        learners and are never merged."""
+        rows = self.net.window_stats_raw(last, stream)
+        if reduce and self.collectives:
+            dev = self.net.device if dist.get_backend(self.pg) == "nccl" else "cpu"
+            per_rank = gather_window_stats(torch.as_tensor(rows, dtype=torch.float64, device=dev), self.pg)
+            rows = [merge_window_stats(rs) for rs in zip(*per_rank)]
+        return [window_stats_dict(r) for r in rows]
 
     # ------------------------------------------------------------ window pieces
     def _overlap_allreduce(self) -> bool:

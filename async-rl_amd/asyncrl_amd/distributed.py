@@ -64,13 +64,53 @@ def merge_episode_stats(vectors):
     return out
 
 
-def gather_episode_stats(v: torch.Tensor, group=None):
-    """All-gather one rank's 8 doubles (a device tensor for RCCL, a host one
-    for gloo); returns the ranks' vectors in rank order as lists."""
+def _gather_doubles(v: torch.Tensor, group=None):
+    """All-gather one rank's float64 tensor of any shape, the same on every
+    rank (a device tensor for RCCL, a host one for gloo); returns the ranks'
+    tensors in rank order as nested lists."""
     world, _ = world_info(group)
     out = [torch.zeros_like(v) for _ in range(world)]
     dist.all_gather(out, v, group=group)
     return [o.cpu().tolist() for o in out]
+
+
+def gather_episode_stats(v: torch.Tensor, group=None):
+    """All-gather one rank's 8 doubles (a device tensor for RCCL, a host one
+    for gloo); returns the ranks' vectors in rank order as lists."""
+    return _gather_doubles(v, group)
+
+
+# fields of a window record (WINDOW_STAT_NAMES) every rank must agree on: window, step, and what the
+# update computes from the all-reduced gradient (grad_sqnorm, clip_scale, lr); the rest are sums
+_WINDOW_EQUAL = (0, 1, 14, 15, 16)
+_WINDOW_FIELDS = 17
+
+
+def merge_window_stats(rows):
+    """Merge one window record (17 doubles, WINDOW_STAT_NAMES order) of
+    several ranks that share their gradients: window, step, grad_sqnorm,
+    clip_scale and lr must be equal on all ranks (ValueError otherwise);
+    samples .. adv_sumsq are summed in rank order.  Pure host arithmetic;
+    returns a list of 17 floats."""
+    rs = [[float(x) for x in r] for r in rows]
+    if not rs or any(len(r) != _WINDOW_FIELDS for r in rs):
+        raise ValueError(f"merge_window_stats: need at least one record of {_WINDOW_FIELDS} values")
+    out = list(rs[0])
+    for k, r in enumerate(rs[1:], 1):
+        for i in range(_WINDOW_FIELDS):
+            if i in _WINDOW_EQUAL:
+                if r[i] != out[i]:
+                    raise ValueError(f"merge_window_stats: field {i} differs between rank 0 ({out[i]}) and rank {k} "
+                                     f"({r[i]}): the ranks do not describe the same update")
+            else:
+                out[i] += r[i]
+    return out
+
+
+def gather_window_stats(rows: torch.Tensor, group=None):
+    """All-gather one rank's (k, 17) records (k the same on every rank);
+    returns the ranks' record lists in rank order."""
+    return _gather_doubles(rows, group)
 
 
 def replica_checksum(t: torch.Tensor) -> int:

@@ -18,7 +18,8 @@ import torch
 
 from ._lib import (ARCH_FF, ARCH_FF_NATURE, ARCH_LSTM, ARCH_RGB, ARCH_STACK, ARCH_STATES, ENV_GROUP_ALIGN,
                    EPISODE_LOG, EPISODE_STAT_FIELDS, FWD_KEEP_STATE, POOL_DONES, POOL_FRAMES, POOL_REWARDS,
-                   RESIZE_SCALAR, STAGE_HOST, STAGE_NAMES, check, lib, ptr, stream_handle)
+                   RESIZE_SCALAR, STAGE_HOST, STAGE_NAMES, WINDOW_LOG, WINDOW_STAT_FIELDS, WINDOW_STAT_NAMES, check,
+                   lib, ptr, stream_handle)
 
 
 def param_shapes(arch: int, n_actions: int):
@@ -96,6 +97,35 @@ def episode_stats_dict(v) -> dict:
     d["mean"] = d["return_sum"] / n if n else nan
     d["mean_length"] = d["length_sum"] / n if n else nan
     d["stdev"] = math.sqrt(max(d["return_sumsq"] - d["return_sum"] ** 2 / n, 0.0) / (n - 1)) if n > 1 else nan
+    return d
+
+
+def window_stats_dict(row) -> dict:
+    """One record of the window log (WINDOW_STAT_NAMES order) as a dict, the
+    counters as int, plus what the host derives: entropy, value_mean,
+    return_mean, adv_mean (sum / samples; nan without a sample),
+    explained_variance = 1 - Var(adv) / Var(R) from the sums (nan when Var(R)
+    is 0), grad_norm, clipped (the update scaled the gradient) and total_loss."""
+    if len(row) != WINDOW_STAT_FIELDS:
+        raise ValueError(f"window_stats_dict: need {WINDOW_STAT_FIELDS} values")
+    d = {k: float(x) for k, x in zip(WINDOW_STAT_NAMES, row)}
+    for k in ("window", "step", "samples", "terminals"):
+        d[k] = int(d[k])
+    n = d["samples"]
+    nan = float("nan")
+    for out, src in (("entropy", "entropy_sum"), ("value_mean", "value_sum"), ("return_mean", "return_sum"),
+                     ("adv_mean", "adv_sum")):
+        d[out] = d[src] / n if n else nan
+    ev = nan
+    if n:
+        var_r = d["return_sumsq"] / n - d["return_mean"] ** 2
+        var_a = d["adv_sumsq"] / n - d["adv_mean"] ** 2
+        if var_r > 0:
+            ev = 1.0 - var_a / var_r
+    d["explained_variance"] = ev
+    d["grad_norm"] = math.sqrt(d["grad_sqnorm"])
+    d["clipped"] = d["clip_scale"] < 1
+    d["total_loss"] = d["pi_loss"] + d["v_loss"]
     return d
 
 
@@ -341,6 +371,45 @@ class DeviceNet:
                 "ret": self.buffer("ep_log_ret", torch.float64, (L, n)),
                 "len": self.buffer("ep_log_len", torch.int64, (L, n)),
                 "step": self.buffer("ep_log_step", torch.int64, (L, n))}
+
+    # ------------------------------------------------------------ window statistics
+    window_stats_on = False
+
+    def set_window_stats(self, on: bool = True):
+        """Append one record of training statistics per update to the device-side
+        window log (arl_net_set_window_stats; a3c.py:123-124,136-141,161-163:
+        losses, gradient norm, entropy, value).  Off by default; a captured
+        window keeps the setting it was captured with."""
+        check(lib.arl_net_set_window_stats(self._h, int(on)), "arl_net_set_window_stats")
+        self.window_stats_on = bool(on)
+
+    def window_stats_reset(self, stream=None):
+        """Zero the window log and its record count (arl_window_stats_reset)."""
+        check(lib.arl_window_stats_reset(self._h, stream_handle(stream)), "arl_window_stats_reset")
+
+    def window_stats_raw(self, last: int = 1, stream=None) -> np.ndarray:
+        """The newest min(last, records written, WINDOW_LOG) records, oldest
+        first, as (k, WINDOW_STAT_FIELDS) float64: one copy of the log and its
+        count to the host, which waits for it."""
+        if not self.window_stats_on:
+            raise ValueError("window_stats: the feature is off (set_window_stats)")
+        if last < 0:
+            raise ValueError("window_stats: last must be >= 0")
+        lo, nb = ctypes.c_int64(), ctypes.c_int64()
+        check(lib.arl_net_buffer(self._h, b"win_log", ctypes.byref(lo), ctypes.byref(nb)), "arl_net_buffer")
+        co = ctypes.c_int64()
+        check(lib.arl_net_buffer(self._h, b"win_count", ctypes.byref(co), None), "arl_net_buffer")
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):   # win_count follows win_log in the workspace: one copy for both
+            raw = self.workspace[lo.value:co.value + 8].cpu().numpy()
+        log = raw[:nb.value].view(np.float64).reshape(WINDOW_LOG, WINDOW_STAT_FIELDS)
+        count = int(raw[co.value - lo.value:].view(np.int64)[0])
+        k = min(last, count, WINDOW_LOG)
+        return log[[i % WINDOW_LOG for i in range(count - k, count)]].copy()
+
+    def window_stats(self, last: int = 1, stream=None) -> list:
+        """window_stats_raw as a list of dicts (window_stats_dict), oldest first."""
+        return [window_stats_dict(r) for r in self.window_stats_raw(last, stream)]
 
     def reset_state(self, e0: int = 0, n: int | None = None, stream=None):
         """LSTM: the pi_and_v recurrent state of rows [e0, e0 + n) -> None (arl_reset_state)."""

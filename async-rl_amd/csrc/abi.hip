@@ -175,6 +175,11 @@ int arl_net_prepare(arl_net* h, void* s) {
   return hip_status(arl::ensure_fc_planes(h->net, S(s)), "net_prepare");
 }
 
+// win_log and win_count (adjacent 256-byte aligned buffers: one memset through the padding between them)
+static hipError_t window_stats_zero(arl::Net& n, hipStream_t s) {
+  return hipMemsetAsync(n.ws + n.w_win_log, 0, (size_t)(n.w_win_count + 8 - n.w_win_log), s);
+}
+
 int arl_net_reset(arl_net* h, void* s) {
   NEED_BOUND(h);
   arl::Net& n = h->net;
@@ -193,6 +198,7 @@ int arl_net_reset(arl_net* h, void* s) {
     if (e == hipSuccess) e = hipMemsetAsync(n.ws + n.w_zero, 0, arl::ZERO_ROW_FLOATS * 4, S(s));
   }
   if (e == hipSuccess) e = arl::launch_episode_reset(n.ws + n.w_episodes, n.N, S(s));
+  if (e == hipSuccess) e = window_stats_zero(n, S(s));
   return hip_status(e, "net_reset");
 }
 
@@ -217,6 +223,20 @@ int arl_episode_stats(arl_net* h, double* out8_device, int clear, void* s) {
   if (!out8_device || !aligned(out8_device, 8)) return fail(ARL_EINVAL, "episode_stats: out8 null / not 8-byte aligned");
   return hip_status(arl::launch_episode_reduce(n.ws + n.w_episodes, n.N, out8_device, clear ? 1 : 0, S(s)),
                     "episode_stats");
+}
+
+static_assert(arl::WINDOW_LOG == ARL_WINDOW_LOG && arl::WINDOW_STAT_FIELDS == ARL_WINDOW_STAT_FIELDS,
+              "window statistics record");
+
+int arl_net_set_window_stats(arl_net* h, int on) {
+  NEED_BOUND(h);
+  h->net.window_stats = on != 0;
+  return ARL_OK;
+}
+
+int arl_window_stats_reset(arl_net* h, void* s) {
+  NEED_BOUND(h);
+  return hip_status(window_stats_zero(h->net, S(s)), "window_stats_reset");
 }
 
 int arl_net_set_pool(arl_net* h, int kind, const void* pool, int64_t bytes) {

@@ -196,6 +196,11 @@ struct Net {
   ReturnsCfg ret{};
   int norm_rest_blocks = 64;
   bool episode_stats = false;   // arl_net_set_episode_stats: the observations accumulate into w_episodes
+  // arl_net_set_window_stats: every net_optimize appends a record to w_win_log (window_stats_kernel, optim.hip);
+  // win_gamma / win_clip_reward = those of the net's last returns launch, which the record's returns repeat
+  bool window_stats = false;
+  double win_gamma = 0.99;
+  int win_clip_reward = 1;
   int hid;                 // width of the layer the heads read (256 NIPS / LSTM, 512 Nature)
   int env_offset;          // global id of env 0 on this rank (RNG stream)
   uint64_t seed;
@@ -213,6 +218,7 @@ struct Net {
       w_dG, w_dhn, w_dcn, w_da2, w_slab, w_norm, w_loss, w_tick, w_fcb_part = 0, w_fcb_tick = 0, w_zero = 0,
       w_a2m = 0,   // (T+1, N, 81) a2 > 0 bits (ring-frame NIPS nets; 0: none)
       w_fcplanes = 0;   // FC_PLANES_BYTES: the FC weight's bf16 split planes (NIPS nets)
+  int64_t w_win_log = 0, w_win_count = 0;   // (WINDOW_LOG, WINDOW_STAT_FIELDS) f64 ring of records; int64 records written
   int64_t w_episodes = 0;   // episode_block_bytes(N): the episode statistics (EpisodeView), last in the workspace
   int64_t w_a3 = 0, w_da1 = 0, w_da3 = 0;   // Nature head only (w_da1 also ARCH_STATES)
   // LSTM recurrent state of pi_and_v on explicit states (A3CLSTM.pi_and_v, a3c_ale.py:55-63):
@@ -440,11 +446,44 @@ hipError_t launch_rmsprop(float* p, float* ms, const float* g, int64_t n, double
                           int64_t total_steps, int64_t n_total, int t_max, hipStream_t s,
                           const AdvanceArgs* adv = nullptr, const DecayArgs* wd = nullptr);
 hipError_t launch_grad_sqnorm(const float* g, int64_t n, double* partials, int blocks, hipStream_t s);
+// Per-window training statistics (arl_net_set_window_stats; the header's "window statistics"): one record
+// of WINDOW_STAT_FIELDS doubles per update, slot count % WINDOW_LOG of the ring `log`.
+constexpr int WINDOW_LOG = 64, WINDOW_STAT_FIELDS = 17;
+struct WindowStatsArgs {
+  const float* rewards;     // (T, n)
+  const uint8_t* dones;     // (T, n)
+  const float* v;           // (T + 1, n), row T = the bootstrap value
+  const float* entropy;     // (T + 1, n)
+  const float* loss;        // (n, 2)
+  int T, n;
+  double gamma;
+  int clip_reward;
+  const int64_t* ctl;       // the control block, not yet advanced
+  double* log;
+  int64_t* count;
+};
+// One 256-thread workgroup (optim.hip window_stats_kernel).  The remaining arguments are launch_rmsprop's for
+// the update that follows, so that the recorded lr and clip scale come from the values (and the device
+// functions) the update kernel uses; norm_sq is always given, clip <= 0: the update does not clip.
+hipError_t launch_window_stats(const WindowStatsArgs& w, double lr, const double* norm_sq, int nparts, float clip,
+                               const int64_t* lr_ctl, int64_t total_steps, int64_t n_total, int t_max, bool advance,
+                               hipStream_t s);
 hipError_t launch_stream_copy(const void* src, void* dst, int64_t bytes, int blocks, int mode, hipStream_t s);
 hipError_t launch_policy(const float* h, int64_t n, const float* Wpi, const float* bpi, const float* Wv,
                          const float* bv, int A, uint64_t seed, const int64_t* ctl, int64_t step_off,
                          int env_offset, int mode, float* logits, float* probs, float* logp, float* v,
                          float* ent, int32_t* act, float* logp_a, hipStream_t s, int hid = HID);
+// The learner's n-step return recurrence (a3c.py:82-92), one step backwards in time: R = 0 at a terminal
+// (dones bit 0), then R = R * gamma + r with the reward clipped to [-1, 1] iff clip_reward (a3c.py:69-70);
+// f64, unfused.  returns_compute (policy.hip) and window_stats_kernel (optim.hip) both scan with it.
+__device__ inline double clip_reward_f64(float r, int clip_reward) {
+  const double x = (double)r;
+  return clip_reward ? (x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x)) : x;
+}
+__device__ inline double return_step(double R, int done, float r, double gamma, int clip_reward) {
+  if (done & 1) R = 0.0;
+  return __dadd_rn(__dmul_rn(R, gamma), clip_reward_f64(r, clip_reward));
+}
 // dones: bit 0 = the transition t -> t+1 ended the episode; bit 1 = step t lies
 // past the end of this window (arl_truncate_window: no loss, no gradient).
 // pcoef = pi_loss_coef; keep_scale: keep_loss_scale_same (a3c.py:110-121)

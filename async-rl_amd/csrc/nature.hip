@@ -257,6 +257,8 @@ hipError_t nature_learn(Net& net, double gamma, float beta, float vcoef, int cli
   float* dl = net.at<float>(net.w_dlogits);
   float* dv = net.at<float>(net.w_dv);
   // n-step returns + loss gradient (a3c.py:82-126)
+  net.win_gamma = gamma;
+  net.win_clip_reward = clip_reward;
   ARL_TRY(launch_returns(net.at<float>(net.w_rewards), net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v),
                          net.at<float>(net.w_probs), net.at<float>(net.w_logp), net.at<int32_t>(net.w_act), T, n, A,
                          gamma, beta, vcoef, clip_reward, dl, dv, net.at<float>(net.w_loss), s,

@@ -283,6 +283,9 @@ bool net_init(Net& net, int arch, int n_actions, int n_envs, int t_max, int env_
   net.w_eval_reset = buf("eval_reset", L ? n : 0);
   net.w_zero = buf("zero_row", L ? ZERO_ROW_FLOATS * 4 : 0);
   net.w_fcplanes = buf("fc_planes", NAT ? 0 : FC_PLANES_BYTES);
+  // window statistics (optim.hip window_stats_kernel): the ring of records and the count of records written
+  net.w_win_log = buf("win_log", (int64_t)WINDOW_LOG * WINDOW_STAT_FIELDS * 8);
+  net.w_win_count = buf("win_count", 8);
   // episode statistics: the 14 arrays of EpisodeView, in its order (episode_view computes the same offsets)
   net.w_episodes = wo;
   for (const char* nm : {"ep_run_ret", "ep_run_len", "ep_total", "ep_steps", "ep_count", "ep_sum", "ep_sumsq", "ep_min",
@@ -395,6 +398,8 @@ hipError_t net_act(Net& net, int t, int mode, hipStream_t s, int e0, int ne) {
                                        net.keep_scale, net.at<float>(net.w_hfc), net.at<float>(net.w_dfc), s));
       net.returns_done = true;
       net.norm_ready = false;   // a new gradient (as LEARN_RETURNS)
+      net.win_gamma = r.gamma;
+      net.win_clip_reward = r.clip_reward;
       return stamp(net, STAGE_POLICY, s);
     }
     ARL_TRY(launch_policy_fc(fc_slab, ne, P + net.o_fcb, hfc, pa, s));
@@ -558,6 +563,8 @@ hipError_t net_learn_part(Net& net, int part, double gamma, float beta, float vc
     // n-step returns + loss gradient wrt logits / v (a3c.py:82-126); also snapshots the step counter for
     // the optimizer's fused advance and, in the same launch, the heads' backward dh (FF: dfc = dh * (hfc > 0))
     net.norm_ready = false;   // a new gradient: no folded norm until net_learn's reduce
+    net.win_gamma = gamma;
+    net.win_clip_reward = clip_reward;
     ARL_TRY(launch_returns_heads(net.at<float>(net.w_rewards), net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v),
                                  net.at<float>(net.w_probs), net.at<float>(net.w_logp), net.at<int32_t>(net.w_act), T,
                                  n, A, gamma, beta, vcoef, clip_reward, net.at<float>(net.w_dlogits),
@@ -698,9 +705,19 @@ hipError_t net_optimize(Net& net, double lr0, int64_t total_steps, int64_t n_tot
   const bool fused = advance;
   const bool folded = do_clip && net.norm_ready;   // partials left by arl_learn's conv reduce
   net.norm_ready = false;
-  if (do_clip && !folded) {
+  // the window statistics record the squared norm even when the update does not clip
+  if ((do_clip || net.window_stats) && !folded) {
     ARL_TRY(launch_grad_sqnorm(net.g, net.param_floats, parts, net.norm_blocks, s));
     ARL_TRY(stamp(net, STAGE_GRAD_SQNORM, s));
+  }
+  const int nparts = folded ? conv_norm_parts(net.norm_rest_blocks) : net.norm_blocks;
+  const int64_t* lr_ctl = total_steps > 0 ? net.at<int64_t>(net.w_ctl) : nullptr;
+  if (net.window_stats) {   // one record of the window this update consumes, before anything advances
+    const WindowStatsArgs w{net.at<float>(net.w_rewards), net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v),
+                            net.at<float>(net.w_ent), net.at<float>(net.w_loss), net.T, net.N, net.win_gamma,
+                            net.win_clip_reward, net.at<int64_t>(net.w_ctl), net.at<double>(net.w_win_log),
+                            net.at<int64_t>(net.w_win_count)};
+    ARL_TRY(launch_window_stats(w, lr0, parts, nparts, clip, lr_ctl, total_steps, n_total, net.T, fused, s));
   }
   const bool L = net.arch == ARCH_LSTM;
   // the update rewrites the FC weight's split planes with the new W (all of them, so they are current
@@ -710,9 +727,8 @@ hipError_t net_optimize(Net& net, double lr0, int64_t total_steps, int64_t n_tot
                         L ? net.at<float>(net.w_hbuf) : nullptr, L ? net.at<float>(net.w_cbuf) : nullptr, net.T,
                         net.N};
   if (planes != nullptr) net.planes_gen = net.param_gen;
-  ARL_TRY(launch_rmsprop(net.p, net.ms, net.g, net.param_floats, lr0, alpha, eps, do_clip ? parts : nullptr,
-                         folded ? conv_norm_parts(net.norm_rest_blocks) : net.norm_blocks, clip, total_steps > 0 ? net.at<int64_t>(net.w_ctl) : nullptr, total_steps,
-                         n_total, net.T, s, &adv, &net.decay));
+  ARL_TRY(launch_rmsprop(net.p, net.ms, net.g, net.param_floats, lr0, alpha, eps, do_clip ? parts : nullptr, nparts,
+                         clip, lr_ctl, total_steps, n_total, net.T, s, &adv, &net.decay));
   ARL_TRY(stamp(net, STAGE_RMSPROP, s));
   return advance && !fused ? net_advance(net, s) : hipSuccess;
 }

@@ -19,6 +19,8 @@
 //     f32 op in the reference's order (NumPy f32 semantics, no FMA), so the
 //     result is bit-identical to update_one_cpu.
 // 20 bytes move per parameter (read p, g, ms; write p, ms) + 4 for the norm.
+// With arl_net_set_window_stats on, window_stats_kernel (below) runs between the two and records what
+// the update is about to apply, through the same device functions (update_lr, partials_sum, clip_scale).
 //
 // NonbiasWeightDecay(rate) (a3c_ale.py:227-228, nonbias_weight_decay.py:4-28), the hook the reference adds
 // after the clip: g += rate * p for every parameter whose name is not a bias, i.e. t = f32(f32(rate) * p),
@@ -30,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "arl_internal.hpp"
@@ -78,6 +81,41 @@ struct RmsConst {   // (AdvanceArgs is declared in arl_internal.hpp)
   int ctl_idx;              // CTL_STEP, or CTL_STEP_SNAP when this launch also advances
 };
 
+// The three pieces below are shared by rmsprop_kernel and window_stats_kernel, so that the recorded
+// learning rate, squared norm and clip scale are bit for bit the ones the update applies.
+
+// the update's learning rate: c.lr, or the anneal when the control block and a step budget are given
+__device__ inline float update_lr(const RmsConst& c) {
+  if (c.ctl == nullptr || c.total <= 0) return c.lr;
+  const int64_t gt = (c.ctl[c.ctl_idx] + c.t_max) * c.n_total;
+  // clamped at 0: the reference stops training once global_t passes the
+  // step budget (run_a3c.py:64-68); a replay past it must not ascend
+  return (float)(((double)max(c.total - gt - 1, (int64_t)0) / (double)c.total) * c.lr0);
+}
+
+// the squared norm: re-reduce the partials [0, nparts) in block order (4 loads a thread in flight);
+// sh: 8 doubles of LDS; every thread of the 256 gets the sum
+__device__ inline double partials_sum(const double* __restrict__ norm_sq, int nparts, double* sh) {
+  double t = 0.0, v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = norm_sq[min((int)threadIdx.x + 256 * k, nparts - 1)];
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if ((int)threadIdx.x + 256 * k < nparts) t += v[k];
+  return block_sum_f64(t, sh);
+}
+
+// GradientClipping: does the update scale the gradient, and by which f32 factor (else scale is left alone)
+__device__ inline bool clip_scale(double sqnorm, float clip, float& scale) {
+  const double norm = sqrt(sqnorm);
+  const double rate = (double)clip / norm;
+  if (norm > 0.0 && rate < 1.0) {
+    scale = (float)rate;
+    return true;
+  }
+  return false;
+}
+
 
 
 __device__ inline void rms1(float& p, float& ms, float g, const RmsConst& c) {
@@ -108,12 +146,7 @@ rmsprop_kernel(float* __restrict__ p, float* __restrict__ ms, const float* __res
                const double* __restrict__ norm_sq, int nparts, float clip, AdvanceArgs adv, Decay wd) {
   constexpr bool WD = std::is_same<Decay, DecayArgs>::value;
   __shared__ double sh[8];
-  if (c.ctl != nullptr && c.total > 0) {
-    const int64_t gt = (c.ctl[c.ctl_idx] + c.t_max) * c.n_total;
-    // clamped at 0: the reference stops training once global_t passes the
-    // step budget (run_a3c.py:64-68); a replay past it must not ascend
-    c.lr = (float)(((double)max(c.total - gt - 1, (int64_t)0) / (double)c.total) * c.lr0);
-  }
+  c.lr = update_lr(c);
   const int64_t n4 = n >> 2;
   float4* p4 = reinterpret_cast<float4*>(p);
   float4* m4 = reinterpret_cast<float4*>(ms);
@@ -136,21 +169,7 @@ rmsprop_kernel(float* __restrict__ p, float* __restrict__ ms, const float* __res
   }
   float scale = 1.f;
   bool do_clip = false;
-  if (norm_sq != nullptr) {   // re-reduce the partials [0, nparts) in block order (4 loads a thread in flight)
-    double t = 0.0, v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = norm_sq[min((int)threadIdx.x + 256 * k, nparts - 1)];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if ((int)threadIdx.x + 256 * k < nparts) t += v[k];
-    t = block_sum_f64(t, sh);
-    const double norm = sqrt(t);
-    const double rate = (double)clip / norm;
-    if (norm > 0.0 && rate < 1.0) {
-      do_clip = true;
-      scale = (float)rate;
-    }
-  }
+  if (norm_sq != nullptr) do_clip = clip_scale(partials_sum(norm_sq, nparts, sh), clip, scale);
   for (int64_t ib = i0; ib < n4; ib += gsz) {
     if (ib != i0) {
       pv = p4[ib];
@@ -200,6 +219,135 @@ rmsprop_kernel(float* __restrict__ p, float* __restrict__ ms, const float* __res
   }
 }
 
+// Per-window training statistics (arl_net_set_window_stats; semantics in include/asyncrl_hip.h, "window
+// statistics"): one record per update, launched by net_optimize between the norm's partials and the update
+// kernel.  One workgroup of 256: thread j owns envs j, j + 256, ...; per env one reverse scan of the
+// learner's return recurrence (return_step) gives (float)R_t, then t ascends over the steps; the twelve
+// f64 partial sums (fields 2..13) go through LDS, and lane f of the first wave adds partials 1..255 of
+// field 2 + f to partial 0 in order (twelve lanes, one instruction stream: one thread walking all twelve
+// chains issued twelve times the f64 adds and measured 10 us longer).  The lr, the squared norm and the
+// clip scale come from rmsprop_kernel's own device functions on the arguments the update gets.
+// Windows up to WS_RW steps keep an env's rewards / dones / v / entropy and its R_t in registers (static
+// indices, clamped offsets, as returns_load); longer ones loop over memory with the R_t in LDS.
+// Dynamic LDS, reused in turn: block_sum_f64's scratch, the R_t columns (T x 256 f32, T > WS_RW), the
+// partials (256 x WS_SUMS f64).
+constexpr int WS_SUMS = 12, WS_RW = 8;
+static_assert(2 + WS_SUMS + 3 == WINDOW_STAT_FIELDS, "window record layout");
+
+// one env's window in registers (T <= WS_RW): static indices, clamped offsets, as returns_load (policy.hip)
+struct WsEnv {
+  float rw[WS_RW], vv[WS_RW], en[WS_RW], vboot, l0, l1;
+  int dn[WS_RW];
+};
+__device__ inline void ws_load(const WindowStatsArgs& w, int e, WsEnv& x) {
+#pragma unroll
+  for (int k = 0; k < WS_RW; ++k) {
+    const int64_t o = (int64_t)min(k, w.T - 1) * w.n + e;
+    x.rw[k] = w.rewards[o];
+    x.dn[k] = w.dones[o];
+    x.vv[k] = w.v[o];
+    x.en[k] = w.entropy[o];
+  }
+  x.vboot = w.v[(int64_t)w.T * w.n + e];
+  x.l0 = w.loss[2 * e];
+  x.l1 = w.loss[2 * e + 1];
+}
+
+// the per-env terms: pi_loss, v_loss
+__device__ inline void ws_env(double* acc, float pi_loss, float v_loss) {
+  acc[3] = __dadd_rn(acc[3], (double)pi_loss);
+  acc[4] = __dadd_rn(acc[4], (double)v_loss);
+}
+
+// One sample (t, e) into the sums, without a branch.  A sample past a truncated window's end (dones bit
+// 1) adds +0.0 to every sum, which leaves its bits alone: the sums start at +0.0, and a round-to-nearest
+// sum that started there is never -0.0, the only value x + 0.0 would change.
+__device__ inline void ws_sample(double* acc, int d, float r, float vi, float ent, float rf, int clip_reward) {
+  const bool live = (d & 2) == 0;
+  const double vd = (double)vi, rd = (double)rf, ad = (double)__fsub_rn(rf, vi);
+  const double x[WS_SUMS] = {1.0, (d & 1) ? 1.0 : 0.0, clip_reward_f64(r, clip_reward), 0.0, 0.0, (double)ent,
+                             vd, __dmul_rn(vd, vd), rd, __dmul_rn(rd, rd), ad, __dmul_rn(ad, ad)};
+#pragma unroll
+  for (int f = 0; f < WS_SUMS; ++f)
+    if (f != 3 && f != 4) acc[f] = __dadd_rn(acc[f], live ? x[f] : 0.0);
+}
+
+__global__ void __launch_bounds__(256)
+window_stats_kernel(WindowStatsArgs w, RmsConst c, const double* __restrict__ norm_sq, int nparts, float clip) {
+  extern __shared__ double dyn[];
+  const int j = threadIdx.x, T = w.T, n = w.n;
+  // what only the record's writer needs, loaded first so that it is there by the end
+  const int64_t cnt = *w.count, window = w.ctl[CTL_WINDOW], step = w.ctl[c.ctl_idx];
+  const double sqnorm = partials_sum(norm_sq, nparts, dyn);
+  float scale = 1.f;
+  if (clip > 0.f) clip_scale(sqnorm, clip, scale);   // (clip <= 0: the update gets no partials and does not clip)
+  const float lr = update_lr(c);
+  __syncthreads();   // block_sum_f64's scratch is read: the R_t columns may overwrite it
+  double acc[WS_SUMS];
+#pragma unroll
+  for (int f = 0; f < WS_SUMS; ++f) acc[f] = 0.0;
+  if (T <= WS_RW) {   // an env's window in registers, the next env's loads in flight while this one is summed
+    WsEnv cur, nxt;
+    if (j < n) ws_load(w, j, cur);
+    for (int e = j; e < n; e += 256) {
+      ws_load(w, e + 256 < n ? e + 256 : e, nxt);   // (past the last env: this one again, unused)
+      float rf[WS_RW];
+      double R = (double)cur.vboot;
+#pragma unroll
+      for (int k = WS_RW - 1; k >= 0; --k)
+        if (k < T) {
+          R = return_step(R, cur.dn[k], cur.rw[k], w.gamma, w.clip_reward);
+          rf[k] = (float)R;
+        }
+      ws_env(acc, cur.l0, cur.l1);
+#pragma unroll
+      for (int k = 0; k < WS_RW; ++k)
+        if (k < T) ws_sample(acc, cur.dn[k], cur.rw[k], cur.vv[k], cur.en[k], rf[k], w.clip_reward);
+      cur = nxt;
+    }
+  } else {            // longer windows: loops over memory, the R_t of the reverse scan in the thread's LDS column
+    float* Rf = reinterpret_cast<float*>(dyn);
+    for (int e = j; e < n; e += 256) {
+      double R = (double)w.v[(int64_t)T * n + e];
+      for (int t = T - 1; t >= 0; --t) {
+        const int64_t i = (int64_t)t * n + e;
+        R = return_step(R, w.dones[i], w.rewards[i], w.gamma, w.clip_reward);
+        Rf[t * 256 + j] = (float)R;
+      }
+      ws_env(acc, w.loss[2 * e], w.loss[2 * e + 1]);
+      for (int t = 0; t < T; ++t) {
+        const int64_t i = (int64_t)t * n + e;
+        ws_sample(acc, w.dones[i], w.rewards[i], w.v[i], w.entropy[i], Rf[t * 256 + j], w.clip_reward);
+      }
+    }
+  }
+  __syncthreads();   // every R_t column is read: the partials may overwrite them
+#pragma unroll
+  for (int f = 0; f < WS_SUMS; ++f) dyn[j * WS_SUMS + f] = acc[f];
+  __syncthreads();
+  if (j >= WS_SUMS) return;
+  // lane f of the first wave combines field 2 + f: partial 0, then 1 .. 255 in order
+  // (the LDS reads of 32 partials at a time are in flight ahead of the chain of adds that waits for them)
+  double sum = dyn[j];
+  for (int q0 = 1; q0 < 256; q0 += 32) {
+    double x[32];
+#pragma unroll
+    for (int u = 0; u < 32; ++u) x[u] = dyn[min(q0 + u, 255) * WS_SUMS + j];
+#pragma unroll
+    for (int u = 0; u < 32; ++u)
+      if (q0 + u < 256) sum = __dadd_rn(sum, x[u]);
+  }
+  double* rec = w.log + (int64_t)((uint64_t)cnt % WINDOW_LOG) * WINDOW_STAT_FIELDS;
+  rec[2 + j] = sum;
+  if (j != 0) return;
+  rec[0] = (double)window;
+  rec[1] = (double)step;
+  rec[14] = sqnorm;
+  rec[15] = (double)scale;
+  rec[16] = (double)lr;
+  *w.count = cnt + 1;
+}
+
 static int stream_blocks(int64_t n) {
   int64_t b = (n / 4 + 255) / 256;
   if (b > 2048) b = 2048;
@@ -213,14 +361,9 @@ hipError_t launch_grad_sqnorm(const float* g, int64_t n, double* partials, int b
   return hipGetLastError();
 }
 
-hipError_t launch_rmsprop(float* p, float* ms, const float* g, int64_t n, double lr, double alpha, double eps,
-                          const double* norm_sq, int nparts, float clip, const int64_t* ctl,
-                          int64_t total_steps, int64_t n_total, int t_max, hipStream_t s, const AdvanceArgs* adv,
-                          const DecayArgs* wd) {
-  if (wd != nullptr && (wd->n_bias < 0 || wd->n_bias > DECAY_MAX_BIAS)) return hipErrorInvalidValue;
-  if (norm_sq != nullptr && (nparts < 1 || nparts > NORM_MAX_PARTS)) return hipErrorInvalidValue;
-  if (n <= 0) return hipSuccess;
-  // each Python-float hyperparameter meets the f32 arrays as f32(value)
+// each Python-float hyperparameter meets the f32 arrays as f32(value); advance: the launch also ends the window
+static RmsConst rms_const(double lr, double alpha, double eps, const int64_t* ctl, int64_t total_steps, int64_t n_total,
+                          int t_max, bool advance) {
   RmsConst c;
   c.lr = (float)lr;
   c.alpha = (float)alpha;
@@ -231,7 +374,30 @@ hipError_t launch_rmsprop(float* p, float* ms, const float* g, int64_t n, double
   c.n_total = n_total;
   c.t_max = t_max;
   c.ctl = ctl;
-  c.ctl_idx = (adv != nullptr && adv->ctl != nullptr) ? CTL_STEP_SNAP : CTL_STEP;
+  c.ctl_idx = advance ? CTL_STEP_SNAP : CTL_STEP;
+  return c;
+}
+
+hipError_t launch_window_stats(const WindowStatsArgs& w, double lr, const double* norm_sq, int nparts, float clip,
+                               const int64_t* lr_ctl, int64_t total_steps, int64_t n_total, int t_max, bool advance,
+                               hipStream_t s) {
+  if (w.T < 1 || w.T > 64 || w.n < 1) return hipErrorInvalidValue;   // (the R_t columns: at most 64 KB of LDS)
+  if (norm_sq == nullptr || nparts < 1 || nparts > NORM_MAX_PARTS) return hipErrorInvalidValue;
+  // alpha / eps do not enter the record
+  const RmsConst c = rms_const(lr, 0.0, 0.0, lr_ctl, total_steps, n_total, t_max, advance);
+  const size_t lds = std::max(w.T > WS_RW ? (size_t)w.T * 256 * sizeof(float) : 0, (size_t)WS_SUMS * 256 * sizeof(double));
+  hipLaunchKernelGGL(window_stats_kernel, dim3(1), dim3(256), lds, s, w, c, norm_sq, nparts, clip);
+  return hipGetLastError();
+}
+
+hipError_t launch_rmsprop(float* p, float* ms, const float* g, int64_t n, double lr, double alpha, double eps,
+                          const double* norm_sq, int nparts, float clip, const int64_t* ctl,
+                          int64_t total_steps, int64_t n_total, int t_max, hipStream_t s, const AdvanceArgs* adv,
+                          const DecayArgs* wd) {
+  if (wd != nullptr && (wd->n_bias < 0 || wd->n_bias > DECAY_MAX_BIAS)) return hipErrorInvalidValue;
+  if (norm_sq != nullptr && (nparts < 1 || nparts > NORM_MAX_PARTS)) return hipErrorInvalidValue;
+  if (n <= 0) return hipSuccess;
+  const RmsConst c = rms_const(lr, alpha, eps, ctl, total_steps, n_total, t_max, adv != nullptr && adv->ctl != nullptr);
   AdvanceArgs a{};
   if (adv != nullptr) a = *adv;
   if (wd != nullptr && wd->rate != 0.f)

@@ -210,7 +210,6 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
     lv = 0.f;
     return;
   }
-  auto clip = [&](double r) { return a.clip_reward ? (r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r)) : r; };
   double R = (double)vboot;
   int seg_end = -1;   // first terminal at or after t: closes t's segment
   int seg_start = 0;  // first step after the last terminal before t
@@ -218,11 +217,8 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
 #pragma unroll
     for (int k = RW - 1; k >= 0; --k)
       if (k < T && k >= t) {
-        if (dn[k] & 1) {
-          R = 0.0;
-          seg_end = k;
-        }
-        R = __dadd_rn(__dmul_rn(R, a.gamma), clip((double)rw[k]));
+        if (dn[k] & 1) seg_end = k;
+        R = return_step(R, dn[k], rw[k], a.gamma, a.clip_reward);
       }
 #pragma unroll
     for (int k = 0; k < RW; ++k)
@@ -230,11 +226,8 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
   } else {
     for (int tt = T - 1; tt >= t; --tt) {
       const int64_t j = (int64_t)tt * n + e;
-      if (a.dones[j] & 1) {
-        R = 0.0;
-        seg_end = tt;
-      }
-      R = __dadd_rn(__dmul_rn(R, a.gamma), clip((double)a.rewards[j]));
+      if (a.dones[j] & 1) seg_end = tt;
+      R = return_step(R, a.dones[j], a.rewards[j], a.gamma, a.clip_reward);
     }
     for (int tt = t - 1; tt >= 0; --tt)
       if (a.dones[(int64_t)tt * n + e] & 1) {

@@ -410,6 +410,69 @@ int arl_net_set_episode_stats(arl_net* net, int on);
 int arl_episode_stats_reset(arl_net* net, void* stream);
 int arl_episode_stats(arl_net* net, double* out8_device, int clear, void* stream);
 
+/* ------------------------------------------------------------------ window statistics */
+
+/* Device-side per-window training statistics: what the reference's learner
+ * logs at every update -- pi_loss / v_loss (a3c.py:123-124), the gradient norm
+ * before the clip (a3c.py:136-141), entropy and value per step
+ * (a3c.py:161-163), the annealed learning rate -- without a host sync per
+ * window and inside a graph replay.  Off by default; additions to ABI 4.
+ * While on, every update of the net (arl_optimize, arl_optimize_advance,
+ * arl_run_window) appends one record of ARL_WINDOW_STAT_FIELDS doubles to a
+ * ring log in the workspace: one extra single-workgroup launch, stream-ordered
+ * (and graph-capturable) after the clip norm's partials exist and before the
+ * update kernel, so the control block is not yet advanced.  The record
+ * describes the window whose gradient the update consumes.  A sample (t, e),
+ * t < t_max, is live when dones[t, e] bit 1 is clear (not past a truncated
+ * window's end).
+ *    0 window        ctl window counter before the update
+ *    1 step          the per-env step counter the update's lr anneal reads
+ *    2 samples       number of live samples
+ *    3 terminals     live samples with dones bit 0
+ *    4 reward_sum    sum over live of the reward as the learner uses it:
+ *                    (double)r, clipped to [-1, 1] iff the window's clip_reward
+ *    5 pi_loss       sum over envs of (double)loss[2e]
+ *    6 v_loss        sum over envs of (double)loss[2e + 1]
+ *    7 entropy_sum   sum over live of (double)entropy[t, e]
+ *    8, 9   value_sum, value_sumsq     of (double)v[t, e] and its f64 square
+ *   10, 11  return_sum, return_sumsq   of (double)Rf and its f64 square, Rf =
+ *                    (float)R_t the learner's n-step return: f64 recurrence from
+ *                    v[t_max, e], R = 0 at bit-0 terminals, R = R * gamma + clip(r)
+ *   12, 13  adv_sum, adv_sumsq         of (double)adv, adv = f32(Rf - v), and its f64 square
+ *   14 grad_sqnorm   squared norm of the gradient the update consumes, from the
+ *                    partials the update kernel reads (with several ranks: of
+ *                    the all-reduced gradient)
+ *   15 clip_scale    (double) of the f32 scale the update applies; 1.0 when it does not clip
+ *   16 lr            (double) of the f32 learning rate the update uses, anneal included
+ * gamma and clip_reward are those of the last returns launch of the net
+ * (arl_learn, arl_learn_part(LEARN_RETURNS), the returns fused into the
+ * bootstrap step, arl_run_window); 0.99 and 1 before any.  With clip <= 0 the
+ * update still launches the squared-norm kernel while the feature is on, so
+ * field 14 is always filled; field 15 is then 1.0.
+ * All sums are float64 with unfused round-to-nearest adds / multiplies, in a
+ * fixed order: one 256-thread workgroup; thread j walks envs j, j + 256, ...
+ * ascending and, for each env, t = 0 .. t_max - 1 ascending (after one reverse
+ * scan for the R_t); each field's partials 0 .. 255 are then combined in
+ * order (partial 0, plus partial 1, ...).  A sample that is not live adds
+ * +0.0, which changes no bit.  Counts are exact integers stored as doubles.  A NumPy float64 replay in that
+ * order is bit-identical for fields 0-13; the return recurrence, the clip
+ * scale and the lr anneal are the learner's and the update kernel's own device
+ * functions, so fields 10-13, 15 and 16 are bit for bit what they use.
+ * Storage: two arl_net_buffer entries before the episode block, both 256-byte
+ * aligned: win_log, (ARL_WINDOW_LOG, ARL_WINDOW_STAT_FIELDS) float64, and
+ * win_count, one int64: records ever written; a record goes to slot
+ * count % ARL_WINDOW_LOG.  Read them through their offsets, as the episode
+ * log.  arl_net_reset zeroes both, whether the feature is on or not.
+ *
+ * arl_net_set_window_stats: on / off for the updates launched (or captured)
+ * from now on; off: no extra launch, the same kernels with the same arguments.
+ * arl_window_stats_reset: zero win_log and win_count.
+ * Both: ARL_ESTATE on an unbound net. */
+#define ARL_WINDOW_LOG 64
+#define ARL_WINDOW_STAT_FIELDS 17
+int arl_net_set_window_stats(arl_net* net, int on);
+int arl_window_stats_reset(arl_net* net, void* stream);
+
 /* ------------------------------------------------------------------ granular ops */
 
 /* RMSpropAsync.update_one (rmsprop_async.py:23-38) on flat f32 arrays, with
