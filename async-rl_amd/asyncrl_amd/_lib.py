@@ -63,6 +63,7 @@ SIGNATURES = {
     "arl_truncate_window": (c_int, [c_void_p, c_int, c_void_p]),
     "arl_net_set_loss": (c_int, [c_void_p, c_double, c_int]),
     "arl_net_set_weight_decay": (c_int, [c_void_p, c_double]),
+    "arl_net_set_gae": (c_int, [c_void_p, c_double]),
     "arl_net_set_norm_fold": (c_int, [c_void_p, c_int]),
     "arl_net_set_returns_fusion": (c_int, [c_void_p, c_int, c_double, c_double, c_double, c_int]),
     "arl_reset_state": (c_int, [c_void_p, c_i64, c_i64, c_void_p]),
@@ -95,6 +96,9 @@ SIGNATURES = {
     "arl_returns_lossgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64,
                                      c_int, c_double, c_double, c_double, c_double, c_int, c_int, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
+    "arl_returns_lossgrad_gae": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64,
+                                         c_int, c_double, c_double, c_double, c_double, c_double, c_int, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "arl_stream_copy": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p]),
     "arl_net_set_episode_stats": (c_int, [c_void_p, c_int]),
     "arl_episode_stats_reset": (c_int, [c_void_p, c_void_p]),

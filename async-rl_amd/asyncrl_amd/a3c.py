@@ -207,14 +207,20 @@ class A3C:
     def __init__(self, model: A3CModel, optimizer, t_max: int, gamma: float, beta: float = 1e-2,
                  process_idx: int = 0, clip_reward: bool = True, phi=None, pi_loss_coef: float = 1.0,
                  v_loss_coef: float = 0.5, keep_loss_scale_same: bool = False, resize_mode: int = RESIZE_SCALAR,
-                 process_group=None, batch_loss: str = "sum", collectives: bool | None = None):
-        """collectives: all-reduce the window gradient over the process group
+                 process_group=None, batch_loss: str = "sum", collectives: bool | None = None,
+                 gae_lambda: float = 1.0):
+        """gae_lambda: GAE(lambda) advantages in the policy term (an extension,
+        the reference has none; DeviceNet.set_gae).  The default 1 is the
+        reference's n-step advantage and runs exactly what ran without it.
+        collectives: all-reduce the window gradient over the process group
         (default: when torch.distributed is initialised with > 1 rank; True
         also on a one-rank group, which runs the RCCL calls of the N > 1 path
         on one GPU).  A one-env drop-in model (the reference-contract `act`)
         updates at its own episode's terminals, so its ranks would enter the
         collectives at different times: it refuses collectives, and with
         collectives=False every rank is an independent learner."""
+        if not 0.0 <= float(gae_lambda) <= 1.0:   # (nan fails both)
+            raise ValueError("gae_lambda must be in [0, 1]")
         if model.net.t_max != t_max:
             raise ValueError("model was built for a different t_max")
         if batch_loss not in ("sum", "mean"):
@@ -250,6 +256,8 @@ class A3C:
         scale = 1.0 if batch_loss == "sum" else 1.0 / (self.net.n_envs * (self.world if self.collectives else 1))
         self._vcoef = v_loss_coef * scale
         self.net.set_loss(pi_loss_coef * scale, keep_loss_scale_same)
+        self.gae_lambda = float(gae_lambda)
+        self.net.set_gae(self.gae_lambda)
         # no all-reduce between learn and update: the clip norm comes from the learner's conv reduce
         self.net.set_norm_fold(not self.collectives)
         self.t = 0          # env-steps taken (per env)

@@ -331,6 +331,13 @@ class DeviceNet:
         A captured window keeps the rate it was captured with."""
         check(lib.arl_net_set_weight_decay(self._h, float(rate)), "arl_net_set_weight_decay")
 
+    def set_gae(self, lambda_: float = 1.0):
+        """GAE(lambda) advantages in the policy term (arl_net_set_gae); the value
+        target stays the n-step return.  1 = the n-step advantage: the kernels
+        and arguments of a net that never called this.  A captured window keeps
+        the lambda it was captured with."""
+        check(lib.arl_net_set_gae(self._h, float(lambda_)), "arl_net_set_gae")
+
     # ------------------------------------------------------------ episode statistics
     episode_stats_on = False
 

@@ -418,6 +418,15 @@ int arl_net_set_weight_decay(arl_net* h, double rate) {
   return ARL_OK;
 }
 
+static bool gae_lambda_ok(double lambda) { return lambda >= 0.0 && lambda <= 1.0; }   // (nan fails both)
+
+int arl_net_set_gae(arl_net* h, double lambda) {
+  if (!h) return fail(ARL_EINVAL, "null net");
+  if (!gae_lambda_ok(lambda)) return fail(ARL_EINVAL, "set_gae: lambda must be finite and in [0, 1]");
+  h->net.gae_lambda = lambda;
+  return ARL_OK;
+}
+
 int arl_act(arl_net* h, int t, void* s) {
   NEED_BOUND(h);
   if (t < 0 || t > h->net.T) return fail(ARL_EINVAL, "act: t out of [0, t_max]");
@@ -691,6 +700,20 @@ int arl_returns_lossgrad(const float* rewards, const uint8_t* dones, const float
                                         (float)vcoef, clip_reward, dlogits, dv, loss, S(s), nullptr,
                                         (float)pi_loss_coef, keep_loss_scale_same ? 1 : 0),
                     "returns");
+}
+
+int arl_returns_lossgrad_gae(const float* rewards, const uint8_t* dones, const float* v, const float* probs,
+                             const float* logp, const int32_t* act, int T, int64_t n, int A, double gamma,
+                             double lambda, double beta, double pi_loss_coef, double vcoef, int keep_loss_scale_same,
+                             int clip_reward, float* dlogits, float* dv, float* loss, void* s) {
+  if (T < 1 || n < 0 || A < 1) return fail(ARL_EINVAL, "returns_gae: bad T / n / A");
+  if (n > 0 && (!rewards || !dones || !v || !probs || !logp || !act || !dlogits || !dv))
+    return fail(ARL_EINVAL, "returns_gae: null pointer");
+  if (!gae_lambda_ok(lambda)) return fail(ARL_EINVAL, "returns_gae: lambda must be finite and in [0, 1]");
+  return hip_status(arl::launch_returns(rewards, dones, v, probs, logp, act, T, (int)n, A, gamma, (float)beta,
+                                        (float)vcoef, clip_reward, dlogits, dv, loss, S(s), nullptr,
+                                        (float)pi_loss_coef, keep_loss_scale_same ? 1 : 0, lambda),
+                    "returns_gae");
 }
 
 int arl_stream_copy(const void* src, void* dst, int64_t bytes, int blocks, int mode, void* s) {

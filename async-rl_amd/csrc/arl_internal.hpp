@@ -201,6 +201,9 @@ struct Net {
   bool window_stats = false;
   double win_gamma = 0.99;
   int win_clip_reward = 1;
+  // GAE(lambda) advantages of the policy term (arl_net_set_gae; 1 = the n-step advantage, today's kernels):
+  // read at every returns launch; win_lambda = that of the net's last returns launch, beside win_gamma
+  double gae_lambda = 1.0, win_lambda = 1.0;
   int hid;                 // width of the layer the heads read (256 NIPS / LSTM, 512 Nature)
   int env_offset;          // global id of env 0 on this rank (RNG stream)
   uint64_t seed;
@@ -465,9 +468,10 @@ struct WindowStatsArgs {
 // One 256-thread workgroup (optim.hip window_stats_kernel).  The remaining arguments are launch_rmsprop's for
 // the update that follows, so that the recorded lr and clip scale come from the values (and the device
 // functions) the update kernel uses; norm_sq is always given, clip <= 0: the update does not clip.
+// lambda != 1: adv_sum / adv_sumsq are those of the GAE advantage (gae_step), another kernel; 1: today's launch
 hipError_t launch_window_stats(const WindowStatsArgs& w, double lr, const double* norm_sq, int nparts, float clip,
                                const int64_t* lr_ctl, int64_t total_steps, int64_t n_total, int t_max, bool advance,
-                               hipStream_t s);
+                               hipStream_t s, double lambda = 1.0);
 hipError_t launch_stream_copy(const void* src, void* dst, int64_t bytes, int blocks, int mode, hipStream_t s);
 hipError_t launch_policy(const float* h, int64_t n, const float* Wpi, const float* bpi, const float* Wv,
                          const float* bv, int A, uint64_t seed, const int64_t* ctl, int64_t step_off,
@@ -484,20 +488,33 @@ __device__ inline double return_step(double R, int done, float r, double gamma, 
   if (done & 1) R = 0.0;
   return __dadd_rn(__dmul_rn(R, gamma), clip_reward_f64(r, clip_reward));
 }
+// GAE(lambda) (Schulman et al. 2016; an extension, the reference has none), one step backwards in time beside
+// return_step: delta_k = (r_k + gamma v(s_k+1)) - v(s_k) with v(s_k+1) = 0 after a terminal, then
+// G = delta_k + gl G with G = 0 carried across a terminal; gl = gamma * lambda, one f64 product of the host.
+// f64, unfused.  vnext of step T - 1 is the bootstrap value.  The advantage of step t is (float)G after k = t.
+__device__ inline double gae_step(double G, int done, float r, float vk, float vnext, double gamma, double gl,
+                                  int clip_reward) {
+  const double vn = (done & 1) ? 0.0 : (double)vnext;
+  const double d = __dsub_rn(__dadd_rn(clip_reward_f64(r, clip_reward), __dmul_rn(gamma, vn)), (double)vk);
+  if (done & 1) G = 0.0;
+  return __dadd_rn(d, __dmul_rn(gl, G));
+}
+// lambda == 1 is not GAE: the launchers below then run the n-step kernels with the arguments they always had
+inline bool gae_on(double lambda) { return lambda != 1.0; }
 // dones: bit 0 = the transition t -> t+1 ended the episode; bit 1 = step t lies
 // past the end of this window (arl_truncate_window: no loss, no gradient).
 // pcoef = pi_loss_coef; keep_scale: keep_loss_scale_same (a3c.py:110-121)
 hipError_t launch_returns(const float* rewards, const uint8_t* dones, const float* v, const float* probs,
                           const float* logp, const int32_t* act, int T, int n, int A, double gamma, float beta,
                           float vcoef, int clip_reward, float* dlogits, float* dv, float* loss, hipStream_t s,
-                          int64_t* ctl_snap = nullptr, float pcoef = 1.f, int keep_scale = 0);
+                          int64_t* ctl_snap = nullptr, float pcoef = 1.f, int keep_scale = 0, double lambda = 1.0);
 // launch_returns + the heads' backward dh = dlogits Wpi + dv Wv (times
 // mask > 0 when mask is given) for hidden width HID, one launch (T <= 64)
 hipError_t launch_returns_heads(const float* rewards, const uint8_t* dones, const float* v, const float* probs,
                                 const float* logp, const int32_t* act, int T, int n, int A, double gamma, float beta,
                                 float vcoef, int clip_reward, float* dlogits, float* dv, float* loss, hipStream_t s,
                                 int64_t* ctl_snap, float pcoef, int keep_scale, const float* Wpi, const float* Wv,
-                                const float* mask, float* dh);
+                                const float* mask, float* dh, double lambda = 1.0);
 // launch_policy_fc of the bootstrap slot (no draw) + launch_returns_heads for the same n envs, one launch
 // (policy.hip policy_fc_returns_kernel; v(s_T) handed over in LDS); bit-identical to the two launches
 hipError_t launch_policy_fc_returns(const float* slab, int n, const float* fc_bias, float* hfc, const PolicyArgs& pa,
@@ -505,6 +522,6 @@ hipError_t launch_policy_fc_returns(const float* slab, int n, const float* fc_bi
                                     const float* logp, const int32_t* act, int T, double gamma, float beta,
                                     float vcoef, int clip_reward, float* dlogits, float* dv, float* loss,
                                     int64_t* ctl_snap, float pcoef, int keep_scale, const float* mask, float* dh,
-                                    hipStream_t s);
+                                    hipStream_t s, double lambda = 1.0);
 
 }  // namespace arl

@@ -395,11 +395,13 @@ hipError_t net_act(Net& net, int t, int mode, hipStream_t s, int e0, int ne) {
                                        net.at<int32_t>(net.w_act), net.T, r.gamma, r.beta, r.vcoef, r.clip_reward,
                                        net.at<float>(net.w_dlogits), net.at<float>(net.w_dv),
                                        net.at<float>(net.w_loss), net.at<int64_t>(net.w_ctl), net.pi_coef,
-                                       net.keep_scale, net.at<float>(net.w_hfc), net.at<float>(net.w_dfc), s));
+                                       net.keep_scale, net.at<float>(net.w_hfc), net.at<float>(net.w_dfc), s,
+                                       net.gae_lambda));
       net.returns_done = true;
       net.norm_ready = false;   // a new gradient (as LEARN_RETURNS)
       net.win_gamma = r.gamma;
       net.win_clip_reward = r.clip_reward;
+      net.win_lambda = net.gae_lambda;
       return stamp(net, STAGE_POLICY, s);
     }
     ARL_TRY(launch_policy_fc(fc_slab, ne, P + net.o_fcb, hfc, pa, s));
@@ -565,13 +567,14 @@ hipError_t net_learn_part(Net& net, int part, double gamma, float beta, float vc
     net.norm_ready = false;   // a new gradient: no folded norm until net_learn's reduce
     net.win_gamma = gamma;
     net.win_clip_reward = clip_reward;
+    net.win_lambda = net.gae_lambda;
     ARL_TRY(launch_returns_heads(net.at<float>(net.w_rewards), net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v),
                                  net.at<float>(net.w_probs), net.at<float>(net.w_logp), net.at<int32_t>(net.w_act), T,
                                  n, A, gamma, beta, vcoef, clip_reward, net.at<float>(net.w_dlogits),
                                  net.at<float>(net.w_dv), net.at<float>(net.w_loss), s, net.at<int64_t>(net.w_ctl),
                                  net.pi_coef, net.keep_scale, P + net.o_piW, P + net.o_vW,
                                  L ? nullptr : net.at<float>(net.w_hfc),
-                                 L ? net.at<float>(net.w_dh) : net.at<float>(net.w_dfc)));
+                                 L ? net.at<float>(net.w_dh) : net.at<float>(net.w_dfc), net.gae_lambda));
     return stamp(net, STAGE_RETURNS, s);
   }
   if (part == LEARN_CONV) {
@@ -717,7 +720,8 @@ hipError_t net_optimize(Net& net, double lr0, int64_t total_steps, int64_t n_tot
                             net.at<float>(net.w_ent), net.at<float>(net.w_loss), net.T, net.N, net.win_gamma,
                             net.win_clip_reward, net.at<int64_t>(net.w_ctl), net.at<double>(net.w_win_log),
                             net.at<int64_t>(net.w_win_count)};
-    ARL_TRY(launch_window_stats(w, lr0, parts, nparts, clip, lr_ctl, total_steps, n_total, net.T, fused, s));
+    ARL_TRY(launch_window_stats(w, lr0, parts, nparts, clip, lr_ctl, total_steps, n_total, net.T, fused, s,
+                                net.win_lambda));
   }
   const bool L = net.arch == ARCH_LSTM;
   // the update rewrites the FC weight's split planes with the new W (all of them, so they are current

@@ -262,9 +262,12 @@ __device__ inline void ws_env(double* acc, float pi_loss, float v_loss) {
 // One sample (t, e) into the sums, without a branch.  A sample past a truncated window's end (dones bit
 // 1) adds +0.0 to every sum, which leaves its bits alone: the sums start at +0.0, and a round-to-nearest
 // sum that started there is never -0.0, the only value x + 0.0 would change.
-__device__ inline void ws_sample(double* acc, int d, float r, float vi, float ent, float rf, int clip_reward) {
+// G (the kernel's GAE form, below): the advantage is af, the GAE one the learner used, instead of f32(rf - vi).
+template <bool G>
+__device__ inline void ws_sample(double* acc, int d, float r, float vi, float ent, float rf, float af,
+                                 int clip_reward) {
   const bool live = (d & 2) == 0;
-  const double vd = (double)vi, rd = (double)rf, ad = (double)__fsub_rn(rf, vi);
+  const double vd = (double)vi, rd = (double)rf, ad = G ? (double)af : (double)__fsub_rn(rf, vi);
   const double x[WS_SUMS] = {1.0, (d & 1) ? 1.0 : 0.0, clip_reward_f64(r, clip_reward), 0.0, 0.0, (double)ent,
                              vd, __dmul_rn(vd, vd), rd, __dmul_rn(rd, rd), ad, __dmul_rn(ad, ad)};
 #pragma unroll
@@ -272,8 +275,19 @@ __device__ inline void ws_sample(double* acc, int d, float r, float vi, float en
     if (f != 3 && f != 4) acc[f] = __dadd_rn(acc[f], live ? x[f] : 0.0);
 }
 
+// GAE form (G, compile time; the host picks it for lambda != 1): adv_sum / adv_sumsq are the sums of the GAE
+// advantage, the f32 the learner used, from the same gae_step on the same values.  The register path scans it
+// beside R.  The memory path has one LDS column per thread, so after an env's samples are summed with a zero
+// advantage (+0.0 leaves the two sums' bits alone, as above) a second reverse scan puts the advantages in the
+// column and a second ascent adds them: each sum still sees its terms in the order t ascending, env by env.
+struct WindowStatsArgsGae : WindowStatsArgs {
+  double gl;   // gamma * lambda
+};
+template <bool G>
+using WindowStatsArgsT = std::conditional_t<G, WindowStatsArgsGae, WindowStatsArgs>;
+template <bool G = false>
 __global__ void __launch_bounds__(256)
-window_stats_kernel(WindowStatsArgs w, RmsConst c, const double* __restrict__ norm_sq, int nparts, float clip) {
+window_stats_kernel(WindowStatsArgsT<G> w, RmsConst c, const double* __restrict__ norm_sq, int nparts, float clip) {
   extern __shared__ double dyn[];
   const int j = threadIdx.x, T = w.T, n = w.n;
   // what only the record's writer needs, loaded first so that it is there by the end
@@ -291,18 +305,24 @@ window_stats_kernel(WindowStatsArgs w, RmsConst c, const double* __restrict__ no
     if (j < n) ws_load(w, j, cur);
     for (int e = j; e < n; e += 256) {
       ws_load(w, e + 256 < n ? e + 256 : e, nxt);   // (past the last env: this one again, unused)
-      float rf[WS_RW];
+      float rf[WS_RW], af[WS_RW] = {};
       double R = (double)cur.vboot;
+      double Gl = 0.0;
 #pragma unroll
       for (int k = WS_RW - 1; k >= 0; --k)
         if (k < T) {
           R = return_step(R, cur.dn[k], cur.rw[k], w.gamma, w.clip_reward);
           rf[k] = (float)R;
+          if constexpr (G) {
+            Gl = gae_step(Gl, cur.dn[k], cur.rw[k], cur.vv[k], k == T - 1 ? cur.vboot : cur.vv[k < WS_RW - 1 ? k + 1 : k],
+                          w.gamma, w.gl, w.clip_reward);
+            af[k] = (float)Gl;
+          }
         }
       ws_env(acc, cur.l0, cur.l1);
 #pragma unroll
       for (int k = 0; k < WS_RW; ++k)
-        if (k < T) ws_sample(acc, cur.dn[k], cur.rw[k], cur.vv[k], cur.en[k], rf[k], w.clip_reward);
+        if (k < T) ws_sample<G>(acc, cur.dn[k], cur.rw[k], cur.vv[k], cur.en[k], rf[k], af[k], w.clip_reward);
       cur = nxt;
     }
   } else {            // longer windows: loops over memory, the R_t of the reverse scan in the thread's LDS column
@@ -317,7 +337,22 @@ window_stats_kernel(WindowStatsArgs w, RmsConst c, const double* __restrict__ no
       ws_env(acc, w.loss[2 * e], w.loss[2 * e + 1]);
       for (int t = 0; t < T; ++t) {
         const int64_t i = (int64_t)t * n + e;
-        ws_sample(acc, w.dones[i], w.rewards[i], w.v[i], w.entropy[i], Rf[t * 256 + j], w.clip_reward);
+        ws_sample<G>(acc, w.dones[i], w.rewards[i], w.v[i], w.entropy[i], Rf[t * 256 + j], 0.f, w.clip_reward);
+      }
+      if constexpr (G) {
+        const float vboot = w.v[(int64_t)T * n + e];
+        double Gl = 0.0;
+        for (int t = T - 1; t >= 0; --t) {
+          const int64_t i = (int64_t)t * n + e;
+          Gl = gae_step(Gl, w.dones[i], w.rewards[i], w.v[i], t == T - 1 ? vboot : w.v[i + n], w.gamma, w.gl,
+                        w.clip_reward);
+          Rf[t * 256 + j] = (float)Gl;
+        }
+        for (int t = 0; t < T; ++t) {
+          const double ad = (w.dones[(int64_t)t * n + e] & 2) ? 0.0 : (double)Rf[t * 256 + j];
+          acc[10] = __dadd_rn(acc[10], ad);
+          acc[11] = __dadd_rn(acc[11], __dmul_rn(ad, ad));
+        }
       }
     }
   }
@@ -380,13 +415,20 @@ static RmsConst rms_const(double lr, double alpha, double eps, const int64_t* ct
 
 hipError_t launch_window_stats(const WindowStatsArgs& w, double lr, const double* norm_sq, int nparts, float clip,
                                const int64_t* lr_ctl, int64_t total_steps, int64_t n_total, int t_max, bool advance,
-                               hipStream_t s) {
+                               hipStream_t s, double lambda) {
   if (w.T < 1 || w.T > 64 || w.n < 1) return hipErrorInvalidValue;   // (the R_t columns: at most 64 KB of LDS)
   if (norm_sq == nullptr || nparts < 1 || nparts > NORM_MAX_PARTS) return hipErrorInvalidValue;
   // alpha / eps do not enter the record
   const RmsConst c = rms_const(lr, 0.0, 0.0, lr_ctl, total_steps, n_total, t_max, advance);
   const size_t lds = std::max(w.T > WS_RW ? (size_t)w.T * 256 * sizeof(float) : 0, (size_t)WS_SUMS * 256 * sizeof(double));
-  hipLaunchKernelGGL(window_stats_kernel, dim3(1), dim3(256), lds, s, w, c, norm_sq, nparts, clip);
+  if (gae_on(lambda)) {
+    WindowStatsArgsGae wg;
+    static_cast<WindowStatsArgs&>(wg) = w;
+    wg.gl = w.gamma * lambda;
+    hipLaunchKernelGGL(window_stats_kernel<true>, dim3(1), dim3(256), lds, s, wg, c, norm_sq, nparts, clip);
+  } else {
+    hipLaunchKernelGGL(window_stats_kernel<false>, dim3(1), dim3(256), lds, s, w, c, norm_sq, nparts, clip);
+  }
   return hipGetLastError();
 }
 

@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "arl_internal.hpp"
 #include "policy_rows.hpp"
@@ -151,6 +152,12 @@ struct ReturnsArgs {
   float* loss;
   int64_t* ctl;
 };
+// the GAE form's arguments (below): + gl = gamma * lambda.  ReturnsArgsT<false> is ReturnsArgs itself.
+struct ReturnsArgsGae : ReturnsArgs {
+  double gl;
+};
+template <bool G>
+using ReturnsArgsT = std::conditional_t<G, ReturnsArgsGae, ReturnsArgs>;
 
 // dlogits / dv of (step t, env e); returns the two loss terms of the step
 // (pi term without the sign, v term) through lpi / lv
@@ -160,16 +167,27 @@ struct ReturnsArgs {
 // wait for the one before it.  Windows up to RW steps keep their rewards /
 // dones in registers; longer ones loop over memory.
 constexpr int RW = 8;
+// GAE form (G, compile time; the host picks it for lambda != 1, arl_net_set_gae): the policy term's advantage
+// is the GAE(lambda) one (gae_step) instead of f32(Rf - v); the value target stays the n-step return.  It
+// carries gl = gamma * lambda and the register window of v: v[0 .. RW-1] at clamped offsets beside vboot, the
+// RW + 1 values v[k + 1] is taken from.  The G = false forms hold and do nothing more than they did.
+template <bool G>
+struct GaeIn {};
+template <>
+struct GaeIn<true> {
+  float vw[RW];
+  double gl;
+};
 // AM >= A: the action count the registers are sized for (4 / 8 / MAXA)
-template <int AM>
-struct RetIn {   // everything returns_one reads of step (t, e)
+template <int AM, bool G = false>
+struct RetIn : GaeIn<G> {   // everything returns_one reads of step (t, e)
   float pr[AM], lp[AM], rw[RW];
   int dn[RW];
   float vboot, vi;
   int ac, di;
 };
-template <int AM>
-__device__ inline void returns_load(const ReturnsArgs& a, int t, int e, RetIn<AM>& in) {
+template <int AM, bool G>
+__device__ inline void returns_load(const ReturnsArgs& a, int t, int e, RetIn<AM, G>& in) {
   const int T = a.T, n = a.n, A = a.A;
   const int64_t i = (int64_t)t * n + e;
 #pragma unroll
@@ -183,15 +201,16 @@ __device__ inline void returns_load(const ReturnsArgs& a, int t, int e, RetIn<AM
     const int64_t o = (int64_t)min(k, T - 1) * n + e;
     in.rw[k] = a.rewards[o];
     in.dn[k] = a.dones[o];
+    if constexpr (G) in.vw[k] = a.v[o];
   }
   in.vboot = a.v[(int64_t)T * n + e];
   in.vi = a.v[i];
   in.ac = a.act[i];
   in.di = a.dones[i];
 }
-template <int AM>
-__device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const RetIn<AM>& in, float& lpi, float& lv,
-                                       float* sdl) {
+template <int AM, bool G>
+__device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const RetIn<AM, G>& in, float& lpi,
+                                       float& lv, float* sdl) {
   const int T = a.T, n = a.n, A = a.A;
   const int64_t i = (int64_t)t * n + e;
   const float* pr = in.pr;
@@ -211,6 +230,7 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
     return;
   }
   double R = (double)vboot;
+  double Gl = 0.0;    // GAE form: the advantage's scan, beside R's
   int seg_end = -1;   // first terminal at or after t: closes t's segment
   int seg_start = 0;  // first step after the last terminal before t
   if (T <= RW) {
@@ -219,6 +239,9 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
       if (k < T && k >= t) {
         if (dn[k] & 1) seg_end = k;
         R = return_step(R, dn[k], rw[k], a.gamma, a.clip_reward);
+        if constexpr (G)   // v[k + 1]: the bootstrap value at the window's last step (k = RW - 1 is always that)
+          Gl = gae_step(Gl, dn[k], rw[k], in.vw[k], k == T - 1 ? vboot : in.vw[k < RW - 1 ? k + 1 : k], a.gamma,
+                        in.gl, a.clip_reward);
       }
 #pragma unroll
     for (int k = 0; k < RW; ++k)
@@ -228,6 +251,9 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
       const int64_t j = (int64_t)tt * n + e;
       if (a.dones[j] & 1) seg_end = tt;
       R = return_step(R, a.dones[j], a.rewards[j], a.gamma, a.clip_reward);
+      if constexpr (G)
+        Gl = gae_step(Gl, a.dones[j], a.rewards[j], a.v[j], tt == T - 1 ? vboot : a.v[j + n], a.gamma, in.gl,
+                      a.clip_reward);
     }
     for (int tt = t - 1; tt >= 0; --tt)
       if (a.dones[(int64_t)tt * n + e] & 1) {
@@ -245,7 +271,9 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
     }
   }
   const float Rf = (float)R;
-  const float adv = __fsub_rn(Rf, vi);
+  float adv;
+  if constexpr (G) adv = (float)Gl;
+  else adv = __fsub_rn(Rf, vi);
   float H = 0.f, lpa = 0.f;
 #pragma unroll
   for (int k = 0; k < AM; ++k)
@@ -271,8 +299,10 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
   lpi = __fmul_rn(pf, __fadd_rn(__fmul_rn(lpa, adv), __fmul_rn(a.beta, H)));
   lv = __fmul_rn(vf, __fmul_rn(__fmul_rn(dvv, dvv), 0.5f));
 }
-__device__ inline void returns_one(const ReturnsArgs& a, int t, int e, float& lpi, float& lv) {
-  RetIn<MAXA> in;
+template <bool G>
+__device__ inline void returns_one(const ReturnsArgsT<G>& a, int t, int e, float& lpi, float& lv) {
+  RetIn<MAXA, G> in;
+  if constexpr (G) in.gl = a.gl;
   returns_load(a, t, e, in);
   returns_compute(a, t, e, in, lpi, lv, nullptr);
 }
@@ -288,15 +318,16 @@ __device__ inline void env_loss(const ReturnsArgs& a, const float* lpi, const fl
   a.loss[2 * e + 1] = v_loss;
 }
 
+template <bool G = false>
 __global__ void __launch_bounds__(256)
-returns_kernel(ReturnsArgs a) {
+returns_kernel(ReturnsArgsT<G> a) {
   __shared__ float lpi[256], lv[256];
   if (a.ctl != nullptr && blockIdx.x == 0 && threadIdx.x == 0) a.ctl[CTL_STEP_SNAP] = a.ctl[CTL_STEP];
   const int EB = 256 / a.T;
   const int tid = threadIdx.x, t = tid / EB, el = tid - t * EB;
   const int e = blockIdx.x * EB + el;
   const bool on = t < a.T && e < a.n;
-  if (on) returns_one(a, t, e, lpi[tid], lv[tid]);
+  if (on) returns_one<G>(a, t, e, lpi[tid], lv[tid]);
   if (a.loss == nullptr) return;
   __syncthreads();
   if (t == 0 && on) env_loss(a, lpi, lv, EB, el, e);
@@ -314,19 +345,19 @@ returns_kernel(ReturnsArgs a) {
 // AM >= A actions, RB rows (steps) per pass: the register arrays (mask
 // entries, head-weight column, loaded probs / log-probs) are sized for the
 // window, e.g. 5 rows and 4 actions at C2 instead of 32 and 32
-template <int AM, int RB>
+template <int AM, int RB, bool G = false>
 struct RhState {
   float mv[RB];
   int64_t so[RB];
   float wc[AM + 1];
-  RetIn<AM> in;
+  RetIn<AM, G> in;
 };
 
 // mask entries of rows r0 .. r0 + RB - 1 (row r = step r of env e) for column j = threadIdx.x
 // (unconditional loads at clamped offsets: a load under a per-lane branch would wait for each one in turn)
-template <int AM, int RB>
+template <int AM, int RB, bool G>
 __device__ inline void rh_rows(const ReturnsArgs& a, const float* __restrict__ mask, int e, int r0,
-                               RhState<AM, RB>& st) {
+                               RhState<AM, RB, G>& st) {
   const int j = threadIdx.x;
 #pragma unroll
   for (int u = 0; u < RB; ++u) {
@@ -337,9 +368,9 @@ __device__ inline void rh_rows(const ReturnsArgs& a, const float* __restrict__ m
   for (int u = 0; u < RB; ++u) st.mv[u] = mask != nullptr ? mask[st.so[u] < 0 ? j : st.so[u]] : 1.f;
 }
 
-template <int AM, int RB>
+template <int AM, int RB, bool G>
 __device__ inline void rh_load(const ReturnsArgs& a, const float* __restrict__ Wpi, const float* __restrict__ Wv,
-                               const float* __restrict__ mask, int e, RhState<AM, RB>& st) {
+                               const float* __restrict__ mask, int e, RhState<AM, RB, G>& st) {
   const int T = a.T, A = a.A, j = threadIdx.x;
   rh_rows(a, mask, e, 0, st);
 #pragma unroll
@@ -348,9 +379,9 @@ __device__ inline void rh_load(const ReturnsArgs& a, const float* __restrict__ W
 }
 
 // lpi / lv: 64 floats, sdl: 64 (AM + 1), w: (AM + 1) HID of LDS
-template <int AM, int RB>
+template <int AM, int RB, bool G>
 __device__ inline void rh_finish(const ReturnsArgs& a, const float* __restrict__ mask, float* __restrict__ dh, int e,
-                                 RhState<AM, RB>& st, float* lpi, float* lv, float* sdl, float* w) {
+                                 RhState<AM, RB, G>& st, float* lpi, float* lv, float* sdl, float* w) {
   const int T = a.T, A = a.A;
   const int tid = threadIdx.x, t = tid, j = tid;
   const bool on = t < T && e < a.n;
@@ -374,15 +405,16 @@ __device__ inline void rh_finish(const ReturnsArgs& a, const float* __restrict__
   }
 }
 
-template <int AM, int RB>
+template <int AM, int RB, bool G = false>
 __global__ void __launch_bounds__(256)
-returns_heads_kernel(ReturnsArgs a, const float* __restrict__ Wpi, const float* __restrict__ Wv,
+returns_heads_kernel(ReturnsArgsT<G> a, const float* __restrict__ Wpi, const float* __restrict__ Wv,
                      const float* __restrict__ mask, float* __restrict__ dh) {
   __shared__ float lpi[64], lv[64];
   __shared__ float sdl[64 * (AM + 1)];
   __shared__ float w[(AM + 1) * HID];
   if (a.ctl != nullptr && blockIdx.x == 0 && threadIdx.x == 0) a.ctl[CTL_STEP_SNAP] = a.ctl[CTL_STEP];
-  RhState<AM, RB> st;
+  RhState<AM, RB, G> st;
+  if constexpr (G) st.in.gl = a.gl;
   rh_load(a, Wpi, Wv, mask, blockIdx.x, st);
   rh_finish(a, mask, dh, blockIdx.x, st, lpi, lv, sdl, w);
 }
@@ -394,10 +426,11 @@ returns_heads_kernel(ReturnsArgs a, const float* __restrict__ Wpi, const float* 
 // f32 the policy stores to v).  Every load of the returns part is issued
 // before the FC partials' loads.  Results are bit-identical to the two
 // launches: the same per-element arithmetic in the same order.
-template <int AM, int RB>
+// GAE form: v(s_T) from LDS as here; the other v rows (slots 0 .. T - 1, earlier launches' stores) from memory.
+template <int AM, int RB, bool G = false>
 __global__ void __launch_bounds__(256)
 policy_fc_returns_kernel(const float* __restrict__ slab, int n, const float* __restrict__ fc_bias,
-                         float* __restrict__ hfc, PolicyArgs pa, ReturnsArgs ra, const float* __restrict__ mask,
+                         float* __restrict__ hfc, PolicyArgs pa, ReturnsArgsT<G> ra, const float* __restrict__ mask,
                          float* __restrict__ dh) {
   __shared__ float part[4][16][MAXA + 2];
   __shared__ float zs[16][MAXA + 2];
@@ -409,7 +442,8 @@ policy_fc_returns_kernel(const float* __restrict__ slab, int n, const float* __r
   const int tid = threadIdx.x;
   const int e = blockIdx.x;
   if (ra.ctl != nullptr && e == 0 && tid == 0) ra.ctl[CTL_STEP_SNAP] = ra.ctl[CTL_STEP];
-  RhState<AM, RB> st;
+  RhState<AM, RB, G> st;
+  if constexpr (G) st.in.gl = ra.gl;
   rh_load(ra, pa.Wpi, pa.Wv, mask, e, st);
   const HeadsPrefetch<HID> pf = heads_prefetch<HID>(pa);
   // policy_fc_kernel's row (PF_ROWS = 1): threads 0..63 hold one float4 column of the 8 partials
@@ -437,16 +471,27 @@ policy_fc_returns_kernel(const float* __restrict__ slab, int n, const float* __r
   rh_finish(ra, mask, dh, e, st, lpi, lv, sdl, w);
 }
 
+// gl = gamma * lambda: one f64 product, formed here on the host
+static ReturnsArgsGae gae_args(const ReturnsArgs& ra, double lambda) {
+  ReturnsArgsGae rg;
+  static_cast<ReturnsArgs&>(rg) = ra;
+  rg.gl = ra.gamma * lambda;
+  return rg;
+}
+
 hipError_t launch_returns(const float* rewards, const uint8_t* dones, const float* v, const float* probs,
                           const float* logp, const int32_t* act, int T, int n, int A, double gamma, float beta,
                           float vcoef, int clip_reward, float* dlogits, float* dv, float* loss, hipStream_t s,
-                          int64_t* ctl_snap, float pcoef, int keep_scale) {
+                          int64_t* ctl_snap, float pcoef, int keep_scale, double lambda) {
   if (n <= 0) return hipSuccess;
   if (T < 1 || T > 256) return hipErrorInvalidValue;
   const int EB = 256 / T;
   const ReturnsArgs ra{rewards, dones, v, probs, logp, act, T, n, A, gamma, beta, vcoef, pcoef, clip_reward,
                        keep_scale, dlogits, dv, loss, ctl_snap};
-  hipLaunchKernelGGL(returns_kernel, dim3((n + EB - 1) / EB), dim3(256), 0, s, ra);
+  if (gae_on(lambda))
+    hipLaunchKernelGGL(returns_kernel<true>, dim3((n + EB - 1) / EB), dim3(256), 0, s, gae_args(ra, lambda));
+  else
+    hipLaunchKernelGGL(returns_kernel<false>, dim3((n + EB - 1) / EB), dim3(256), 0, s, ra);
   return hipGetLastError();
 }
 
@@ -454,12 +499,20 @@ hipError_t launch_returns_heads(const float* rewards, const uint8_t* dones, cons
                                 const float* logp, const int32_t* act, int T, int n, int A, double gamma, float beta,
                                 float vcoef, int clip_reward, float* dlogits, float* dv, float* loss, hipStream_t s,
                                 int64_t* ctl_snap, float pcoef, int keep_scale, const float* Wpi, const float* Wv,
-                                const float* mask, float* dh) {
+                                const float* mask, float* dh, double lambda) {
   if (n <= 0) return hipSuccess;
   if (T < 1 || T > 64 || A < 1 || A > MAXA) return hipErrorInvalidValue;
   const ReturnsArgs ra{rewards, dones, v, probs, logp, act, T, n, A, gamma, beta, vcoef, pcoef, clip_reward,
                        keep_scale, dlogits, dv, loss, ctl_snap};
   const dim3 grid(n), blk(256);
+  if (gae_on(lambda)) {
+    const ReturnsArgsGae rg = gae_args(ra, lambda);
+    if (T > 8) hipLaunchKernelGGL((returns_heads_kernel<MAXA, 32, true>), grid, blk, 0, s, rg, Wpi, Wv, mask, dh);
+    else if (A <= 4) hipLaunchKernelGGL((returns_heads_kernel<4, 8, true>), grid, blk, 0, s, rg, Wpi, Wv, mask, dh);
+    else if (A <= 8) hipLaunchKernelGGL((returns_heads_kernel<8, 8, true>), grid, blk, 0, s, rg, Wpi, Wv, mask, dh);
+    else hipLaunchKernelGGL((returns_heads_kernel<MAXA, 8, true>), grid, blk, 0, s, rg, Wpi, Wv, mask, dh);
+    return hipGetLastError();
+  }
   if (T <= 8) {
     if (A <= 4) hipLaunchKernelGGL((returns_heads_kernel<4, 8>), grid, blk, 0, s, ra, Wpi, Wv, mask, dh);
     else if (A <= 8) hipLaunchKernelGGL((returns_heads_kernel<8, 8>), grid, blk, 0, s, ra, Wpi, Wv, mask, dh);
@@ -475,13 +528,29 @@ hipError_t launch_policy_fc_returns(const float* slab, int n, const float* fc_bi
                                     const float* logp, const int32_t* act, int T, double gamma, float beta,
                                     float vcoef, int clip_reward, float* dlogits, float* dv, float* loss,
                                     int64_t* ctl_snap, float pcoef, int keep_scale, const float* mask, float* dh,
-                                    hipStream_t s) {
+                                    hipStream_t s, double lambda) {
   if (n <= 0) return hipSuccess;
   const int A = pa.A;
   if (T < 1 || T > 64 || A < 1 || A > MAXA) return hipErrorInvalidValue;
   const ReturnsArgs ra{rewards, dones, v, probs, logp, act, T, n, A, gamma, beta, vcoef, pcoef, clip_reward,
                        keep_scale, dlogits, dv, loss, ctl_snap};
   const dim3 grid(n), blk(256);
+  if (gae_on(lambda)) {
+    const ReturnsArgsGae rg = gae_args(ra, lambda);
+    if (T > 8)
+      hipLaunchKernelGGL((policy_fc_returns_kernel<MAXA, 32, true>), grid, blk, 0, s, slab, n, fc_bias, hfc, pa, rg,
+                         mask, dh);
+    else if (A <= 4)
+      hipLaunchKernelGGL((policy_fc_returns_kernel<4, 8, true>), grid, blk, 0, s, slab, n, fc_bias, hfc, pa, rg, mask,
+                         dh);
+    else if (A <= 8)
+      hipLaunchKernelGGL((policy_fc_returns_kernel<8, 8, true>), grid, blk, 0, s, slab, n, fc_bias, hfc, pa, rg, mask,
+                         dh);
+    else
+      hipLaunchKernelGGL((policy_fc_returns_kernel<MAXA, 8, true>), grid, blk, 0, s, slab, n, fc_bias, hfc, pa, rg,
+                         mask, dh);
+    return hipGetLastError();
+  }
   if (T <= 8) {
     if (A <= 4)
       hipLaunchKernelGGL((policy_fc_returns_kernel<4, 8>), grid, blk, 0, s, slab, n, fc_bias, hfc, pa, ra, mask, dh);

@@ -200,6 +200,32 @@ int arl_net_set_loss(arl_net* net, double pi_loss_coef, int keep_loss_scale_same
  * arl_run_stage(ARL_STAGE_RMSPROP) stays the decay-free timing form. */
 int arl_net_set_weight_decay(arl_net* net, double rate);
 
+/* Generalized advantage estimation, GAE(lambda) (Schulman et al. 2016), for
+ * the policy term.  An extension: the reference has only the n-step advantage.
+ * With lambda != 1 the learner's returns kernel also scans, per env and in
+ * float64 with unfused round-to-nearest operations, k = t_max - 1 .. t:
+ *   r_k   = (double)rewards[k, e], clipped to [-1, 1] iff clip_reward
+ *   vn    = dones[k, e] bit 0 ? 0.0 : (double)v[k + 1, e]    (v[t_max, e]: the bootstrap value)
+ *   d_k   = (r_k + gamma * vn) - (double)v[k, e]
+ *   G     = dones[k, e] bit 0 ? 0.0 : G                      (G = 0.0 before the scan)
+ *   G     = d_k + gl * G,       gl = gamma * lambda, one float64 product of the host
+ *   adv_t = (float)G after k = t
+ * and adv_t replaces f32(Rf - v) in dlogits and in the pi_loss term.  The value
+ * target stays the n-step return, so R, dv and v_loss are bit for bit what
+ * they are without it; pi_loss_coef, keep_loss_scale_same, beta and a
+ * truncated window (dones bit 1) behave as before, and a terminal cuts the
+ * scan, so steps past a truncated window's end do not reach a live step.
+ * lambda == 1 (the default) is not routed through this: the n-step kernels
+ * run with the arguments they always had.
+ * Host state of the handle, like arl_net_set_loss (works on an unbound handle),
+ * read at every returns launch: arl_learn, arl_learn_part(LEARN_RETURNS), the
+ * returns fused into the bootstrap step, arl_run_window, every architecture.
+ * gl is a kernel argument, so a captured graph keeps the lambda it was
+ * captured with (as it keeps gamma and the weight-decay rate): changing it
+ * needs a re-capture.  lambda outside [0, 1] or not finite: ARL_EINVAL.
+ * Addition to ABI 4. */
+int arl_net_set_gae(arl_net* net, double lambda);
+
 /* GradientClipping's squared norm (a3c_ale.py:226) folded into arl_learn:
  * with on != 0, arl_learn's conv slab reduce also leaves the f64 partial
  * sums of squares of the whole gradient (the conv tensors it writes, and the
@@ -438,13 +464,15 @@ int arl_episode_stats(arl_net* net, double* out8_device, int clear, void* stream
  *   10, 11  return_sum, return_sumsq   of (double)Rf and its f64 square, Rf =
  *                    (float)R_t the learner's n-step return: f64 recurrence from
  *                    v[t_max, e], R = 0 at bit-0 terminals, R = R * gamma + clip(r)
- *   12, 13  adv_sum, adv_sumsq         of (double)adv, adv = f32(Rf - v), and its f64 square
+ *   12, 13  adv_sum, adv_sumsq         of (double)adv, adv = f32(Rf - v), and its f64 square;
+ *                    with arl_net_set_gae(lambda != 1) adv is the GAE adv_t the learner
+ *                    used (the same device function on the same values)
  *   14 grad_sqnorm   squared norm of the gradient the update consumes, from the
  *                    partials the update kernel reads (with several ranks: of
  *                    the all-reduced gradient)
  *   15 clip_scale    (double) of the f32 scale the update applies; 1.0 when it does not clip
  *   16 lr            (double) of the f32 learning rate the update uses, anneal included
- * gamma and clip_reward are those of the last returns launch of the net
+ * gamma, clip_reward and the GAE lambda are those of the last returns launch of the net
  * (arl_learn, arl_learn_part(LEARN_RETURNS), the returns fused into the
  * bootstrap step, arl_run_window); 0.99 and 1 before any.  With clip <= 0 the
  * update still launches the squared-norm kernel while the feature is on, so
@@ -510,6 +538,16 @@ int arl_returns_lossgrad(const float* rewards, const uint8_t* dones, const float
                          double gamma, double beta, double pi_loss_coef, double v_loss_coef,
                          int keep_loss_scale_same, int clip_reward, float* dlogits, float* dv, float* loss,
                          void* stream);
+
+/* arl_returns_lossgrad with the GAE(lambda) advantage in the policy term
+ * (arl_net_set_gae has the definition); lambda == 1 launches
+ * arl_returns_lossgrad's kernel with its arguments.  lambda outside [0, 1] or
+ * not finite: ARL_EINVAL.  Addition to ABI 4. */
+int arl_returns_lossgrad_gae(const float* rewards, const uint8_t* dones, const float* v, const float* probs,
+                             const float* log_probs, const int32_t* actions, int t_max, int64_t n, int n_actions,
+                             double gamma, double lambda, double beta, double pi_loss_coef, double v_loss_coef,
+                             int keep_loss_scale_same, int clip_reward, float* dlogits, float* dv, float* loss,
+                             void* stream);
 
 /* ------------------------------------------------------------------ measurement */
 

@@ -1,0 +1,428 @@
+"""GPU: GAE(lambda) advantages in the device learner (arl_net_set_gae, arl_returns_lossgrad_gae,
+A3C(gae_lambda=)) against the NumPy float64 replay of gae_replay.py.  GAE has no reference
+counterpart: the replay is pinned on the CPU by its closed forms and autograd (test_gae.py).
+
+Tolerances: 1e-5 norm-scaled (and componentwise for the gradients), as test_gpu_parity /
+test_gpu_configs hold the same quantities to on the n-step path; everything the feature must leave
+alone (dv, v_loss, the lambda = 1 path, fused against unfused, a graph against eager) bit for bit."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import oracle as O
+from conftest import close_normscaled, grads_match
+from gae_replay import gae_adv, patched, replay_adv_sums, returns_and_lossgrad_gae, window_case
+from sim import OracleEnvView, OracleStatesView, make_pools, make_state_pools
+from window_replay import NAMES, case_pools, replay, same_bits
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-5
+GAMMA, BETA, VCOEF = 0.99, 0.01, 0.5
+F = {k: i for i, k in enumerate(NAMES)}
+HYPER = dict(resize_mode=0, gamma=GAMMA, beta=BETA, v_loss_coef=VCOEF, clip_reward=True, lr0=7e-4, total_steps=10_000,
+             alpha=0.99, eps=0.1, clip=40.0)
+
+
+def dev(x, gpu):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(gpu)
+
+
+def bits_equal(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+# ------------------------------------------------------------------ the granular entry
+def granular(c, T, n, A, gpu, lam=None, pcoef=1.0, keep=False, clip_reward=True):
+    """arl_returns_lossgrad (lam None) or arl_returns_lossgrad_gae on the arrays of a window_case."""
+    from asyncrl_amd._lib import lib
+    t = {k: dev(v, gpu) for k, v in c.items()}
+    dl = torch.full((T, n, A), float("nan"), device=gpu)
+    dv = torch.full((T, n), float("nan"), device=gpu)
+    loss = torch.full((n, 2), float("nan"), device=gpu)
+    ptr = lambda x: ctypes.c_void_p(x.data_ptr())                                            # noqa: E731
+    head = [ptr(t[k]) for k in ("rewards", "dones", "v", "probs", "logp", "actions")] + [T, n, A, GAMMA]
+    tail = [BETA, pcoef, VCOEF, int(keep), int(clip_reward), ptr(dl), ptr(dv), ptr(loss), None]
+    if lam is None:
+        rc = lib.arl_returns_lossgrad(*head, *tail)
+    else:
+        rc = lib.arl_returns_lossgrad_gae(*head, float(lam), *tail)
+    assert rc == 0, lib.arl_last_error()
+    torch.cuda.synchronize()
+    return dl.cpu().numpy(), dv.cpu().numpy(), loss.cpu().numpy()
+
+
+def replay_case(c, T, lam, pcoef=1.0, keep=False, clip_reward=True):
+    d = c["dones"]
+    return returns_and_lossgrad_gae(c["rewards"], d & 1, c["v"][:T], c["v"][T], c["probs"][:T], c["logp"][:T],
+                                    c["actions"][:T], gamma=GAMMA, beta=BETA, v_loss_coef=VCOEF, clip_reward=clip_reward,
+                                    pi_loss_coef=pcoef, keep_loss_scale_same=keep, t_max=T, valid=(d & 2) == 0, lam=lam,
+                                    per_env=True)
+
+
+# (T, n, A): 51 envs per block so the second block holds one env; T > 8, the memory-loop path; the longest
+# window and the widest action set; the smallest.  The first case carries a truncated env (dones bit 1 on its
+# tail, closed by a terminal) and the loss options.
+GRANULAR = [(5, 52, 4, dict(truncate=True, pcoef=0.5, keep=True)), (9, 29, 6, dict(clip_reward=False)),
+            (64, 5, 18, {}), (1, 3, 4, {})]
+_NSTEP = {}
+
+
+def nstep(i, gpu):
+    """The lambda = 1 entry's outputs of case i, computed once and shared (read only)."""
+    if i not in _NSTEP:
+        T, n, A, o = GRANULAR[i]
+        o = dict(o)
+        c = window_case(40 + i, T, n, A, truncate=o.pop("truncate", False))
+        _NSTEP[i] = (c, o, granular(c, T, n, A, gpu, None, **o))
+    return _NSTEP[i]
+
+
+@pytest.mark.parametrize("lam", [0.0, 0.5, 0.95])
+@pytest.mark.parametrize("i", range(len(GRANULAR)))
+def test_granular_entry_matches_the_replay(gpu, i, lam):
+    T, n, A, _ = GRANULAR[i]
+    c, o, (dl1, dv1, loss1) = nstep(i, gpu)
+    dl, dv, loss = granular(c, T, n, A, gpu, lam, **o)
+    assert bits_equal(dv, dv1) and bits_equal(loss[:, 1], loss1[:, 1])          # the value side is untouched
+    _, adv, dl_w, dv_w, pi_w, v_w = replay_case(c, T, lam, **o)
+    for name, got, want in (("dlogits", dl, dl_w), ("dv", dv, dv_w), ("pi_loss", loss[:, 0], pi_w),
+                            ("v_loss", loss[:, 1], v_w)):
+        ok, err = close_normscaled(got, want, RTOL)
+        print(f"case {i} lambda {lam} {name}: err {err:.3e} of the scale")
+        assert ok, (name, err)
+    if T > 1:
+        assert not bits_equal(dl, dl1)                                          # and the policy side is not
+    live = (c["dones"] & 2) == 0
+    assert (dl[~live] == 0).all() and (dv[~live] == 0).all() and (~live).sum() == (2 if i == 0 else 0)
+
+
+@pytest.mark.parametrize("i", range(len(GRANULAR)))
+def test_lambda_one_through_the_gae_entry_is_the_n_step_kernel(gpu, i):
+    T, n, A, _ = GRANULAR[i]
+    c, o, want = nstep(i, gpu)
+    got = granular(c, T, n, A, gpu, 1.0, **o)
+    for g, w in zip(got, want):
+        assert bits_equal(g, w) and np.isfinite(g).all()
+
+
+# ------------------------------------------------------------------ whole windows
+def dev_acts(net, T, N):
+    a1 = net.buffer("a1", torch.float32, (T + 1, N, 16, 20, 20))[:T].cpu().numpy()
+    a2 = net.buffer("a2", torch.float32, (T + 1, N, 32, 9, 9))[:T].cpu().numpy()
+    h = net.buffer("hfc", torch.float32, (T + 1, N, 256))[:T].cpu().numpy()
+    return a1.reshape(T * N, 16, 20, 20), a2.reshape(T * N, 32, 9, 9), h.reshape(T * N, 256)
+
+
+def check_learner_outputs(net, aux, acts, r, d, T, N, A, lam):
+    """dlogits, dv and the per-env losses the returns kernel left against the replay on the oracle's forward."""
+    lg = aux["logits"].reshape(T * N, A)
+    _, _, dl_w, dv_w, pi_w, v_w = returns_and_lossgrad_gae(
+        r, d, aux["v"], aux["vboot"], O.softmax(lg).reshape(T, N, A), O.log_softmax(lg).reshape(T, N, A), acts,
+        gamma=GAMMA, beta=BETA, v_loss_coef=VCOEF, lam=lam, per_env=True)
+    assert bits_equal(dl_w, aux["dlogits"]) and bits_equal(dv_w, aux["dv"])     # what the patched oracle used
+    loss = net.buffer("loss", torch.float32, (N, 2)).cpu().numpy()
+    for name, got, want in (("dlogits", net.buffer("dlogits", torch.float32, (T, N, A)).cpu().numpy(), dl_w),
+                            ("dv", net.buffer("dv", torch.float32, (T, N)).cpu().numpy(), dv_w),
+                            ("pi_loss", loss[:, 0], pi_w), ("v_loss", loss[:, 1], v_w)):
+        ok, err = close_normscaled(got, want, RTOL)
+        print(f"{name}: err {err:.3e} of the scale")
+        assert ok, (name, err)
+
+
+@pytest.mark.parametrize("N,T,A,nature", [(33, 5, 4, False), (33, 9, 6, False), (5, 5, 18, False), (32, 5, 4, True)])
+def test_ff_window_matches_the_replay(gpu, N, T, A, nature):
+    """One window at lambda 0.95.  NIPS head: f32 states (no phi on the host side); the step-by-step window runs the
+    returns inside the bootstrap policy launch (policy_fc_returns_kernel; T = 9: its 32-row form).  The Nature
+    head, on frame pairs, has its own learner (returns_kernel)."""
+    from asyncrl_amd import A3C, A3CFF, A3CFFNature, GradientClipping, RMSpropAsync
+    lam = 0.95
+    rng = np.random.default_rng(N + T + A)
+    P = T + 1
+    if nature:
+        states, rewards, dones = make_pools(rng, P, N, "palette", p_done=0.2)
+        model = A3CFFNature(A, n_envs=N, t_max=T, seed=99, init_seed=3, frames="pairs")
+    else:
+        states, rewards, dones = make_state_pools(rng, P, N, p_done=0.2)
+        model = A3CFF(A, n_envs=N, t_max=T, seed=99, init_seed=3, frames="states")
+    opt = RMSpropAsync(lr=7e-4, eps=1e-1, alpha=0.99).setup(model)
+    opt.add_hook(GradientClipping(40))
+    agent = A3C(model, opt, T, GAMMA, beta=BETA, gae_lambda=lam)
+    net = model.net
+    params = net.state_dict()
+    agent.run_window(dev(states, gpu), dev(rewards, gpu), dev(dones, gpu), P, first=True, split_update=True)
+    torch.cuda.synchronize()
+    view = OracleEnvView(states, dones) if nature else OracleStatesView(states, dones)
+    x, boot = view.states_f32(0, T)
+    r, d = view.window_rd(rewards, 0, T)
+    acts = net.buffer("actions", torch.int32, (T + 1, N))[:T].cpu().numpy()
+    arch = O.ARCH_FF_NATURE if nature else O.ARCH_FF
+    with patched(lam):
+        g, aux = O.ff_window_grads(params, x, acts, r, d, boot, gamma=GAMMA, beta=BETA, v_loss_coef=VCOEF, arch=arch,
+                                   dev_acts=None if nature else dev_acts(net, T, N))
+    assert d.any() and not bits_equal(aux["adv"], (aux["R"] - aux["v"]).astype(np.float32))
+    check_learner_outputs(net, aux, acts, r, d, T, N, A, lam)
+    grads_match(net.state_dict(net.grads), g, aux["grad_mag"], RTOL)
+    agent.finish_window()
+    torch.cuda.synchronize()
+    assert torch.isfinite(net.params).all()
+
+
+def test_lstm_window_matches_the_replay(gpu):
+    from asyncrl_amd import A3C, A3CLSTM, GradientClipping, RMSpropAsync
+    N, T, A, lam = 32, 5, 6, 0.95
+    rng = np.random.default_rng(31)
+    P = T + 1
+    states, rewards, dones = make_state_pools(rng, P, N, p_done=0.2)
+    model = A3CLSTM(A, n_envs=N, t_max=T, seed=5, init_seed=31, frames="states")
+    opt = RMSpropAsync(lr=7e-4, eps=1e-1, alpha=0.99).setup(model)
+    opt.add_hook(GradientClipping(40))
+    agent = A3C(model, opt, T, GAMMA, beta=BETA, gae_lambda=lam)
+    net = model.net
+    params = net.state_dict()
+    agent.run_window(dev(states, gpu), dev(rewards, gpu), dev(dones, gpu), P, first=True, split_update=True)
+    torch.cuda.synchronize()
+    view = OracleStatesView(states, dones)
+    x, boot = view.states_f32(0, T)
+    r, d = view.window_rd(rewards, 0, T)
+    dprev = np.concatenate([np.ones((1, N), np.uint8), d[:-1]], 0)
+    acts = net.buffer("actions", torch.int32, (T + 1, N))[:T].cpu().numpy()
+    st = O.LSTMState(h=np.zeros((N, 256), np.float32), c=np.zeros((N, 256), np.float32), has=np.zeros(N, bool))
+    with patched(lam):
+        g, aux = O.lstm_window(params, x, acts, r, dprev, d, boot, st, gamma=GAMMA, beta=BETA, v_loss_coef=VCOEF,
+                               dev_acts=dev_acts(net, T, N))
+    check_learner_outputs(net, aux, acts, r, d, T, N, A, lam)
+    grads_match(net.state_dict(net.grads), g, aux["grad_mag"], RTOL)
+    agent.finish_window()
+
+
+def test_fused_bootstrap_launch_equals_the_separate_one(gpu, tmp_path):
+    """The window as one C call (the returns in policy_fc_returns_kernel) in this process against the window issued
+    step by step with the separate returns_heads_kernel launch in a child, three shapes, lambda 0.95, bit for bit."""
+    import gae_worker
+    from asyncrl_amd import a3c
+    assert a3c.WINDOW_C and a3c.FUSE_RETURNS
+    here = os.path.dirname(os.path.abspath(__file__))
+    f0, f1 = str(tmp_path / "fused.npz"), str(tmp_path / "separate.npz")
+    gae_worker.main(f0, 0.95)
+    subprocess.run([sys.executable, os.path.join(here, "gae_worker.py"), f1, "0.95"],
+                   env=dict(os.environ, ARL_WINDOW_C="0", ARL_FUSE_RETURNS="0"), check=True, timeout=240)
+    a, b = np.load(f0), np.load(f1)
+    assert sorted(a.files) == sorted(b.files) and len(a.files) == 3 * 7
+    for k in a.files:
+        assert bits_equal(a[k], b[k]), k
+        assert np.isfinite(a[k]).all() and (np.abs(a[k]).max() > 0 or k.endswith("dfc")), k
+
+
+def test_env_groups_equal_one_chain(gpu):
+    """Two env groups (the separate returns launch after the chains join) against one chain (the fused launch)."""
+    from asyncrl_amd import A3C, A3CFF, GradientClipping, RMSpropAsync
+    N, T, A, P = 64, 5, 4, 6
+    pairs, rewards, dones = make_pools(np.random.default_rng(8), P, N, "uniform", p_done=0.2)
+    pools = (dev(pairs, gpu), dev(rewards, gpu), dev(dones, gpu))
+    outs = []
+    for groups in (1, 2):
+        model = A3CFF(A, n_envs=N, t_max=T, seed=9, init_seed=10, frames="pairs", device=gpu)
+        opt = RMSpropAsync(lr=7e-4, eps=0.1, alpha=0.99).setup(model)
+        opt.add_hook(GradientClipping(40))
+        agent = A3C(model, opt, T, GAMMA, gae_lambda=0.5)
+        agent.run_window(*pools, P, first=True, env_groups=groups, split_update=True)
+        torch.cuda.synchronize()
+        outs.append([model.net.buffer(k, torch.float32).cpu().numpy() for k in ("dlogits", "dv", "loss")]
+                    + [model.net.grads.cpu().numpy()])
+    for x, y in zip(*outs):
+        assert bits_equal(x, y) and np.abs(x).max() > 0
+
+
+# ------------------------------------------------------------------ the one-env drop-in
+def test_dropin_act_with_a_truncated_window(gpu):
+    """A3C(gae_lambda=0.95).act on a one-env model: an episode that ends 3 steps into a window (the truncated
+    update), then a full window.  After each update the parameters equal oracle clip + RMSProp on the replay's
+    gradient, 1e-5 norm-scaled as test_gpu_dropin holds the reference's trajectories."""
+    from asyncrl_amd import A3C, A3CFF, GradientClipping, RMSpropAsync, dqn_phi
+    T, A, lam = 5, 4, 0.95
+    model = A3CFF(A, n_envs=1, t_max=T, seed=4, init_seed=2, device=gpu)
+    opt = RMSpropAsync(lr=7e-4, eps=1e-1, alpha=0.99).setup(model)
+    opt.add_hook(GradientClipping(40.0))
+    agent = A3C(model, opt, T, GAMMA, beta=BETA, phi=dqn_phi, gae_lambda=lam)
+    net = model.net
+    rng = np.random.default_rng(9)
+    stacks = rng.integers(0, 256, (10, 4, 84, 84), dtype=np.uint8)
+    rewards = [0.0, 2.0, -0.3, 0.7, 0.0, 0.5, -1.5, 0.25, 0.0, 1.0]       # reward[k]: of the transition into call k
+    terminal = [False, False, False, True] + [False] * 6
+    updates = {3: (0, 3), 9: (4, 5)}                                      # call -> (first call of its window, steps)
+    acts, n_updates = {}, 0
+    params, ms = net.state_dict(), net.state_dict(net.ms)
+    for k in range(10):
+        a = agent.act(list(stacks[k]), rewards[k], terminal[k])
+        assert (a is None) == terminal[k]
+        if k in updates:
+            torch.cuda.synchronize()
+            k0, L = updates[k]
+            x = O.PHI_LUT[stacks[k0:k0 + L]][:, None]                    # (L, 1, 4, 84, 84)
+            boot = O.PHI_LUT[stacks[k0 + L]][None]                       # unused after a terminal (R = 0)
+            r = np.array(rewards[k0 + 1:k0 + L + 1], np.float32)[:, None]
+            d = np.array(terminal[k0 + 1:k0 + L + 1], np.uint8)[:, None]
+            aw = np.array([acts[j] for j in range(k0, k0 + L)], np.int32)[:, None]
+            with patched(lam):
+                g, aux = O.ff_window_grads(params, x, aw, r, d, boot, gamma=GAMMA, beta=BETA, v_loss_coef=VCOEF)
+            names = list(g)
+            gl, _ = O.clip_grads([g[n] for n in names], 40.0, exact_norm=True)
+            new, new_ms = net.state_dict(), net.state_dict(net.ms)
+            for n, gn in zip(names, gl):
+                p1, _ = O.rmsprop_update(params[n], ms[n], gn, 7e-4)
+                ok, err = close_normscaled(new[n], p1, RTOL)
+                assert ok, (k, n, "param", err)
+                ok, err = close_normscaled(new[n] - params[n], p1 - params[n], 1e-3)   # and it did move the right way
+                assert ok, (k, n, "delta", err)
+            loss = net.buffer("loss", torch.float32, (1, 2)).cpu().numpy()[0]
+            assert abs(loss[0] - aux["pi_loss"]) <= RTOL * max(abs(aux["pi_loss"]), 1e-3), (k, loss, aux["pi_loss"])
+            assert abs(loss[1] - aux["v_loss"]) <= RTOL * max(abs(aux["v_loss"]), 1e-3), (k, loss, aux["v_loss"])
+            params, ms = new, new_ms
+            n_updates += 1
+        if a is not None:
+            acts[k] = a
+    assert n_updates == 2
+
+
+# ------------------------------------------------------------------ window statistics, graph, default
+_PAIRS = {}
+
+
+def pair_pool(P, n, gpu):
+    if (P, n) not in _PAIRS:
+        g = torch.Generator(device="cpu").manual_seed(P * 1000 + n)
+        _PAIRS[P, n] = torch.randint(0, 256, (P, n, 2, 210, 160, 3), dtype=torch.uint8, generator=g).to(gpu)
+    return _PAIRS[P, n]
+
+
+def make_net(A, n, T, gpu, lam=None, stats=False, seed=3, stack=False):
+    from asyncrl_amd import DeviceNet, init_like_torch
+    from asyncrl_amd._lib import ARCH_FF, ARCH_STACK
+    arch = ARCH_FF | (ARCH_STACK if stack else 0)
+    net = DeviceNet(arch, A, n, T, seed=seed, device=gpu)
+    net.load_params(init_like_torch(arch, A, np.random.default_rng(seed)))
+    net.reset()
+    if stats:
+        net.set_window_stats(True)
+    if lam is not None:
+        net.set_gae(lam)
+    return net
+
+
+def snapshot(net):
+    torch.cuda.synchronize()
+    T, n, A, f32 = net.t_max, net.n_envs, net.n_actions, torch.float32
+    b = lambda name, dt, shape: net.buffer(name, dt, shape).cpu().numpy()   # noqa: E731
+    return dict(rewards=b("rewards", f32, (T, n)), dones=b("dones", torch.uint8, (T, n)), v=b("v", f32, (T + 1, n)),
+                entropy=b("entropy", f32, (T + 1, n)), loss=b("loss", f32, (n, 2)),
+                dlogits=b("dlogits", f32, (T, n, A)), dv=b("dv", f32, (T, n)), grads=net.grads.cpu().numpy())
+
+
+def manual_window(net, pools, P, first, truncate=None):
+    T = net.t_max
+    for t in range(0 if first else 1, T + 1):
+        net.observe(t, *pools, P, force_reset=(first and t == 0))
+        net.act(t, mode=1 if t < T else 0)
+    if truncate is not None:
+        net.truncate_window(truncate)
+    net.learn(gamma=GAMMA, beta=BETA, v_loss_coef=VCOEF)
+    net.optimize(advance=True)
+
+
+@pytest.mark.parametrize("n,T,truncate,c_call", [(40, 5, None, True), (300, 2, None, False), (5, 9, 7, False)])
+def test_window_statistics_record_the_gae_advantage(gpu, n, T, truncate, c_call):
+    """lambda 0.95 with the record on: fields 12, 13 equal the float64 replay of the record's summation order over
+    the replay's advantage bit for bit; so do fields 2..11 over the window's own buffers (window_replay.replay).
+    Against the lambda = 1 record of the same window, fields 0..4 and 6..11 are equal bit for bit.  Field 5,
+    pi_loss, is the one field of 0..11 that must differ: the policy loss is computed with the GAE advantage.
+    40 envs through arl_run_window (the fused launch), 300 envs (threads own two envs; whole stacks as the
+    observation, 34 MB instead of 240 MB of frame pairs), and t_max 9 truncated to 7 (the record's loop over
+    memory)."""
+    A, P = 4, T + 2
+    rewards, dones = case_pools(1, P, n)
+    if n > 256:
+        g = torch.Generator(device="cpu").manual_seed(11)
+        frames = torch.randint(0, 256, (P, n, 4, 84, 84), dtype=torch.uint8, generator=g).to(gpu)
+    else:
+        frames = pair_pool(P, n, gpu)
+    pools = (frames, dev(rewards, gpu), dev(dones, gpu))
+    recs = []
+    for lam in (0.95, None):
+        net = make_net(A, n, T, gpu, lam, stats=True, stack=n > 256)
+        if c_call:
+            net.set_norm_fold(True)
+            net.run_window(*pools, P, first=True, n_total=n, **HYPER)
+        else:
+            manual_window(net, pools, P, True, truncate)
+        s = snapshot(net)
+        rec = net.window_stats_raw()[0]
+        want = replay(s["rewards"], s["dones"], s["v"], s["entropy"], s["loss"], GAMMA, True)
+        if lam is not None:
+            adv = gae_adv(s["rewards"], s["dones"], s["v"][:T], s["v"][T], GAMMA, lam, True)
+            want[10], want[11] = replay_adv_sums(adv, s["dones"])
+        bad = [(NAMES[2 + i], rec[2 + i], want[i]) for i in range(12)
+               if not same_bits(np.float64(rec[2 + i]), np.float64(want[i]))]
+        assert not bad, (lam, bad)
+        recs.append(rec)
+    gae, one = recs
+    same = [i for i in range(12) if i != F["pi_loss"]]
+    assert all(same_bits(np.float64(gae[i]), np.float64(one[i])) for i in same), (gae, one)
+    assert gae[F["pi_loss"]] != one[F["pi_loss"]] and gae[F["adv_sum"]] != one[F["adv_sum"]]
+    assert gae[F["samples"]] == (T if truncate is None else truncate) * n
+
+
+def test_captured_window_keeps_its_lambda(gpu):
+    """A run_window captured at lambda 0.5 and replayed twice against two eager windows: the same parameters bit
+    for bit -- also after the handle's lambda changed: gl is an argument of the captured launch."""
+    n, T, A, P = 8, 5, 4, 7
+    rewards, dones = case_pools(5, P, n)
+    pools = (pair_pool(P, n, gpu), dev(rewards, gpu), dev(dones, gpu))
+    hyper = dict(HYPER, n_total=n)
+    eager = make_net(A, n, T, gpu, 0.5)
+    for w in range(3):
+        eager.run_window(*pools, P, first=(w == 0), **hyper)
+    net = make_net(A, n, T, gpu, 0.5)
+    net.run_window(*pools, P, first=True, **hyper)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        net.run_window(*pools, P, first=False, **hyper)
+    net.set_gae(1.0)
+    g.replay()
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(net.params.view(torch.int32), eager.params.view(torch.int32))
+    assert torch.equal(net.ms.view(torch.int32), eager.ms.view(torch.int32))
+    plain = make_net(A, n, T, gpu, None)
+    for w in range(3):
+        plain.run_window(*pools, P, first=(w == 0), **hyper)
+    torch.cuda.synchronize()
+    assert not torch.equal(plain.params.view(torch.int32), eager.params.view(torch.int32))
+
+
+def test_default_is_untouched(gpu):
+    """A net that never calls set_gae and one that calls set_gae(1.0): dlogits, dv, the losses, the gradient, the
+    updated parameters and the window-statistics record, bit for bit."""
+    n, T, A, P = 33, 5, 4, 7
+    rewards, dones = case_pools(4, P, n)
+    pools = (pair_pool(P, n, gpu), dev(rewards, gpu), dev(dones, gpu))
+    outs = []
+    for lam in (None, 1.0):
+        net = make_net(A, n, T, gpu, lam, stats=True)
+        manual_window(net, pools, P, True)
+        s = snapshot(net)
+        net.set_norm_fold(True)
+        net.run_window(*pools, P, first=False, n_total=n, **HYPER)
+        s2 = snapshot(net)
+        outs.append([s[k] for k in ("dlogits", "dv", "loss", "grads")] + [s2[k] for k in ("dlogits", "loss", "grads")]
+                    + [net.window_stats_raw(last=2), net.params.cpu().numpy()])
+    for x, y in zip(*outs):
+        assert bits_equal(x, y) and np.abs(x).max() > 0
