@@ -64,6 +64,10 @@ SIGNATURES = {
     "arl_net_set_loss": (c_int, [c_void_p, c_double, c_int]),
     "arl_net_set_weight_decay": (c_int, [c_void_p, c_double]),
     "arl_net_set_gae": (c_int, [c_void_p, c_double]),
+    "arl_net_set_adam": (c_int, [c_void_p, c_void_p, c_double, c_double]),
+    "arl_net_set_adam_t": (c_int, [c_void_p, c_i64, c_void_p]),
+    "arl_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_double, c_double, c_double, c_double, c_i64,
+                         c_double, c_void_p, c_double, c_void_p]),
     "arl_net_set_norm_fold": (c_int, [c_void_p, c_int]),
     "arl_net_set_returns_fusion": (c_int, [c_void_p, c_int, c_double, c_double, c_double, c_int]),
     "arl_reset_state": (c_int, [c_void_p, c_i64, c_i64, c_void_p]),
@@ -128,6 +132,7 @@ ACT_AFTER_CONV = 8
 ENV_GROUP_ALIGN = 32   # arl_observe_envs / arl_act_envs: e0 % ENV_GROUP_ALIGN == 0
 LEARN_RETURNS, LEARN_TRUNK, LEARN_CONV = range(3)
 POOL_FRAMES, POOL_REWARDS, POOL_DONES = range(3)   # arl_net_set_pool kinds
+CTL_ADAM_T = 3         # ARL_CTL_ADAM_T: the control block's count of Adam updates made (buffer "ctl", int64[16])
 EPISODE_LOG = 8        # ARL_EPISODE_LOG: episodes per env the device-side episode log keeps
 # the 8 doubles of arl_episode_stats, in order
 EPISODE_STAT_FIELDS = ("episodes", "return_sum", "return_sumsq", "return_min", "return_max", "length_sum", "steps",

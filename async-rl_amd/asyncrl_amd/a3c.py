@@ -136,6 +136,9 @@ class A3CModel:
                         device=old.device)
         net.copy_params_from(old)
         net.ms.copy_(old.ms)
+        if old.adam_betas is not None:      # an Adam set this model up: its first moment moves too
+            net.set_adam(*old.adam_betas)
+            net.adam_m.copy_(old.adam_m)
         self.net, self.frames = net, frames
 
     def pi_and_v(self, state, keep_same_state: bool = False, deterministic: bool = False):

@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 import torch
 
-from ._lib import (ARCH_FF, ARCH_FF_NATURE, ARCH_LSTM, ARCH_RGB, ARCH_STACK, ARCH_STATES, ENV_GROUP_ALIGN,
+from ._lib import (ARCH_FF, ARCH_FF_NATURE, ARCH_LSTM, ARCH_RGB, ARCH_STACK, ARCH_STATES, CTL_ADAM_T, ENV_GROUP_ALIGN,
                    EPISODE_LOG, EPISODE_STAT_FIELDS, FWD_KEEP_STATE, POOL_DONES, POOL_FRAMES, POOL_REWARDS,
                    RESIZE_SCALAR, STAGE_HOST, STAGE_NAMES, WINDOW_LOG, WINDOW_STAT_FIELDS, WINDOW_STAT_NAMES, check,
                    lib, ptr, stream_handle)
@@ -337,6 +337,35 @@ class DeviceNet:
         and arguments of a net that never called this.  A captured window keeps
         the lambda it was captured with."""
         check(lib.arl_net_set_gae(self._h, float(lambda_)), "arl_net_set_gae")
+
+    # ------------------------------------------------------------ Adam
+    adam_m = None     # Adam's first moment (flat f32, the params' layout), allocated by the first set_adam
+    adam_betas = None   # (beta1, beta2) while Adam is the net's optimizer, else None
+
+    def set_adam(self, beta1: float | None = 0.9, beta2: float = 0.999):
+        """Make Adam the optimizer of every update of this net (arl_net_set_adam):
+        the first moment in `adam_m` (allocated once, zeroed), the second in
+        `ms`, the update count on the device (adam_t).  beta1=None switches
+        back to RMSpropAsync.  A captured window keeps the optimizer it was
+        captured with."""
+        if beta1 is None:
+            check(lib.arl_net_set_adam(self._h, None, 0.0, 0.0), "arl_net_set_adam")
+            self.adam_betas = None
+            return
+        if self.adam_m is None:
+            self.adam_m = torch.zeros(self.param_floats, dtype=torch.float32, device=self.device)
+        check(lib.arl_net_set_adam(self._h, ptr(self.adam_m), float(beta1), float(beta2)), "arl_net_set_adam")
+        self.adam_betas = (float(beta1), float(beta2))
+
+    def set_adam_t(self, t: int, stream=None):
+        """Write the device-side count of Adam updates made (arl_net_set_adam_t;
+        checkpoint resume).  Asynchronous on `stream`."""
+        check(lib.arl_net_set_adam_t(self._h, int(t), stream_handle(stream)), "arl_net_set_adam_t")
+
+    def adam_t(self) -> int:
+        """The device-side count of Adam updates made (the host waits for it): a
+        graph replay moves it, not the optimizer object's t."""
+        return int(self.buffer("ctl", torch.int64)[CTL_ADAM_T].item())
 
     # ------------------------------------------------------------ episode statistics
     episode_stats_on = False

@@ -56,8 +56,10 @@ class RMSpropAsync:
 
     def setup(self, model):
         """Chainer Optimizer.setup: bind the model whose flat params/grads and
-        `ms` state (rmsprop_async.py:19-21, zero-initialised) are updated."""
+        `ms` state (rmsprop_async.py:19-21, zero-initialised) are updated.  A net
+        that an Adam had set up goes back to the RMSProp kernel."""
         self.target = model
+        model.net.set_adam(None)
         return self
 
     def add_hook(self, hook):

@@ -8,7 +8,9 @@ File layout = Chainer 1.8.1's HDF5Serializer on these objects:
               tests/test_checkpoint.py);
   optimizer:  scalars "t" and "epoch", then every parameter's state under
               its path, "0/0/W/ms", ... (Optimizer.serialize restated; no
-              reference .opt file exists to pin it).
+              reference .opt file exists to pin it); an Adam's states are
+              "0/0/W/m", "0/0/W/v", ... and its "t" is the device's update
+              count (DeviceNet.adam_t), written back on load.
 Reading accepts the chunked/deflated files h5py writes; writing produces
 contiguous datasets (hdf5.py).  Host-side, off the hot path."""
 from __future__ import annotations
@@ -23,13 +25,29 @@ def _is_optimizer(obj) -> bool:
     return hasattr(obj, "target") and hasattr(obj, "hooks")
 
 
+def _is_adam(obj) -> bool:
+    return hasattr(obj, "beta1") and hasattr(obj, "beta2")
+
+
+def _states(obj, net):
+    """(state name, flat device tensor) of the optimizer's per-parameter state:
+    RMSpropAsync's ms, or Adam's m and v (v lives in the net's ms buffer)."""
+    if _is_adam(obj):
+        if net.adam_m is None:
+            net.set_adam(obj.beta1, obj.beta2)
+        return (("m", net.adam_m), ("v", net.ms))
+    return (("ms", net.ms),)
+
+
 def state_arrays(obj) -> dict:
     if _is_optimizer(obj):
         net = obj.target.net
-        out = {"t": np.array(int(getattr(obj, "t", 0)), np.int64), "epoch": np.array(int(getattr(obj, "epoch", 0)),
-                                                                                       np.int64)}
-        for name, a in net.state_dict(net.ms).items():
-            out[name + "/ms"] = a
+        # Adam's update count is the device's: a graph replay moves it, not the host object's t
+        t = net.adam_t() if _is_adam(obj) else int(getattr(obj, "t", 0))
+        out = {"t": np.array(t, np.int64), "epoch": np.array(int(getattr(obj, "epoch", 0)), np.int64)}
+        for state, flat in _states(obj, net):
+            for name, a in net.state_dict(flat).items():
+                out[name + "/" + state] = a
         return out
     return obj.net.state_dict()
 
@@ -48,11 +66,14 @@ def load_hdf5(filename, obj) -> None:
         net = obj.target.net
         obj.t = int(data["t"]) if "t" in data else 0
         obj.epoch = int(data["epoch"]) if "epoch" in data else 0
-        for name, (_, shape) in net.layout.items():
-            key = name + "/ms"
-            if key not in data:
-                raise KeyError("%s: no dataset %s" % (filename, key))
-            net.view(net.ms, name).copy_(torch.from_numpy(np.asarray(data[key], np.float32).reshape(shape)))
+        for state, flat in _states(obj, net):
+            for name, (_, shape) in net.layout.items():
+                key = name + "/" + state
+                if key not in data:
+                    raise KeyError("%s: no dataset %s" % (filename, key))
+                net.view(flat, name).copy_(torch.from_numpy(np.asarray(data[key], np.float32).reshape(shape)))
+        if _is_adam(obj):
+            net.set_adam_t(obj.t)
         return
     net = obj.net
     missing = [n for n in net.layout if n not in data]

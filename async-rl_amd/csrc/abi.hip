@@ -418,6 +418,29 @@ int arl_net_set_weight_decay(arl_net* h, double rate) {
   return ARL_OK;
 }
 
+static_assert(arl::CTL_ADAM_T == ARL_CTL_ADAM_T, "control block layout");
+static bool adam_beta_ok(double b) { return b >= 0.0 && b < 1.0; }   // (nan fails both)
+
+int arl_net_set_adam(arl_net* h, float* m, double beta1, double beta2) {
+  if (!h) return fail(ARL_EINVAL, "null net");
+  if (!m) {   // back to RMSpropAsync
+    h->net.adam_m = nullptr;
+    return ARL_OK;
+  }
+  if (!aligned(m, 16)) return fail(ARL_EINVAL, "set_adam: m must be 16-byte aligned");
+  if (!adam_beta_ok(beta1) || !adam_beta_ok(beta2)) return fail(ARL_EINVAL, "set_adam: beta1 and beta2 must be in [0, 1)");
+  h->net.adam_m = m;
+  h->net.adam_beta1 = beta1;
+  h->net.adam_beta2 = beta2;
+  return ARL_OK;
+}
+
+int arl_net_set_adam_t(arl_net* h, int64_t t, void* s) {
+  NEED_BOUND(h);
+  if (t < 0) return fail(ARL_EINVAL, "set_adam_t: t < 0");
+  return hip_status(arl::launch_ctl_write(h->net.at<int64_t>(h->net.w_ctl), arl::CTL_ADAM_T, t, S(s)), "set_adam_t");
+}
+
 static bool gae_lambda_ok(double lambda) { return lambda >= 0.0 && lambda <= 1.0; }   // (nan fails both)
 
 int arl_net_set_gae(arl_net* h, double lambda) {
@@ -671,6 +694,27 @@ int arl_rmsprop_wd(float* p, float* ms, const float* g, int64_t n, double lr, do
   arl::DecayArgs wd{};
   wd.rate = (float)weight_decay;
   return rmsprop_array(p, ms, g, n, lr, alpha, eps, clip, parts, &wd, s);
+}
+
+int arl_adam(float* p, float* m, float* v, const float* g, int64_t n, double alpha, double beta1, double beta2,
+             double eps, int64_t t, double clip, double* parts, double weight_decay, void* s) {
+  if (n < 0 || (n > 0 && (!p || !m || !v || !g))) return fail(ARL_EINVAL, "adam: null pointer / n < 0");
+  if (!aligned(p, 16) || !aligned(m, 16) || !aligned(v, 16) || !aligned(g, 16))
+    return fail(ARL_EINVAL, "adam: 16-byte alignment");
+  if (t < 1) return fail(ARL_EINVAL, "adam: t must be >= 1 (the number of this update)");
+  if (!adam_beta_ok(beta1) || !adam_beta_ok(beta2)) return fail(ARL_EINVAL, "adam: beta1 and beta2 must be in [0, 1)");
+  if (!decay_rate_ok(weight_decay)) return fail(ARL_EINVAL, "adam: weight_decay must be finite and >= 0");
+  if (clip > 0 && !parts) return fail(ARL_EINVAL, "adam: clip needs norm_partials scratch");
+  arl::DecayArgs wd{};
+  wd.rate = (float)weight_decay;
+  const arl::AdamArgs ad{beta1, beta2, nullptr, t};
+  hipError_t e = hipSuccess;
+  const int blocks = 256;
+  if (clip > 0) e = arl::launch_grad_sqnorm(g, n, parts, blocks, S(s));
+  if (e == hipSuccess)
+    e = arl::launch_adam(p, m, v, g, n, alpha, eps, ad, clip > 0 ? parts : nullptr, blocks, (float)clip, nullptr, 0, 0,
+                         0, S(s), nullptr, &wd);
+  return hip_status(e, "adam");
 }
 
 int arl_policy(const float* hh, int64_t n, const float* Wpi, const float* bpi, const float* Wv, const float* bv,

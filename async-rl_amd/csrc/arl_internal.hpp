@@ -13,7 +13,8 @@ namespace arl {
 // CTL_STEP_SNAP: the step counter as the learner saw it (written at learn start),
 // read by the fused optimizer for the lr anneal so it can advance CTL_STEP itself
 // CTL_ZERO: never written (0 after arl_net_reset); the step base of draws keyed by a host counter
-enum { CTL_STEP = 0, CTL_WINDOW = 1, CTL_STEP_SNAP = 2, CTL_ZERO = 15, CTL_SIZE = 16 };
+// CTL_ADAM_T: Adam updates made so far (adam_tick_kernel counts, adam_kernel reads; optim.hip)
+enum { CTL_STEP = 0, CTL_WINDOW = 1, CTL_STEP_SNAP = 2, CTL_ADAM_T = 3, CTL_ZERO = 15, CTL_SIZE = 16 };
 
 enum Arch { ARCH_FF = 0, ARCH_LSTM = 1, ARCH_FF_NATURE = 2 };
 // arch flag: RGB (Doom) observations, train_a3c_doom.py:25-63 (NIPSDQNHead(n_input_channels=3)
@@ -176,6 +177,10 @@ struct Net {
   // NonbiasWeightDecay of the update: the rate (arl_net_set_weight_decay; 0 = the hook is not installed)
   // and the bias tensors it skips, from the names in `params` (net_init)
   DecayArgs decay{};
+  // arl_net_set_adam: non-null = every update of the net runs adam_kernel (first moment here, the second
+  // in ms, the update count in ctl[CTL_ADAM_T]) instead of rmsprop_kernel
+  float* adam_m = nullptr;
+  double adam_beta1 = 0.9, adam_beta2 = 0.999;
   int64_t eval_draws = 0;  // sampling forward_states calls so far (Philox stream 1 counter)
   // clip norm folded into the learner's conv reduce (arl_net_set_norm_fold; only valid when
   // nothing changes the gradient between arl_learn and the update, e.g. no all-reduce):
@@ -448,6 +453,23 @@ hipError_t launch_rmsprop(float* p, float* ms, const float* g, int64_t n, double
                           const double* norm_sq, int nparts, float clip, const int64_t* ctl,
                           int64_t total_steps, int64_t n_total, int t_max, hipStream_t s,
                           const AdvanceArgs* adv = nullptr, const DecayArgs* wd = nullptr);
+// Adam (Chainer 1.8.1 optimizers.Adam restated in include/asyncrl_hip.h) with launch_rmsprop's hooks and side
+// duties: lr = Adam's alpha (annealed as launch_rmsprop's lr), v = the second moment.  tctl = the control block:
+// a one-thread launch ahead of the update kernel adds 1 to tctl[CTL_ADAM_T], the update number the kernel then
+// reads; with stats_log set (launch_window_stats ran just before) it also makes field 16 of that record the Adam
+// step size.  tctl null: the host's t >= 1 (flat arrays: the f32 step size then comes from the host's libm).
+struct AdamArgs {
+  double beta1, beta2;
+  int64_t* tctl;
+  int64_t t;
+  double* stats_log = nullptr;
+  const int64_t* stats_count = nullptr;
+};
+hipError_t launch_adam(float* p, float* m, float* v, const float* g, int64_t n, double lr, double eps,
+                       const AdamArgs& ad, const double* norm_sq, int nparts, float clip, const int64_t* ctl,
+                       int64_t total_steps, int64_t n_total, int t_max, hipStream_t s,
+                       const AdvanceArgs* adv = nullptr, const DecayArgs* wd = nullptr);
+hipError_t launch_ctl_write(int64_t* ctl, int idx, int64_t value, hipStream_t s);
 hipError_t launch_grad_sqnorm(const float* g, int64_t n, double* partials, int blocks, hipStream_t s);
 // Per-window training statistics (arl_net_set_window_stats; the header's "window statistics"): one record
 // of WINDOW_STAT_FIELDS doubles per update, slot count % WINDOW_LOG of the ring `log`.

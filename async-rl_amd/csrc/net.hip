@@ -715,6 +715,8 @@ hipError_t net_optimize(Net& net, double lr0, int64_t total_steps, int64_t n_tot
   }
   const int nparts = folded ? conv_norm_parts(net.norm_rest_blocks) : net.norm_blocks;
   const int64_t* lr_ctl = total_steps > 0 ? net.at<int64_t>(net.w_ctl) : nullptr;
+  const bool adam = net.adam_m != nullptr;
+  AdamArgs ad{net.adam_beta1, net.adam_beta2, net.at<int64_t>(net.w_ctl), 0};
   if (net.window_stats) {   // one record of the window this update consumes, before anything advances
     const WindowStatsArgs w{net.at<float>(net.w_rewards), net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v),
                             net.at<float>(net.w_ent), net.at<float>(net.w_loss), net.T, net.N, net.win_gamma,
@@ -722,6 +724,8 @@ hipError_t net_optimize(Net& net, double lr0, int64_t total_steps, int64_t n_tot
                             net.at<int64_t>(net.w_win_count)};
     ARL_TRY(launch_window_stats(w, lr0, parts, nparts, clip, lr_ctl, total_steps, n_total, net.T, fused, s,
                                 net.win_lambda));
+    ad.stats_log = net.at<double>(net.w_win_log);   // (Adam: the record's lr becomes its step size, launch_adam)
+    ad.stats_count = net.at<int64_t>(net.w_win_count);
   }
   const bool L = net.arch == ARCH_LSTM;
   // the update rewrites the FC weight's split planes with the new W (all of them, so they are current
@@ -731,8 +735,13 @@ hipError_t net_optimize(Net& net, double lr0, int64_t total_steps, int64_t n_tot
                         L ? net.at<float>(net.w_hbuf) : nullptr, L ? net.at<float>(net.w_cbuf) : nullptr, net.T,
                         net.N};
   if (planes != nullptr) net.planes_gen = net.param_gen;
-  ARL_TRY(launch_rmsprop(net.p, net.ms, net.g, net.param_floats, lr0, alpha, eps, do_clip ? parts : nullptr, nparts,
-                         clip, lr_ctl, total_steps, n_total, net.T, s, &adv, &net.decay));
+  // the net's optimizer (arl_net_set_adam): Adam takes lr0 as its alpha and ms as its second moment
+  if (adam)
+    ARL_TRY(launch_adam(net.p, net.adam_m, net.ms, net.g, net.param_floats, lr0, eps, ad, do_clip ? parts : nullptr,
+                        nparts, clip, lr_ctl, total_steps, n_total, net.T, s, &adv, &net.decay));
+  else
+    ARL_TRY(launch_rmsprop(net.p, net.ms, net.g, net.param_floats, lr0, alpha, eps, do_clip ? parts : nullptr, nparts,
+                           clip, lr_ctl, total_steps, n_total, net.T, s, &adv, &net.decay));
   ARL_TRY(stamp(net, STAGE_RMSPROP, s));
   return advance && !fused ? net_advance(net, s) : hipSuccess;
 }

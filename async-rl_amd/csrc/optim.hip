@@ -29,10 +29,14 @@
 // come as [begin, end) float ranges in the kernel arguments, so the decay moves no extra byte.  The clip
 // norm stays the norm of the gradient before the decay (the reference clips first).  rate == 0 launches
 // rmsprop_kernel<NoDecay>, the decay-free instantiation (g + f32(0 * p) would also turn a -0 gradient into +0).
+//
+// Adam (arl_net_set_adam; an extension, off by default): adam_kernel below takes rmsprop_kernel's place in the
+// update with the same hooks and side duties; 28 bytes per parameter.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <type_traits>
 
 #include "arl_internal.hpp"
@@ -84,13 +88,18 @@ struct RmsConst {   // (AdvanceArgs is declared in arl_internal.hpp)
 // The three pieces below are shared by rmsprop_kernel and window_stats_kernel, so that the recorded
 // learning rate, squared norm and clip scale are bit for bit the ones the update applies.
 
-// the update's learning rate: c.lr, or the anneal when the control block and a step budget are given
-__device__ inline float update_lr(const RmsConst& c) {
-  if (c.ctl == nullptr || c.total <= 0) return c.lr;
+// the anneal in f64 (only with the control block and a step budget): update_lr rounds it to f32, Adam's
+// bias correction goes on in f64 (adam_lr)
+__device__ inline double anneal_f64(const RmsConst& c) {
   const int64_t gt = (c.ctl[c.ctl_idx] + c.t_max) * c.n_total;
   // clamped at 0: the reference stops training once global_t passes the
   // step budget (run_a3c.py:64-68); a replay past it must not ascend
-  return (float)(((double)max(c.total - gt - 1, (int64_t)0) / (double)c.total) * c.lr0);
+  return ((double)max(c.total - gt - 1, (int64_t)0) / (double)c.total) * c.lr0;
+}
+// the update's learning rate: c.lr, or the anneal when the control block and a step budget are given
+__device__ inline float update_lr(const RmsConst& c) {
+  if (c.ctl == nullptr || c.total <= 0) return c.lr;
+  return (float)anneal_f64(c);
 }
 
 // the squared norm: re-reduce the partials [0, nparts) in block order (4 loads a thread in flight);
@@ -218,6 +227,149 @@ rmsprop_kernel(float* __restrict__ p, float* __restrict__ ms, const float* __res
     adv.ctl[CTL_WINDOW] += 1;
   }
 }
+
+// Adam (arl_net_set_adam, arl_adam; an extension, the reference has none): Chainer 1.8.1's optimizers.Adam
+// as NumPy evaluates it on f32 arrays, restated in include/asyncrl_hip.h ("Adam").  State m, v (f32); for
+// update number t: lr_t = (float)(alpha * sqrt(1 - beta2^t) / (1 - beta1^t)) in f64, then per element
+//   m += c1 * (g - m); v += c2 * (g * g - v); p -= (lr_t * m) / (sqrt(v) + eps)
+// every op an explicit round-to-nearest f32 op in that order (adam1), c1 = f32(1 - beta1), c2 = f32(1 - beta2).
+// adam_kernel is rmsprop_kernel's body with a fourth array: the same clip, decay, FC plane rewrite and
+// window advance; 28 bytes move per parameter (read p, m, v, g; write p, m, v).
+// t lives on the device, so that a captured update replays with a fresh bias correction (as the lr anneal
+// does): ctl[CTL_ADAM_T] holds the updates made so far.  No workgroup may read a word another workgroup of
+// the launch writes (the CTL_STEP / CTL_STEP_SNAP hazard), so the count moves in a launch of its own:
+// adam_tick_kernel (one thread, before the update on the same stream) adds 1, and adam_kernel only reads it;
+// every workgroup computes lr_t for that t itself in f64 while its first loads are in flight.  (The count moved
+// by the update kernel's last workgroup to finish, a ticket on a second ctl slot, measured 19 us a window at C4
+// -- 662 agent-scope releases and atomics on one word; the extra launch measures 4.6 us: DESIGN.md.)
+// beta^t is binary exponentiation in explicit f64 multiplies (exact at t = 1, a relative error below 2 log2(t)
+// ulp, which leaves the f32 lr_t within 1 ulp of Python's): two pow calls in every workgroup cost 2.3 us.
+struct AdamConst {
+  RmsConst lr;            // lr0 = Adam's alpha with update_lr's anneal arguments (lr.alpha / one_minus_alpha / eps unused)
+  float c1, c2, eps;
+  double beta1, beta2;
+  const int64_t* tctl;    // the control block: t = tctl[CTL_ADAM_T]; null: lr_t below is the host's for its t
+  float lr_t;
+};
+
+// the bias-corrected step size of update t (>= 1), shared by adam_kernel and adam_tick_kernel's record
+__device__ inline float adam_lr(const AdamConst& a, int64_t t) {
+  const double alpha = (a.lr.ctl == nullptr || a.lr.total <= 0) ? a.lr.lr0 : anneal_f64(a.lr);
+  double r1 = 1.0, r2 = 1.0, b1 = a.beta1, b2 = a.beta2;   // beta1^t, beta2^t
+  for (int64_t k = t; k > 0; k >>= 1) {
+    if (k & 1) {
+      r1 = __dmul_rn(r1, b1);
+      r2 = __dmul_rn(r2, b2);
+    }
+    b1 = __dmul_rn(b1, b1);
+    b2 = __dmul_rn(b2, b2);
+  }
+  const double fix1 = 1.0 - r1, fix2 = 1.0 - r2;
+  return (float)(alpha * sqrt(fix2) / fix1);
+}
+
+__device__ inline void adam1(float& p, float& m, float& v, float g, const AdamConst& a, float lr) {
+  m = __fadd_rn(m, __fmul_rn(a.c1, __fsub_rn(g, m)));                    // m += (1-b1)*(g-m)
+  v = __fadd_rn(v, __fmul_rn(a.c2, __fsub_rn(__fmul_rn(g, g), v)));      // v += (1-b2)*(g*g-v)
+  p = __fsub_rn(p, __fdiv_rn(__fmul_rn(lr, m), __fadd_rn(sqrtf(v), a.eps)));   // p -= lr_t*m/(sqrt(v)+eps)
+}
+
+// one float4 of p / m / v / g per thread and pass, the first pass's loads in flight with the norm's
+template <class Decay>
+__global__ void __launch_bounds__(256)
+adam_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g, int64_t n,
+            AdamConst a, const double* __restrict__ norm_sq, int nparts, float clip, AdvanceArgs adv, Decay wd) {
+  constexpr bool WD = std::is_same<Decay, DecayArgs>::value;
+  __shared__ double sh[8];
+  const int64_t n4 = n >> 2;
+  float4* p4 = reinterpret_cast<float4*>(p);
+  float4* m4 = reinterpret_cast<float4*>(m);
+  float4* v4 = reinterpret_cast<float4*>(v);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  float4 pv, mv, vv, gv;
+  bool bias0 = false;
+  if (n4 > 0) {   // (past the end: a clamped duplicate, never stored)
+    const int64_t i = min(i0, n4 - 1);
+    pv = p4[i];
+    mv = m4[i];
+    vv = v4[i];
+    gv = g4[i];
+    if constexpr (WD) bias0 = in_bias(wd, 4 * i);
+  }
+  // (adam_tick_kernel has counted this update; nothing in this launch writes the word)
+  const float lr = a.tctl != nullptr ? adam_lr(a, a.tctl[CTL_ADAM_T]) : a.lr_t;
+  float scale = 1.f;
+  bool do_clip = false;
+  if (norm_sq != nullptr) do_clip = clip_scale(partials_sum(norm_sq, nparts, sh), clip, scale);
+  for (int64_t ib = i0; ib < n4; ib += gsz) {
+    if (ib != i0) {
+      pv = p4[ib];
+      mv = m4[ib];
+      vv = v4[ib];
+      gv = g4[ib];
+    }
+    if (do_clip) {
+      gv.x = __fmul_rn(gv.x, scale); gv.y = __fmul_rn(gv.y, scale);
+      gv.z = __fmul_rn(gv.z, scale); gv.w = __fmul_rn(gv.w, scale);
+    }
+    if constexpr (WD) {   // after the clip, as Chainer runs the two hooks
+      if (!(ib == i0 ? bias0 : in_bias(wd, 4 * ib))) {
+        gv.x = decay1(gv.x, pv.x, wd.rate); gv.y = decay1(gv.y, pv.y, wd.rate);
+        gv.z = decay1(gv.z, pv.z, wd.rate); gv.w = decay1(gv.w, pv.w, wd.rate);
+      }
+    }
+    adam1(pv.x, mv.x, vv.x, gv.x, a, lr);
+    adam1(pv.y, mv.y, vv.y, gv.y, a, lr);
+    adam1(pv.z, mv.z, vv.z, gv.z, a, lr);
+    adam1(pv.w, mv.w, vv.w, gv.w, a, lr);
+    p4[ib] = pv;
+    m4[ib] = mv;
+    v4[ib] = vv;
+    const int64_t e = 4 * ib - adv.fc_w0;   // the FC weight's split planes follow their f32 W (fc.hip)
+    if (adv.fc_planes != nullptr && e >= 0 && e < (int64_t)HID * A2) fc_planes_store(adv.fc_planes, (int)e, pv);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const int64_t j = (n4 << 2) + threadIdx.x;
+    float gt = g[j];
+    if (do_clip) gt = __fmul_rn(gt, scale);
+    float pt = p[j], mt = m[j], vt = v[j];
+    if constexpr (WD)
+      if (!in_bias(wd, j)) gt = decay1(gt, pt, wd.rate);
+    adam1(pt, mt, vt, gt, a, lr);
+    p[j] = pt;
+    m[j] = mt;
+    v[j] = vt;
+  }
+  if (adv.ctl != nullptr) {   // the window advance, as rmsprop_kernel's
+    for (int64_t i = i0; i < adv.n; i += gsz) adv.reset[i] = adv.reset[(int64_t)adv.T * adv.n + i];
+    if (adv.hbuf != nullptr)
+      for (int64_t i = i0; i < (int64_t)adv.n * HID; i += gsz) {
+        adv.hbuf[i] = adv.hbuf[(int64_t)adv.T * adv.n * HID + i];
+        adv.cbuf[i] = adv.cbuf[(int64_t)adv.T * adv.n * HID + i];
+      }
+    if (i0 == 0) {
+      adv.ctl[CTL_STEP] += adv.T;
+      adv.ctl[CTL_WINDOW] += 1;
+    }
+  }
+}
+
+// One thread, before adam_kernel on its stream: count the update (the only writer of ctl[CTL_ADAM_T] besides
+// arl_net_set_adam_t and arl_net_reset).  With window statistics on (log non-null; window_stats_kernel ran just
+// before and left count at its record's index + 1) field 16 of that record becomes this update's Adam lr_t.
+__global__ void adam_tick_kernel(int64_t* ctl, AdamConst a, double* __restrict__ log,
+                                 const int64_t* __restrict__ count) {
+  const int64_t t = ctl[CTL_ADAM_T] + 1;
+  ctl[CTL_ADAM_T] = t;
+  if (log == nullptr) return;
+  const int64_t cnt = *count;
+  if (cnt < 1) return;
+  log[(int64_t)((uint64_t)(cnt - 1) % WINDOW_LOG) * WINDOW_STAT_FIELDS + 16] = (double)adam_lr(a, t);
+}
+
+__global__ void ctl_write_kernel(int64_t* ctl, int idx, int64_t value) { ctl[idx] = value; }
 
 // Per-window training statistics (arl_net_set_window_stats; semantics in include/asyncrl_hip.h, "window
 // statistics"): one record per update, launched by net_optimize between the norm's partials and the update
@@ -448,6 +600,56 @@ hipError_t launch_rmsprop(float* p, float* ms, const float* g, int64_t n, double
   else
     hipLaunchKernelGGL(rmsprop_kernel<NoDecay>, dim3(stream_blocks(n)), dim3(256), 0, s, p, ms, g, n, c, norm_sq, nparts,
                        clip, a, NoDecay{});
+  return hipGetLastError();
+}
+
+// ad.tctl null: lr_t for the host's ad.t from the host's libm, in Python's order (bit-identical to Adam.lr)
+static AdamConst adam_const(double lr, double eps, const AdamArgs& ad, const int64_t* ctl, int64_t total_steps,
+                            int64_t n_total, int t_max, bool advance) {
+  AdamConst a;
+  a.lr = rms_const(lr, 0.0, 0.0, ctl, total_steps, n_total, t_max, advance);
+  a.c1 = (float)(1.0 - ad.beta1);
+  a.c2 = (float)(1.0 - ad.beta2);
+  a.eps = (float)eps;
+  a.beta1 = ad.beta1;
+  a.beta2 = ad.beta2;
+  a.tctl = ad.tctl;
+  a.lr_t = 0.f;
+  if (ad.tctl == nullptr) {
+    const double fix1 = 1.0 - std::pow(ad.beta1, (double)ad.t), fix2 = 1.0 - std::pow(ad.beta2, (double)ad.t);
+    a.lr_t = (float)(lr * std::sqrt(fix2) / fix1);
+  }
+  return a;
+}
+
+hipError_t launch_adam(float* p, float* m, float* v, const float* g, int64_t n, double lr, double eps,
+                       const AdamArgs& ad, const double* norm_sq, int nparts, float clip, const int64_t* ctl,
+                       int64_t total_steps, int64_t n_total, int t_max, hipStream_t s, const AdvanceArgs* adv,
+                       const DecayArgs* wd) {
+  if (wd != nullptr && (wd->n_bias < 0 || wd->n_bias > DECAY_MAX_BIAS)) return hipErrorInvalidValue;
+  if (norm_sq != nullptr && (nparts < 1 || nparts > NORM_MAX_PARTS)) return hipErrorInvalidValue;
+  if (ad.tctl == nullptr && ad.t < 1) return hipErrorInvalidValue;
+  if (n <= 0) return hipSuccess;
+  const AdamConst a = adam_const(lr, eps, ad, ctl, total_steps, n_total, t_max, adv != nullptr && adv->ctl != nullptr);
+  AdvanceArgs av{};
+  if (adv != nullptr) av = *adv;
+  if (ad.tctl != nullptr) {   // count the update (and, with a window record, note its lr_t) ahead of the kernel
+    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, s, ad.tctl, a, ad.stats_log, ad.stats_count);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (wd != nullptr && wd->rate != 0.f)
+    hipLaunchKernelGGL(adam_kernel<DecayArgs>, dim3(stream_blocks(n)), dim3(256), 0, s, p, m, v, g, n, a, norm_sq, nparts,
+                       clip, av, *wd);
+  else
+    hipLaunchKernelGGL(adam_kernel<NoDecay>, dim3(stream_blocks(n)), dim3(256), 0, s, p, m, v, g, n, a, norm_sq, nparts,
+                       clip, av, NoDecay{});
+  return hipGetLastError();
+}
+
+hipError_t launch_ctl_write(int64_t* ctl, int idx, int64_t value, hipStream_t s) {
+  if (idx < 0 || idx >= CTL_SIZE) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ctl_write_kernel, dim3(1), dim3(1), 0, s, ctl, idx, value);
   return hipGetLastError();
 }
 

@@ -200,6 +200,50 @@ int arl_net_set_loss(arl_net* net, double pi_loss_coef, int keep_loss_scale_same
  * arl_run_stage(ARL_STAGE_RMSPROP) stays the decay-free timing form. */
 int arl_net_set_weight_decay(arl_net* net, double rate);
 
+/* Adam (Kingma & Ba 2015) as a second fused update kernel.  An extension,
+ * off by default: the reference has RMSpropAsync only, whose hyperparameters
+ * were tuned for one Hogwild process; the batched learner steps once per window
+ * on the gradient of all envs.  The arithmetic is Chainer 1.8.1's
+ * optimizers.Adam as NumPy evaluates it on float32 arrays.  State m, v: f32,
+ * zero-initialised.  For update number t (1 for the first update):
+ *   fix1 = 1 - beta1**t;  fix2 = 1 - beta2**t                     (float64)
+ *   lr_t = (float)(alpha_a * sqrt(fix2) / fix1)     (float64, left to right, one rounding)
+ *   m = f32(m + f32(c1 * f32(g - m)))               c1 = (float)(1.0 - beta1)
+ *   v = f32(v + f32(c2 * f32(f32(g * g) - v)))      c2 = (float)(1.0 - beta2)
+ *   p = f32(p - f32(f32(lr_t * m) / f32(sqrtf(v) + (float)eps)))
+ * every elementwise operation round-to-nearest f32, unfused, in this order.
+ * alpha_a is the call's lr0 as a double, or with total_steps > 0 the anneal of
+ * arl_optimize in f64: max(total - global_t - 1, 0) / total * lr0.  g is the
+ * gradient after GradientClipping and NonbiasWeightDecay, exactly as they feed
+ * the RMSProp update.
+ *
+ * arl_net_set_adam(net, m, beta1, beta2): while m is set, every update of the
+ * net (arl_optimize, arl_optimize_advance, arl_run_window) runs the Adam kernel
+ * instead of the RMSProp one, with the same side duties (the FC weight's split
+ * planes, the fused window advance).  m: param_floats f32, caller-owned,
+ * 16-byte aligned, zeroed by the caller; the bound ms buffer holds v.  The
+ * update call's lr0 is Adam's alpha and its eps Adam's eps; its alpha argument
+ * (RMSProp's decay) is ignored.  m == NULL switches back to RMSpropAsync.  Host
+ * state of the handle, like arl_net_set_weight_decay; ARL_EINVAL for a
+ * misaligned m or a beta outside [0, 1) (NaN included).  A captured update keeps
+ * the optimizer (and m, beta1, beta2) it was captured with.
+ * arl_run_stage(ARL_STAGE_RMSPROP) keeps launching the RMSProp kernel.
+ *
+ * The update number lives on the device, so that a captured window replays
+ * with a fresh bias correction: slot ARL_CTL_ADAM_T of the control block
+ * (arl_net_buffer "ctl", int64[16]) holds the number of Adam updates made so
+ * far; an update adds 1 (a one-thread launch ahead of the update kernel, so
+ * that no workgroup reads a word its own launch writes) and uses the new count
+ * as t.  Every workgroup computes lr_t itself in f64, beta**t by binary
+ * exponentiation (exact at t = 1); against Python's pow the f32 lr_t can
+ * differ by at most 1 ulp, and almost never does.
+ * arl_net_reset zeroes the counter with the rest of the control block.
+ * arl_net_set_adam_t: asynchronous write of the counter on `stream` (checkpoint
+ * resume); read it through the "ctl" buffer.  ARL_ESTATE on an unbound net. */
+#define ARL_CTL_ADAM_T 3
+int arl_net_set_adam(arl_net* net, float* m, double beta1, double beta2);
+int arl_net_set_adam_t(arl_net* net, int64_t t, void* stream);
+
 /* Generalized advantage estimation, GAE(lambda) (Schulman et al. 2016), for
  * the policy term.  An extension: the reference has only the n-step advantage.
  * With lambda != 1 the learner's returns kernel also scans, per env and in
@@ -298,7 +342,9 @@ int arl_learn_part(arl_net* net, int part, double gamma, double beta, double v_l
 /* GradientClipping(clip) + RMSpropAsync update (a3c_ale.py:224-226,
  * rmsprop_async.py:23-29) of the bound params / ms from the bound grads.
  * total_steps > 0 anneals lr on device (a3c_ale.py:111-112) with global_t =
- * (step + t_max) * n_total; otherwise lr = lr0.  clip <= 0 disables clipping. */
+ * (step + t_max) * n_total; otherwise lr = lr0.  clip <= 0 disables clipping.
+ * After arl_net_set_adam the update is Adam's instead: lr0 is its alpha (annealed
+ * the same way), eps its eps, and the alpha argument is ignored. */
 int arl_optimize(arl_net* net, double lr0, int64_t total_steps, int64_t n_total, double alpha, double eps,
                  double clip, void* stream);
 
@@ -471,7 +517,10 @@ int arl_episode_stats(arl_net* net, double* out8_device, int clear, void* stream
  *                    partials the update kernel reads (with several ranks: of
  *                    the all-reduced gradient)
  *   15 clip_scale    (double) of the f32 scale the update applies; 1.0 when it does not clip
- *   16 lr            (double) of the f32 learning rate the update uses, anneal included
+ *   16 lr            (double) of the f32 learning rate the update uses, anneal included;
+ *                    with arl_net_set_adam the bias-corrected lr_t of this update, from
+ *                    the Adam kernel's own device function (written by the one-thread
+ *                    launch that counts the update)
  * gamma, clip_reward and the GAE lambda are those of the last returns launch of the net
  * (arl_learn, arl_learn_part(LEARN_RETURNS), the returns fused into the
  * bootstrap step, arl_run_window); 0.99 and 1 before any.  With clip <= 0 the
@@ -517,6 +566,16 @@ int arl_rmsprop(float* param, float* ms, const float* grad, int64_t n, double lr
  * arl_rmsprop).  weight_decay < 0 or not finite: ARL_EINVAL. */
 int arl_rmsprop_wd(float* param, float* ms, const float* grad, int64_t n, double lr, double alpha, double eps,
                    double clip, double* norm_partials, double weight_decay, void* stream);
+
+/* One Adam update (the arithmetic of arl_net_set_adam above) on flat f32
+ * arrays, the counterpart of arl_rmsprop / arl_rmsprop_wd: param, m, v updated
+ * from grad (read only) for update number t >= 1, which comes from the caller;
+ * lr_t is computed on the host in double with the C library's pow / sqrt (what
+ * Python uses), so it is bit-identical to the formula evaluated there.  clip,
+ * norm_partials as arl_rmsprop; weight_decay as arl_rmsprop_wd (0: none).
+ * t < 1, a beta outside [0, 1), a bad weight_decay: ARL_EINVAL. */
+int arl_adam(float* param, float* m, float* v, const float* grad, int64_t n, double alpha, double beta1, double beta2,
+             double eps, int64_t t, double clip, double* norm_partials, double weight_decay, void* stream);
 
 /* SoftmaxPolicyOutput (policy_output.py:32-61) + FCSoftmaxPolicy / FCVFunction
  * heads (policy.py:53-58, v_function.py:29-34) for h: (n, 256) f32.  Samples
