@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <string>
 
 #include "../../include/asyncrl_hip.h"
@@ -667,54 +668,63 @@ int arl_reset_state(arl_net* h, int64_t e0, int64_t n, void* s) {
   return hip_status(arl::net_reset_state(h->net, (int)e0, (int)n, S(s)), "reset_state");
 }
 
-// wd: null, or the decay of the whole array (no bias ranges)
+// The one-array updates (arl_rmsprop, arl_rmsprop_wd, arl_adam) share two steps; who: their error texts' prefix.
+// 1. the arrays: none null unless n == 0, all 16-byte aligned
+static int update_arrays_ok(const std::string& who, std::initializer_list<const void*> arrays, int64_t n) {
+  bool null = false, align = true;
+  for (const void* a : arrays) {
+    null |= a == nullptr;
+    align &= aligned(a, 16);
+  }
+  if (n < 0 || (n > 0 && null)) return fail(ARL_EINVAL, who + ": null pointer / n < 0");
+  if (!align) return fail(ARL_EINVAL, who + ": 16-byte alignment");
+  return ARL_OK;
+}
+// 2. the clip's scratch and its norm launch; leaves in u (and wd, the decay of the whole array at `rate`, no bias
+// ranges) what the optimizer's launch takes
+static int update_array_args(const std::string& who, const float* g, int64_t n, double clip, double* parts,
+                             double rate, void* s, arl::DecayArgs& wd, arl::UpdateArgs& u) {
+  if (clip > 0 && !parts) return fail(ARL_EINVAL, who + ": clip needs norm_partials scratch");
+  wd.rate = (float)rate;
+  u.norm_sq = clip > 0 ? parts : nullptr;
+  u.nparts = 256;
+  u.clip = (float)clip;
+  u.wd = &wd;
+  return clip > 0 ? hip_status(arl::launch_grad_sqnorm(g, n, parts, u.nparts, S(s)), who.c_str()) : ARL_OK;
+}
+
 static int rmsprop_array(float* p, float* ms, const float* g, int64_t n, double lr, double alpha, double eps,
-                         double clip, double* parts, const arl::DecayArgs* wd, void* s) {
-  if (n < 0 || (n > 0 && (!p || !ms || !g))) return fail(ARL_EINVAL, "rmsprop: null pointer / n < 0");
-  if (!aligned(p, 16) || !aligned(ms, 16) || !aligned(g, 16)) return fail(ARL_EINVAL, "rmsprop: 16-byte alignment");
-  if (clip > 0 && !parts) return fail(ARL_EINVAL, "rmsprop: clip needs norm_partials scratch");
-  hipError_t e = hipSuccess;
-  const int blocks = 256;
-  if (clip > 0) e = arl::launch_grad_sqnorm(g, n, parts, blocks, S(s));
-  if (e == hipSuccess)
-    e = arl::launch_rmsprop(p, ms, g, n, lr, alpha, eps, clip > 0 ? parts : nullptr, blocks, (float)clip, nullptr, 0,
-                            0, 0, S(s), nullptr, wd);
-  return hip_status(e, "rmsprop");
+                         double clip, double* parts, double rate, void* s) {
+  arl::DecayArgs wd{};
+  arl::UpdateArgs u;
+  if (const int rc = update_arrays_ok("rmsprop", {p, ms, g}, n)) return rc;
+  if (const int rc = update_array_args("rmsprop", g, n, clip, parts, rate, s, wd, u)) return rc;
+  return hip_status(arl::launch_rmsprop(p, ms, g, n, lr, alpha, eps, u, S(s)), "rmsprop");
 }
 
 int arl_rmsprop(float* p, float* ms, const float* g, int64_t n, double lr, double alpha, double eps, double clip,
                 double* parts, void* s) {
-  return rmsprop_array(p, ms, g, n, lr, alpha, eps, clip, parts, nullptr, s);
+  return rmsprop_array(p, ms, g, n, lr, alpha, eps, clip, parts, 0.0, s);
 }
 
 int arl_rmsprop_wd(float* p, float* ms, const float* g, int64_t n, double lr, double alpha, double eps, double clip,
                    double* parts, double weight_decay, void* s) {
   if (!decay_rate_ok(weight_decay))
     return fail(ARL_EINVAL, "rmsprop_wd: weight_decay must be finite and >= 0");
-  arl::DecayArgs wd{};
-  wd.rate = (float)weight_decay;
-  return rmsprop_array(p, ms, g, n, lr, alpha, eps, clip, parts, &wd, s);
+  return rmsprop_array(p, ms, g, n, lr, alpha, eps, clip, parts, weight_decay, s);
 }
 
 int arl_adam(float* p, float* m, float* v, const float* g, int64_t n, double alpha, double beta1, double beta2,
              double eps, int64_t t, double clip, double* parts, double weight_decay, void* s) {
-  if (n < 0 || (n > 0 && (!p || !m || !v || !g))) return fail(ARL_EINVAL, "adam: null pointer / n < 0");
-  if (!aligned(p, 16) || !aligned(m, 16) || !aligned(v, 16) || !aligned(g, 16))
-    return fail(ARL_EINVAL, "adam: 16-byte alignment");
+  if (const int rc = update_arrays_ok("adam", {p, m, v, g}, n)) return rc;
   if (t < 1) return fail(ARL_EINVAL, "adam: t must be >= 1 (the number of this update)");
   if (!adam_beta_ok(beta1) || !adam_beta_ok(beta2)) return fail(ARL_EINVAL, "adam: beta1 and beta2 must be in [0, 1)");
   if (!decay_rate_ok(weight_decay)) return fail(ARL_EINVAL, "adam: weight_decay must be finite and >= 0");
-  if (clip > 0 && !parts) return fail(ARL_EINVAL, "adam: clip needs norm_partials scratch");
-  arl::DecayArgs wd{};
-  wd.rate = (float)weight_decay;
   const arl::AdamArgs ad{beta1, beta2, nullptr, t};
-  hipError_t e = hipSuccess;
-  const int blocks = 256;
-  if (clip > 0) e = arl::launch_grad_sqnorm(g, n, parts, blocks, S(s));
-  if (e == hipSuccess)
-    e = arl::launch_adam(p, m, v, g, n, alpha, eps, ad, clip > 0 ? parts : nullptr, blocks, (float)clip, nullptr, 0, 0,
-                         0, S(s), nullptr, &wd);
-  return hip_status(e, "adam");
+  arl::DecayArgs wd{};
+  arl::UpdateArgs u;
+  if (const int rc = update_array_args("adam", g, n, clip, parts, weight_decay, s, wd, u)) return rc;
+  return hip_status(arl::launch_adam(p, m, v, g, n, alpha, eps, ad, u, S(s)), "adam");
 }
 
 int arl_policy(const float* hh, int64_t n, const float* Wpi, const float* bpi, const float* Wv, const float* bv,

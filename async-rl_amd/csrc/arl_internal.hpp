@@ -448,11 +448,21 @@ struct AdvanceArgs {
 // that sums them (grad_sqnorm_kernel, or reduce_conv_bwd_kernel with a NormFold), one per block;
 // every block of the update kernel re-reduces them in block order
 constexpr int NORM_MAX_PARTS = 1000, NORM_SCRATCH = 1024;
-// norm_sq: the norm's partials [0, nparts), re-reduced by every block; null: no clip
+// What one update's launches share (launch_rmsprop, launch_adam and, for the record of that update,
+// launch_window_stats), whichever optimizer runs it.
+struct UpdateArgs {
+  const double* norm_sq = nullptr;   // the norm's partials [0, nparts), re-reduced by every block; null: no clip
+  int nparts = 0;
+  float clip = 0.f;
+  const int64_t* lr_ctl = nullptr;   // the lr anneal (update_lr, optim.hip): the control block with total_steps > 0,
+  int64_t total_steps = 0;           //   else null: the lr as given
+  int64_t n_total = 0;
+  int t_max = 0;
+  const AdvanceArgs* adv = nullptr;  // null: no advance, no FC planes
+  const DecayArgs* wd = nullptr;     // null or rate == 0: the decay-free kernel
+};
 hipError_t launch_rmsprop(float* p, float* ms, const float* g, int64_t n, double lr, double alpha, double eps,
-                          const double* norm_sq, int nparts, float clip, const int64_t* ctl,
-                          int64_t total_steps, int64_t n_total, int t_max, hipStream_t s,
-                          const AdvanceArgs* adv = nullptr, const DecayArgs* wd = nullptr);
+                          const UpdateArgs& u, hipStream_t s);
 // Adam (Chainer 1.8.1 optimizers.Adam restated in include/asyncrl_hip.h) with launch_rmsprop's hooks and side
 // duties: lr = Adam's alpha (annealed as launch_rmsprop's lr), v = the second moment.  tctl = the control block:
 // a one-thread launch ahead of the update kernel adds 1 to tctl[CTL_ADAM_T], the update number the kernel then
@@ -466,9 +476,7 @@ struct AdamArgs {
   const int64_t* stats_count = nullptr;
 };
 hipError_t launch_adam(float* p, float* m, float* v, const float* g, int64_t n, double lr, double eps,
-                       const AdamArgs& ad, const double* norm_sq, int nparts, float clip, const int64_t* ctl,
-                       int64_t total_steps, int64_t n_total, int t_max, hipStream_t s,
-                       const AdvanceArgs* adv = nullptr, const DecayArgs* wd = nullptr);
+                       const AdamArgs& ad, const UpdateArgs& u, hipStream_t s);
 hipError_t launch_ctl_write(int64_t* ctl, int idx, int64_t value, hipStream_t s);
 hipError_t launch_grad_sqnorm(const float* g, int64_t n, double* partials, int blocks, hipStream_t s);
 // Per-window training statistics (arl_net_set_window_stats; the header's "window statistics"): one record
@@ -487,13 +495,12 @@ struct WindowStatsArgs {
   double* log;
   int64_t* count;
 };
-// One 256-thread workgroup (optim.hip window_stats_kernel).  The remaining arguments are launch_rmsprop's for
-// the update that follows, so that the recorded lr and clip scale come from the values (and the device
-// functions) the update kernel uses; norm_sq is always given, clip <= 0: the update does not clip.
+// One 256-thread workgroup (optim.hip window_stats_kernel).  lr and u are those of the update that follows, so
+// that the recorded lr and clip scale come from the values (and the device functions) the update kernel uses;
+// u.norm_sq is always given, u.clip <= 0: the update does not clip.
 // lambda != 1: adv_sum / adv_sumsq are those of the GAE advantage (gae_step), another kernel; 1: today's launch
-hipError_t launch_window_stats(const WindowStatsArgs& w, double lr, const double* norm_sq, int nparts, float clip,
-                               const int64_t* lr_ctl, int64_t total_steps, int64_t n_total, int t_max, bool advance,
-                               hipStream_t s, double lambda = 1.0);
+hipError_t launch_window_stats(const WindowStatsArgs& w, double lr, const UpdateArgs& u, hipStream_t s,
+                               double lambda = 1.0);
 hipError_t launch_stream_copy(const void* src, void* dst, int64_t bytes, int blocks, int mode, hipStream_t s);
 hipError_t launch_policy(const float* h, int64_t n, const float* Wpi, const float* bpi, const float* Wv,
                          const float* bv, int A, uint64_t seed, const int64_t* ctl, int64_t step_off,

@@ -690,10 +690,14 @@ hipError_t net_stage(Net& net, int stage, int t, hipStream_t s) {
     case STAGE_LSTM_WGRAD:
       if (net.arch != ARCH_LSTM) return hipErrorInvalidValue;
       return lstm_wgrad(net, s);
-    case STAGE_RMSPROP:   // the update kernel as a window runs it (clip 40 from the last norm the window left), lr 0
-      return launch_rmsprop(net.p, net.ms, net.g, net.param_floats, 0.0, 0.99, 0.1, net.at<double>(net.w_norm),
-                            net.norm_ready ? conv_norm_parts(net.norm_rest_blocks) : net.norm_blocks, 40.f, nullptr, 0,
-                            0, net.T, s);
+    case STAGE_RMSPROP: {   // the update kernel as a window runs it (clip 40 from the last norm the window left), lr 0
+      UpdateArgs u;
+      u.norm_sq = net.at<double>(net.w_norm);
+      u.nparts = net.norm_ready ? conv_norm_parts(net.norm_rest_blocks) : net.norm_blocks;
+      u.clip = 40.f;
+      u.t_max = net.T;
+      return launch_rmsprop(net.p, net.ms, net.g, net.param_floats, 0.0, 0.99, 0.1, u, s);
+    }
     default:
       return hipErrorInvalidValue;
   }
@@ -713,20 +717,6 @@ hipError_t net_optimize(Net& net, double lr0, int64_t total_steps, int64_t n_tot
     ARL_TRY(launch_grad_sqnorm(net.g, net.param_floats, parts, net.norm_blocks, s));
     ARL_TRY(stamp(net, STAGE_GRAD_SQNORM, s));
   }
-  const int nparts = folded ? conv_norm_parts(net.norm_rest_blocks) : net.norm_blocks;
-  const int64_t* lr_ctl = total_steps > 0 ? net.at<int64_t>(net.w_ctl) : nullptr;
-  const bool adam = net.adam_m != nullptr;
-  AdamArgs ad{net.adam_beta1, net.adam_beta2, net.at<int64_t>(net.w_ctl), 0};
-  if (net.window_stats) {   // one record of the window this update consumes, before anything advances
-    const WindowStatsArgs w{net.at<float>(net.w_rewards), net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v),
-                            net.at<float>(net.w_ent), net.at<float>(net.w_loss), net.T, net.N, net.win_gamma,
-                            net.win_clip_reward, net.at<int64_t>(net.w_ctl), net.at<double>(net.w_win_log),
-                            net.at<int64_t>(net.w_win_count)};
-    ARL_TRY(launch_window_stats(w, lr0, parts, nparts, clip, lr_ctl, total_steps, n_total, net.T, fused, s,
-                                net.win_lambda));
-    ad.stats_log = net.at<double>(net.w_win_log);   // (Adam: the record's lr becomes its step size, launch_adam)
-    ad.stats_count = net.at<int64_t>(net.w_win_count);
-  }
   const bool L = net.arch == ARCH_LSTM;
   // the update rewrites the FC weight's split planes with the new W (all of them, so they are current
   // afterwards even if they were not before)
@@ -734,14 +724,33 @@ hipError_t net_optimize(Net& net, double lr0, int64_t total_steps, int64_t n_tot
   const AdvanceArgs adv{fused ? net.at<int64_t>(net.w_ctl) : nullptr, planes, net.o_fcW, net.at<uint8_t>(net.w_reset),
                         L ? net.at<float>(net.w_hbuf) : nullptr, L ? net.at<float>(net.w_cbuf) : nullptr, net.T,
                         net.N};
+  UpdateArgs u;   // of the record and of the update
+  u.norm_sq = parts;
+  u.nparts = folded ? conv_norm_parts(net.norm_rest_blocks) : net.norm_blocks;
+  u.clip = clip;
+  u.lr_ctl = total_steps > 0 ? net.at<int64_t>(net.w_ctl) : nullptr;
+  u.total_steps = total_steps;
+  u.n_total = n_total;
+  u.t_max = net.T;
+  u.adv = &adv;
+  u.wd = &net.decay;
+  AdamArgs ad{net.adam_beta1, net.adam_beta2, net.at<int64_t>(net.w_ctl), 0};
+  if (net.window_stats) {   // one record of the window this update consumes, before anything advances
+    const WindowStatsArgs w{net.at<float>(net.w_rewards), net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v),
+                            net.at<float>(net.w_ent), net.at<float>(net.w_loss), net.T, net.N, net.win_gamma,
+                            net.win_clip_reward, net.at<int64_t>(net.w_ctl), net.at<double>(net.w_win_log),
+                            net.at<int64_t>(net.w_win_count)};
+    ARL_TRY(launch_window_stats(w, lr0, u, s, net.win_lambda));
+    ad.stats_log = net.at<double>(net.w_win_log);   // (Adam: the record's lr becomes its step size, launch_adam)
+    ad.stats_count = net.at<int64_t>(net.w_win_count);
+  }
+  if (!do_clip) u.norm_sq = nullptr;   // (the record took the norm; the update reads it only to clip)
   if (planes != nullptr) net.planes_gen = net.param_gen;
   // the net's optimizer (arl_net_set_adam): Adam takes lr0 as its alpha and ms as its second moment
-  if (adam)
-    ARL_TRY(launch_adam(net.p, net.adam_m, net.ms, net.g, net.param_floats, lr0, eps, ad, do_clip ? parts : nullptr,
-                        nparts, clip, lr_ctl, total_steps, n_total, net.T, s, &adv, &net.decay));
+  if (net.adam_m != nullptr)
+    ARL_TRY(launch_adam(net.p, net.adam_m, net.ms, net.g, net.param_floats, lr0, eps, ad, u, s));
   else
-    ARL_TRY(launch_rmsprop(net.p, net.ms, net.g, net.param_floats, lr0, alpha, eps, do_clip ? parts : nullptr, nparts,
-                           clip, lr_ctl, total_steps, n_total, net.T, s, &adv, &net.decay));
+    ARL_TRY(launch_rmsprop(net.p, net.ms, net.g, net.param_floats, lr0, alpha, eps, u, s));
   ARL_TRY(stamp(net, STAGE_RMSPROP, s));
   return advance && !fused ? net_advance(net, s) : hipSuccess;
 }

@@ -10,28 +10,28 @@
 //     grid-stride, f64 across the block) -> partials[block] (the folded form:
 //     reduce_conv_bwd_kernel leaves the same partials, conv_bwd.hip), so the
 //     clip rate needs no host round trip and no extra launch;
-//   rmsprop_kernel: every block sums the partials in block order (their loads
-//     in flight with its first p / ms / g loads; a last-arriving block of the
-//     norm launch leaving one f64 instead measured 2-4 us slower a window, r4c),
-//     then 4 parameters per thread per
-//     iteration: g' = clip ? g*f32(rate) : g; ms = ms*alpha; ms += (c*g')*g';
-//     p -= (lr*g') / sqrt(ms + eps) -- every op an explicit round-to-nearest
-//     f32 op in the reference's order (NumPy f32 semantics, no FMA), so the
-//     result is bit-identical to update_one_cpu.
+//   the update kernel (update_body below, written once; rmsprop_kernel and adam_kernel are its entry points):
+//     every block sums the partials in block order (their loads in flight with its first p / state / g
+//     loads; a last-arriving block of the norm launch leaving one f64 instead measured 2-4 us slower a
+//     window, r4c), then 4 parameters per thread per iteration: g' = clip ? g*f32(rate) : g, the decay
+//     step, and the optimizer's rule on one element.  RMSProp's (rms1): ms = ms*alpha; ms += (c*g')*g';
+//     p -= (lr*g') / sqrt(ms + eps) -- every op an explicit round-to-nearest f32 op in the reference's
+//     order (NumPy f32 semantics, no FMA), so the result is bit-identical to update_one_cpu.  Then the FC
+//     weight's split planes are rewritten from the new W, and the launch that ends a window advances it.
 // 20 bytes move per parameter (read p, g, ms; write p, ms) + 4 for the norm.
 // With arl_net_set_window_stats on, window_stats_kernel (below) runs between the two and records what
 // the update is about to apply, through the same device functions (update_lr, partials_sum, clip_scale).
 //
 // NonbiasWeightDecay(rate) (a3c_ale.py:227-228, nonbias_weight_decay.py:4-28), the hook the reference adds
 // after the clip: g += rate * p for every parameter whose name is not a bias, i.e. t = f32(f32(rate) * p),
-// g = f32(g + t) (two roundings, NumPy's f32 array ops) on the clipped gradient.  rmsprop_kernel<DecayArgs> is the
-// same body with that step between the clip scale and rms1: p is in registers already, the bias tensors
+// g = f32(g + t) (two roundings, NumPy's f32 array ops) on the clipped gradient.  The <DecayArgs> instantiations
+// have that step between the clip scale and the rule: p is in registers already, the bias tensors
 // come as [begin, end) float ranges in the kernel arguments, so the decay moves no extra byte.  The clip
 // norm stays the norm of the gradient before the decay (the reference clips first).  rate == 0 launches
-// rmsprop_kernel<NoDecay>, the decay-free instantiation (g + f32(0 * p) would also turn a -0 gradient into +0).
+// the <NoDecay> instantiation, without the step (g + f32(0 * p) would also turn a -0 gradient into +0).
 //
-// Adam (arl_net_set_adam; an extension, off by default): adam_kernel below takes rmsprop_kernel's place in the
-// update with the same hooks and side duties; 28 bytes per parameter.
+// Adam (arl_net_set_adam; an extension, off by default): the same body with Adam's rule (adam1) and a second
+// state array, behind adam_kernel; 28 bytes per parameter.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -85,7 +85,7 @@ struct RmsConst {   // (AdvanceArgs is declared in arl_internal.hpp)
   int ctl_idx;              // CTL_STEP, or CTL_STEP_SNAP when this launch also advances
 };
 
-// The three pieces below are shared by rmsprop_kernel and window_stats_kernel, so that the recorded
+// The three pieces below are shared by the update kernels and window_stats_kernel, so that the recorded
 // learning rate, squared norm and clip scale are bit for bit the ones the update applies.
 
 // the anneal in f64 (only with the control block and a step budget): update_lr rounds it to f32, Adam's
@@ -125,8 +125,6 @@ __device__ inline bool clip_scale(double sqnorm, float clip, float& scale) {
   return false;
 }
 
-
-
 __device__ inline void rms1(float& p, float& ms, float g, const RmsConst& c) {
   ms = __fmul_rn(ms, c.alpha);                                   // ms *= alpha
   ms = __fadd_rn(ms, __fmul_rn(__fmul_rn(c.one_minus_alpha, g), g));   // ms += (1-a)*g*g
@@ -145,96 +143,13 @@ __device__ inline bool in_bias(const DecayArgs& wd, int64_t e) {
 
 __device__ inline float decay1(float g, float p, float rate) { return __fadd_rn(g, __fmul_rn(rate, p)); }
 
-struct NoDecay {};   // the decay-free instantiation's (empty) last kernel argument
-
-// one float4 of p / ms / g per thread and pass, the first pass's loads in flight with the norm's;
-// Decay = DecayArgs: the NonbiasWeightDecay step on every element outside wd's bias ranges (NoDecay: none)
-template <class Decay>
-__global__ void __launch_bounds__(256)
-rmsprop_kernel(float* __restrict__ p, float* __restrict__ ms, const float* __restrict__ g, int64_t n, RmsConst c,
-               const double* __restrict__ norm_sq, int nparts, float clip, AdvanceArgs adv, Decay wd) {
-  constexpr bool WD = std::is_same<Decay, DecayArgs>::value;
-  __shared__ double sh[8];
-  c.lr = update_lr(c);
-  const int64_t n4 = n >> 2;
-  float4* p4 = reinterpret_cast<float4*>(p);
-  float4* m4 = reinterpret_cast<float4*>(ms);
-  const float4* g4 = reinterpret_cast<const float4*>(g);
-  const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  // the first pass's float4 of p / ms / g are in flight with the squared norm's loads (n4 == 0: none;
-  // past the end: a clamped duplicate, never stored)
-  float4 pv, mv, gv;
-  bool bias0 = false;   // WD: the first pass's float4 lies in a bias tensor
-  if (n4 > 0) {
-    const int64_t i = min(i0, n4 - 1);
-    pv = p4[i];
-    mv = m4[i];
-    gv = g4[i];
-    // decided here so that the range table's kernel-argument loads (two cache lines no other argument
-    // shares) are issued with the first arguments': read first before the loop, the decay arm cost
-    // 1.1 us over the decay-free kernel's 7.8 us at C4, this way 0.5 us
-    if constexpr (WD) bias0 = in_bias(wd, 4 * i);
-  }
-  float scale = 1.f;
-  bool do_clip = false;
-  if (norm_sq != nullptr) do_clip = clip_scale(partials_sum(norm_sq, nparts, sh), clip, scale);
-  for (int64_t ib = i0; ib < n4; ib += gsz) {
-    if (ib != i0) {
-      pv = p4[ib];
-      mv = m4[ib];
-      gv = g4[ib];
-    }
-    if (do_clip) {
-      gv.x = __fmul_rn(gv.x, scale); gv.y = __fmul_rn(gv.y, scale);
-      gv.z = __fmul_rn(gv.z, scale); gv.w = __fmul_rn(gv.w, scale);
-    }
-    if constexpr (WD) {   // after the clip, as Chainer runs the two hooks
-      if (!(ib == i0 ? bias0 : in_bias(wd, 4 * ib))) {
-        gv.x = decay1(gv.x, pv.x, wd.rate); gv.y = decay1(gv.y, pv.y, wd.rate);
-        gv.z = decay1(gv.z, pv.z, wd.rate); gv.w = decay1(gv.w, pv.w, wd.rate);
-      }
-    }
-    rms1(pv.x, mv.x, gv.x, c);
-    rms1(pv.y, mv.y, gv.y, c);
-    rms1(pv.z, mv.z, gv.z, c);
-    rms1(pv.w, mv.w, gv.w, c);
-    p4[ib] = pv;
-    m4[ib] = mv;
-    const int64_t e = 4 * ib - adv.fc_w0;   // the FC weight's split planes follow their f32 W (fc.hip)
-    if (adv.fc_planes != nullptr && e >= 0 && e < (int64_t)HID * A2) fc_planes_store(adv.fc_planes, (int)e, pv);
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const int64_t j = (n4 << 2) + threadIdx.x;
-    float gt = g[j];
-    if (do_clip) gt = __fmul_rn(gt, scale);
-    float pt = p[j], mt = ms[j];
-    if constexpr (WD)
-      if (!in_bias(wd, j)) gt = decay1(gt, pt, wd.rate);
-    rms1(pt, mt, gt, c);
-    p[j] = pt;
-    ms[j] = mt;
-  }
-  if (adv.ctl == nullptr) return;   // (no window advance)
-  for (int64_t i = i0; i < adv.n; i += gsz) adv.reset[i] = adv.reset[(int64_t)adv.T * adv.n + i];
-  if (adv.hbuf != nullptr)
-    for (int64_t i = i0; i < (int64_t)adv.n * HID; i += gsz) {
-      adv.hbuf[i] = adv.hbuf[(int64_t)adv.T * adv.n * HID + i];
-      adv.cbuf[i] = adv.cbuf[(int64_t)adv.T * adv.n * HID + i];
-    }
-  if (i0 == 0) {
-    adv.ctl[CTL_STEP] += adv.T;
-    adv.ctl[CTL_WINDOW] += 1;
-  }
-}
-
 // Adam (arl_net_set_adam, arl_adam; an extension, the reference has none): Chainer 1.8.1's optimizers.Adam
 // as NumPy evaluates it on f32 arrays, restated in include/asyncrl_hip.h ("Adam").  State m, v (f32); for
 // update number t: lr_t = (float)(alpha * sqrt(1 - beta2^t) / (1 - beta1^t)) in f64, then per element
 //   m += c1 * (g - m); v += c2 * (g * g - v); p -= (lr_t * m) / (sqrt(v) + eps)
 // every op an explicit round-to-nearest f32 op in that order (adam1), c1 = f32(1 - beta1), c2 = f32(1 - beta2).
-// adam_kernel is rmsprop_kernel's body with a fourth array: the same clip, decay, FC plane rewrite and
-// window advance; 28 bytes move per parameter (read p, m, v, g; write p, m, v).
+// adam_kernel is update_body (below) with this rule and a second state array; 28 bytes move per parameter
+// (read p, m, v, g; write p, m, v).
 // t lives on the device, so that a captured update replays with a fresh bias correction (as the lr anneal
 // does): ctl[CTL_ADAM_T] holds the updates made so far.  No workgroup may read a word another workgroup of
 // the launch writes (the CTL_STEP / CTL_STEP_SNAP hazard), so the count moves in a launch of its own:
@@ -274,40 +189,66 @@ __device__ inline void adam1(float& p, float& m, float& v, float g, const AdamCo
   p = __fsub_rn(p, __fdiv_rn(__fmul_rn(lr, m), __fadd_rn(sqrtf(v), a.eps)));   // p -= lr_t*m/(sqrt(v)+eps)
 }
 
-// one float4 of p / m / v / g per thread and pass, the first pass's loads in flight with the norm's
-template <class Decay>
-__global__ void __launch_bounds__(256)
-adam_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g, int64_t n,
-            AdamConst a, const double* __restrict__ norm_sq, int nparts, float clip, AdvanceArgs adv, Decay wd) {
+// The per-element rules of update_body: the constants, the set-up every thread runs once while its first
+// loads are in flight, and one element's step on (p, s1, s2, g).  STATES: the state arrays beside p.
+struct RmsRule {
+  static constexpr int STATES = 1;   // ms
+  RmsConst c;
+  __device__ void setup() { c.lr = update_lr(c); }
+  __device__ void step(float& p, float& ms, float&, float g) const { rms1(p, ms, g, c); }
+};
+struct AdamRule {
+  static constexpr int STATES = 2;   // m, v
+  AdamConst a;
+  float lr;
+  // (adam_tick_kernel has counted this update; nothing in this launch writes the word)
+  __device__ void setup() { lr = a.tctl != nullptr ? adam_lr(a, a.tctl[CTL_ADAM_T]) : a.lr_t; }
+  __device__ void step(float& p, float& m, float& v, float g) const { adam1(p, m, v, g, a, lr); }
+};
+
+struct NoDecay {};   // the decay-free instantiations' (empty) last kernel argument
+
+// The fused update, written once for both optimizers: one float4 of p / s1 (/ s2) / g per thread and pass,
+// the first pass's loads in flight with the norm's; then the tail, then the window advance.
+// Decay = DecayArgs: the NonbiasWeightDecay step on every element outside wd's bias ranges (NoDecay: none).
+// s2 is read and written only by a rule with two state arrays (compiled out otherwise).
+template <class Rule, class Decay>
+__device__ __forceinline__ void update_body(Rule& rule, float* __restrict__ p, float* __restrict__ s1,
+                                            float* __restrict__ s2, const float* __restrict__ g, int64_t n,
+                                            const double* __restrict__ norm_sq, int nparts, float clip,
+                                            const AdvanceArgs& adv, const Decay& wd, int64_t i0, int64_t gsz) {
   constexpr bool WD = std::is_same<Decay, DecayArgs>::value;
+  constexpr bool S2 = Rule::STATES == 2;
   __shared__ double sh[8];
   const int64_t n4 = n >> 2;
   float4* p4 = reinterpret_cast<float4*>(p);
-  float4* m4 = reinterpret_cast<float4*>(m);
-  float4* v4 = reinterpret_cast<float4*>(v);
+  float4* a4 = reinterpret_cast<float4*>(s1);
+  float4* b4 = reinterpret_cast<float4*>(s2);
   const float4* g4 = reinterpret_cast<const float4*>(g);
-  const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  float4 pv, mv, vv, gv;
-  bool bias0 = false;
-  if (n4 > 0) {   // (past the end: a clamped duplicate, never stored)
+  // the first pass's float4s are in flight with the squared norm's loads (n4 == 0: none; past the end: a
+  // clamped duplicate, never stored)
+  float4 pv, av, bv, gv;
+  bool bias0 = false;   // WD: the first pass's float4 lies in a bias tensor
+  if (n4 > 0) {
     const int64_t i = min(i0, n4 - 1);
     pv = p4[i];
-    mv = m4[i];
-    vv = v4[i];
+    av = a4[i];
+    if constexpr (S2) bv = b4[i];
     gv = g4[i];
+    // decided here so that the range table's kernel-argument loads (two cache lines no other argument
+    // shares) are issued with the first arguments': read first before the loop, the decay arm cost
+    // 1.1 us over the decay-free kernel's 7.8 us at C4, this way 0.5 us
     if constexpr (WD) bias0 = in_bias(wd, 4 * i);
   }
-  // (adam_tick_kernel has counted this update; nothing in this launch writes the word)
-  const float lr = a.tctl != nullptr ? adam_lr(a, a.tctl[CTL_ADAM_T]) : a.lr_t;
+  rule.setup();
   float scale = 1.f;
   bool do_clip = false;
   if (norm_sq != nullptr) do_clip = clip_scale(partials_sum(norm_sq, nparts, sh), clip, scale);
   for (int64_t ib = i0; ib < n4; ib += gsz) {
     if (ib != i0) {
       pv = p4[ib];
-      mv = m4[ib];
-      vv = v4[ib];
+      av = a4[ib];
+      if constexpr (S2) bv = b4[ib];
       gv = g4[ib];
     }
     if (do_clip) {
@@ -320,13 +261,13 @@ adam_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
         gv.z = decay1(gv.z, pv.z, wd.rate); gv.w = decay1(gv.w, pv.w, wd.rate);
       }
     }
-    adam1(pv.x, mv.x, vv.x, gv.x, a, lr);
-    adam1(pv.y, mv.y, vv.y, gv.y, a, lr);
-    adam1(pv.z, mv.z, vv.z, gv.z, a, lr);
-    adam1(pv.w, mv.w, vv.w, gv.w, a, lr);
+    rule.step(pv.x, av.x, bv.x, gv.x);
+    rule.step(pv.y, av.y, bv.y, gv.y);
+    rule.step(pv.z, av.z, bv.z, gv.z);
+    rule.step(pv.w, av.w, bv.w, gv.w);
     p4[ib] = pv;
-    m4[ib] = mv;
-    v4[ib] = vv;
+    a4[ib] = av;
+    if constexpr (S2) b4[ib] = bv;
     const int64_t e = 4 * ib - adv.fc_w0;   // the FC weight's split planes follow their f32 W (fc.hip)
     if (adv.fc_planes != nullptr && e >= 0 && e < (int64_t)HID * A2) fc_planes_store(adv.fc_planes, (int)e, pv);
   }
@@ -334,26 +275,47 @@ adam_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
     const int64_t j = (n4 << 2) + threadIdx.x;
     float gt = g[j];
     if (do_clip) gt = __fmul_rn(gt, scale);
-    float pt = p[j], mt = m[j], vt = v[j];
+    float pt = p[j], at = s1[j], bt = 0.f;
+    if constexpr (S2) bt = s2[j];
     if constexpr (WD)
       if (!in_bias(wd, j)) gt = decay1(gt, pt, wd.rate);
-    adam1(pt, mt, vt, gt, a, lr);
+    rule.step(pt, at, bt, gt);
     p[j] = pt;
-    m[j] = mt;
-    v[j] = vt;
+    s1[j] = at;
+    if constexpr (S2) s2[j] = bt;
   }
-  if (adv.ctl != nullptr) {   // the window advance, as rmsprop_kernel's
-    for (int64_t i = i0; i < adv.n; i += gsz) adv.reset[i] = adv.reset[(int64_t)adv.T * adv.n + i];
-    if (adv.hbuf != nullptr)
-      for (int64_t i = i0; i < (int64_t)adv.n * HID; i += gsz) {
-        adv.hbuf[i] = adv.hbuf[(int64_t)adv.T * adv.n * HID + i];
-        adv.cbuf[i] = adv.cbuf[(int64_t)adv.T * adv.n * HID + i];
-      }
-    if (i0 == 0) {
-      adv.ctl[CTL_STEP] += adv.T;
-      adv.ctl[CTL_WINDOW] += 1;
+  if (adv.ctl == nullptr) return;   // (no window advance)
+  for (int64_t i = i0; i < adv.n; i += gsz) adv.reset[i] = adv.reset[(int64_t)adv.T * adv.n + i];
+  if (adv.hbuf != nullptr)
+    for (int64_t i = i0; i < (int64_t)adv.n * HID; i += gsz) {
+      adv.hbuf[i] = adv.hbuf[(int64_t)adv.T * adv.n * HID + i];
+      adv.cbuf[i] = adv.cbuf[(int64_t)adv.T * adv.n * HID + i];
     }
+  if (i0 == 0) {
+    adv.ctl[CTL_STEP] += adv.T;
+    adv.ctl[CTL_WINDOW] += 1;
   }
+}
+
+// The two entry points (profiles, the timeline scripts and bench.py know the update by these names).  They
+// compute i0, this thread's first float4, and gsz, the launch's thread count: read in a __global__ function
+// the workgroup size is a scalar kernel-argument load, read inside update_body it became a vector load.
+template <class Decay>
+__global__ void __launch_bounds__(256)
+rmsprop_kernel(float* __restrict__ p, float* __restrict__ ms, const float* __restrict__ g, int64_t n, RmsConst c,
+               const double* __restrict__ norm_sq, int nparts, float clip, AdvanceArgs adv, Decay wd) {
+  RmsRule rule{c};
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, gsz = (int64_t)gridDim.x * blockDim.x;
+  update_body(rule, p, ms, nullptr, g, n, norm_sq, nparts, clip, adv, wd, i0, gsz);
+}
+
+template <class Decay>
+__global__ void __launch_bounds__(256)
+adam_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g, int64_t n,
+            AdamConst a, const double* __restrict__ norm_sq, int nparts, float clip, AdvanceArgs adv, Decay wd) {
+  AdamRule rule{a, 0.f};
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, gsz = (int64_t)gridDim.x * blockDim.x;
+  update_body(rule, p, m, v, g, n, norm_sq, nparts, clip, adv, wd, i0, gsz);
 }
 
 // One thread, before adam_kernel on its stream: count the update (the only writer of ctl[CTL_ADAM_T] besides
@@ -548,66 +510,66 @@ hipError_t launch_grad_sqnorm(const float* g, int64_t n, double* partials, int b
   return hipGetLastError();
 }
 
-// each Python-float hyperparameter meets the f32 arrays as f32(value); advance: the launch also ends the window
-static RmsConst rms_const(double lr, double alpha, double eps, const int64_t* ctl, int64_t total_steps, int64_t n_total,
-                          int t_max, bool advance) {
+// each Python-float hyperparameter meets the f32 arrays as f32(value); the lr reads the learner's step
+// snapshot when the launch also ends the window
+static RmsConst rms_const(double lr, double alpha, double eps, const UpdateArgs& u) {
   RmsConst c;
   c.lr = (float)lr;
   c.alpha = (float)alpha;
   c.one_minus_alpha = (float)(1.0 - alpha);   // (1 - self.alpha) in Python double, then f32
   c.eps = (float)eps;
   c.lr0 = lr;
-  c.total = total_steps;
-  c.n_total = n_total;
-  c.t_max = t_max;
-  c.ctl = ctl;
-  c.ctl_idx = advance ? CTL_STEP_SNAP : CTL_STEP;
+  c.total = u.total_steps;
+  c.n_total = u.n_total;
+  c.t_max = u.t_max;
+  c.ctl = u.lr_ctl;
+  c.ctl_idx = u.adv != nullptr && u.adv->ctl != nullptr ? CTL_STEP_SNAP : CTL_STEP;
   return c;
 }
 
-hipError_t launch_window_stats(const WindowStatsArgs& w, double lr, const double* norm_sq, int nparts, float clip,
-                               const int64_t* lr_ctl, int64_t total_steps, int64_t n_total, int t_max, bool advance,
-                               hipStream_t s, double lambda) {
+hipError_t launch_window_stats(const WindowStatsArgs& w, double lr, const UpdateArgs& u, hipStream_t s, double lambda) {
   if (w.T < 1 || w.T > 64 || w.n < 1) return hipErrorInvalidValue;   // (the R_t columns: at most 64 KB of LDS)
-  if (norm_sq == nullptr || nparts < 1 || nparts > NORM_MAX_PARTS) return hipErrorInvalidValue;
-  // alpha / eps do not enter the record
-  const RmsConst c = rms_const(lr, 0.0, 0.0, lr_ctl, total_steps, n_total, t_max, advance);
+  if (u.norm_sq == nullptr || u.nparts < 1 || u.nparts > NORM_MAX_PARTS) return hipErrorInvalidValue;
+  const RmsConst c = rms_const(lr, 0.0, 0.0, u);   // alpha / eps do not enter the record
   const size_t lds = std::max(w.T > WS_RW ? (size_t)w.T * 256 * sizeof(float) : 0, (size_t)WS_SUMS * 256 * sizeof(double));
   if (gae_on(lambda)) {
     WindowStatsArgsGae wg;
     static_cast<WindowStatsArgs&>(wg) = w;
     wg.gl = w.gamma * lambda;
-    hipLaunchKernelGGL(window_stats_kernel<true>, dim3(1), dim3(256), lds, s, wg, c, norm_sq, nparts, clip);
+    hipLaunchKernelGGL(window_stats_kernel<true>, dim3(1), dim3(256), lds, s, wg, c, u.norm_sq, u.nparts, u.clip);
   } else {
-    hipLaunchKernelGGL(window_stats_kernel<false>, dim3(1), dim3(256), lds, s, w, c, norm_sq, nparts, clip);
+    hipLaunchKernelGGL(window_stats_kernel<false>, dim3(1), dim3(256), lds, s, w, c, u.norm_sq, u.nparts, u.clip);
   }
   return hipGetLastError();
 }
 
-hipError_t launch_rmsprop(float* p, float* ms, const float* g, int64_t n, double lr, double alpha, double eps,
-                          const double* norm_sq, int nparts, float clip, const int64_t* ctl,
-                          int64_t total_steps, int64_t n_total, int t_max, hipStream_t s, const AdvanceArgs* adv,
-                          const DecayArgs* wd) {
-  if (wd != nullptr && (wd->n_bias < 0 || wd->n_bias > DECAY_MAX_BIAS)) return hipErrorInvalidValue;
-  if (norm_sq != nullptr && (nparts < 1 || nparts > NORM_MAX_PARTS)) return hipErrorInvalidValue;
+// What launch_rmsprop and launch_adam share: the checks, the empty array, and the choice of the instantiation.
+// launch(adv, wd) issues the optimizer's kernel(s) for wd, a DecayArgs or NoDecay{}, and returns their status.
+template <class Launch>
+static hipError_t launch_update(int64_t n, const UpdateArgs& u, Launch&& launch) {
+  if (u.wd != nullptr && (u.wd->n_bias < 0 || u.wd->n_bias > DECAY_MAX_BIAS)) return hipErrorInvalidValue;
+  if (u.norm_sq != nullptr && (u.nparts < 1 || u.nparts > NORM_MAX_PARTS)) return hipErrorInvalidValue;
   if (n <= 0) return hipSuccess;
-  const RmsConst c = rms_const(lr, alpha, eps, ctl, total_steps, n_total, t_max, adv != nullptr && adv->ctl != nullptr);
-  AdvanceArgs a{};
-  if (adv != nullptr) a = *adv;
-  if (wd != nullptr && wd->rate != 0.f)
-    hipLaunchKernelGGL(rmsprop_kernel<DecayArgs>, dim3(stream_blocks(n)), dim3(256), 0, s, p, ms, g, n, c, norm_sq, nparts,
-                       clip, a, *wd);
-  else
-    hipLaunchKernelGGL(rmsprop_kernel<NoDecay>, dim3(stream_blocks(n)), dim3(256), 0, s, p, ms, g, n, c, norm_sq, nparts,
-                       clip, a, NoDecay{});
-  return hipGetLastError();
+  AdvanceArgs adv{};
+  if (u.adv != nullptr) adv = *u.adv;
+  if (u.wd != nullptr && u.wd->rate != 0.f) return launch(adv, *u.wd);
+  return launch(adv, NoDecay{});
+}
+
+hipError_t launch_rmsprop(float* p, float* ms, const float* g, int64_t n, double lr, double alpha, double eps,
+                          const UpdateArgs& u, hipStream_t s) {
+  const RmsConst c = rms_const(lr, alpha, eps, u);
+  return launch_update(n, u, [&](const AdvanceArgs& adv, auto wd) {
+    hipLaunchKernelGGL(rmsprop_kernel<decltype(wd)>, dim3(stream_blocks(n)), dim3(256), 0, s, p, ms, g, n, c, u.norm_sq,
+                       u.nparts, u.clip, adv, wd);
+    return hipGetLastError();
+  });
 }
 
 // ad.tctl null: lr_t for the host's ad.t from the host's libm, in Python's order (bit-identical to Adam.lr)
-static AdamConst adam_const(double lr, double eps, const AdamArgs& ad, const int64_t* ctl, int64_t total_steps,
-                            int64_t n_total, int t_max, bool advance) {
+static AdamConst adam_const(double lr, double eps, const AdamArgs& ad, const UpdateArgs& u) {
   AdamConst a;
-  a.lr = rms_const(lr, 0.0, 0.0, ctl, total_steps, n_total, t_max, advance);
+  a.lr = rms_const(lr, 0.0, 0.0, u);
   a.c1 = (float)(1.0 - ad.beta1);
   a.c2 = (float)(1.0 - ad.beta2);
   a.eps = (float)eps;
@@ -623,28 +585,19 @@ static AdamConst adam_const(double lr, double eps, const AdamArgs& ad, const int
 }
 
 hipError_t launch_adam(float* p, float* m, float* v, const float* g, int64_t n, double lr, double eps,
-                       const AdamArgs& ad, const double* norm_sq, int nparts, float clip, const int64_t* ctl,
-                       int64_t total_steps, int64_t n_total, int t_max, hipStream_t s, const AdvanceArgs* adv,
-                       const DecayArgs* wd) {
-  if (wd != nullptr && (wd->n_bias < 0 || wd->n_bias > DECAY_MAX_BIAS)) return hipErrorInvalidValue;
-  if (norm_sq != nullptr && (nparts < 1 || nparts > NORM_MAX_PARTS)) return hipErrorInvalidValue;
+                       const AdamArgs& ad, const UpdateArgs& u, hipStream_t s) {
   if (ad.tctl == nullptr && ad.t < 1) return hipErrorInvalidValue;
-  if (n <= 0) return hipSuccess;
-  const AdamConst a = adam_const(lr, eps, ad, ctl, total_steps, n_total, t_max, adv != nullptr && adv->ctl != nullptr);
-  AdvanceArgs av{};
-  if (adv != nullptr) av = *adv;
-  if (ad.tctl != nullptr) {   // count the update (and, with a window record, note its lr_t) ahead of the kernel
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, s, ad.tctl, a, ad.stats_log, ad.stats_count);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  if (wd != nullptr && wd->rate != 0.f)
-    hipLaunchKernelGGL(adam_kernel<DecayArgs>, dim3(stream_blocks(n)), dim3(256), 0, s, p, m, v, g, n, a, norm_sq, nparts,
-                       clip, av, *wd);
-  else
-    hipLaunchKernelGGL(adam_kernel<NoDecay>, dim3(stream_blocks(n)), dim3(256), 0, s, p, m, v, g, n, a, norm_sq, nparts,
-                       clip, av, NoDecay{});
-  return hipGetLastError();
+  return launch_update(n, u, [&](const AdvanceArgs& adv, auto wd) {
+    const AdamConst a = adam_const(lr, eps, ad, u);
+    if (ad.tctl != nullptr) {   // count the update (and, with a window record, note its lr_t) ahead of the kernel
+      hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, s, ad.tctl, a, ad.stats_log, ad.stats_count);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(adam_kernel<decltype(wd)>, dim3(stream_blocks(n)), dim3(256), 0, s, p, m, v, g, n, a, u.norm_sq,
+                       u.nparts, u.clip, adv, wd);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_ctl_write(int64_t* ctl, int idx, int64_t value, hipStream_t s) {

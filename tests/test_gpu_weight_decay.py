@@ -54,8 +54,10 @@ def _arrays(n, gscale=1.0):
     return p, ms, g
 
 
-# tail only, tail of 3, one exact float4, float4 + tail, more than one block (1027 = 256 float4 + 1 float4 + 3)
-@pytest.mark.parametrize("n", [1, 3, 4, 5, 1027])
+# tail only, tail of 3, one exact float4, float4 + tail, more than one block (1027 = 256 float4 + 1 float4 + 3);
+# the last: one full pass of the launch's cap (2,048 x 256 float4), so that threads take a second pass (the
+# loop's reload branch), plus a float4 and a tail of 3
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 1027, 2048 * 256 * 4 + 1027])
 def test_update_arrays_decay_bit_exact(gpu, n):
     p, ms, g = _arrays(n)
     opt = _opt(rate=RATE)
