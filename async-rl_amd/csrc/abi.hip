@@ -306,6 +306,12 @@ static int ring_args(arl_net* h, int t, const uint8_t* pool, const float* reward
   a.reward_pool = reward_pool;
   a.done_pool = done_pool;
   a.pool_len = pool_len;
+  // the kernels reduce the step counter by pool_len through these constants (divisors below 2^31); without
+  // any pool (a bookkeeping-only stack observation) no pool entry is read and the divisor is immaterial
+  const bool any_pool = pool || reward_pool || done_pool;
+  if (any_pool && pool_len > INT32_MAX) return fail(ARL_EINVAL, "observe: pool_len above 2^31 - 1");
+  a.dpool = arl::fd_make(any_pool ? (uint32_t)pool_len : 1u);
+  a.dR = n.dR;
   a.frames = n.at<uint8_t>(n.w_frames);
   a.nvalid = n.at<uint8_t>(n.w_nvalid);
   a.reset_flags = n.at<uint8_t>(n.w_reset);

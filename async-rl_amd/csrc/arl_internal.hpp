@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+#include "fastdiv.hpp"
+
 namespace arl {
 
 // control block (device int64[16]), read by kernels so that a captured window
@@ -28,11 +30,22 @@ constexpr int ARCH_STACK = 32;
 // convs run on the generic implicit-GEMM template (states.hip)
 constexpr int ARCH_STATES = 64;
 // frame layout of the ring, as the conv kernels read it (conv input plane c of window step t):
+// (the kernels reduce the device counter once, rs = k mod R through the host's FastDiv of R, and wrap
+// window-local offsets such as rs + R - 3 + c with a compare and subtract: no runtime-divisor % in device code)
 //   FRAMES_RING  one screen per slot, plane c = slot (k - 3 + c) % R   (k = ctl[STEP] + t)
 //   FRAMES_RGB   three planes per slot [0, R, G, B] of slot k % R
 //   FRAMES_STACK four planes per slot, plane c of slot k % R
 //   FRAMES_STATES four f32 planes per slot (ARCH_STATES), plane c of slot k % R
 enum FrameLayout { FRAMES_RING = 0, FRAMES_RGB = 1, FRAMES_STACK = 2, FRAMES_STATES = 3 };
+// index (in 84 x 84 planes) of conv input plane c of env e at the obs step in ring slot rs = k mod R, for the three
+// uint8 layouts; selects only, so the four plane loads of a thread go out back to back (RGB: plane 0 is the
+// zero pad and re-reads plane 1's bytes, which the caller zeroes through nvalid = 3)
+__device__ inline int64_t ring_plane(int layout, int rs, int R, int n, int e, int c) {
+  const int slot = layout == FRAMES_RING ? fd_wrap(rs + R - 3 + c, R) : rs;
+  const int mult = layout == FRAMES_STACK ? 4 : layout == FRAMES_RGB ? 3 : 1;
+  const int sub = layout == FRAMES_STACK ? c : layout == FRAMES_RGB ? (c > 0 ? c - 1 : 0) : 0;
+  return ((int64_t)slot * n + e) * mult + sub;
+}
 
 constexpr int PLANE = 84 * 84;         // 7056 B per screen
 constexpr int PAIR = 2 * 210 * 160 * 3; // 201,600 B per frame pair
@@ -57,6 +70,8 @@ struct RingArgs {
   const float* reward_pool;   // (pool_len, n) or null
   const uint8_t* done_pool;   // (pool_len, n) or null
   int64_t pool_len;
+  FastDiv dpool, dR;          // pool_len and R as divisors of the step counter (fastdiv.hpp), filled by the host
+  FastDiv dchunks;            // RGB nets: 16-byte chunks of a source row, W * 3 / 16 (launch_rgb_ring fills it)
   uint8_t* frames;            // (R, n, 84, 84)
   uint8_t* nvalid;            // (R, n)
   uint8_t* reset_flags;       // (T+1, n)
@@ -166,6 +181,7 @@ struct Stamps {
 
 struct Net {
   int arch, A, N, T, R;
+  FastDiv dR, dN;             // R and N as device-side divisors (net_init)
   Stamps* stamps = nullptr;   // null / off: stamp() is a no-op
   bool rgb = false;        // ARCH_RGB: 3 planes per obs step in the ring, conv1 W (16, 3, 8, 8)
   bool stack = false;      // ARCH_STACK: 4 planes (a whole stack) per obs step in the ring
@@ -310,7 +326,8 @@ hipError_t launch_heads_bwd(const float* dl, const float* dv, const float* Wpi, 
                             const float* mask, float* out, int64_t S, hipStream_t s);
 
 // layout: FrameLayout of the ring (FRAMES_RGB: conv1 W (16, 3, 8, 8) on input planes 1..3)
-hipError_t launch_conv_fwd(const uint8_t* frames, const uint8_t* nvalid, const int64_t* ctl, int n, int R, int t,
+hipError_t launch_conv_fwd(const uint8_t* frames, const uint8_t* nvalid, const int64_t* ctl, int n, const FastDiv& R,
+                           int t,
                            const float* W1, const float* b1, const float* W2, const float* b2, float* a1, float* a2,
                            hipStream_t s, int layout = FRAMES_RING, int e0 = 0, int ne = -1, uint32_t* a2m = nullptr);
 // the gradient's squared norm folded into the conv slab reduce (parts == null: not folded)
@@ -321,7 +338,8 @@ struct NormFold {
   int rest_blocks;
 };
 int conv_norm_parts(int rest_blocks);
-hipError_t launch_conv_bwd(const uint8_t* frames, const uint8_t* nvalid, const int64_t* ctl, int n, int R, int S,
+hipError_t launch_conv_bwd(const uint8_t* frames, const uint8_t* nvalid, const int64_t* ctl, const FastDiv& n,
+                           const FastDiv& R, int S,
                            const float* a1, const float* da2, const float* W2, float* slab, float* gW2, float* gb2,
                            float* gW1, float* gb1, hipStream_t s, bool reduce = true, int layout = FRAMES_RING,
                            const NormFold& nf = NormFold{});

@@ -97,10 +97,13 @@ struct ConvBwdArgs {
   const uint8_t* nvalid;
   const int64_t* ctl;
   int n, R;
+  FastDiv dn, dR;      // n and R as divisors (fastdiv.hpp): a workgroup's first sample -> (step, env); ctl[STEP] mod R
   const float* a1;     // (S, 16, 400)
   const float* da2;    // (S, 32, 81), already masked by a2 > 0
   const float* W2;     // (32, 16, 4, 4)
   int S, G;            // samples; workgroups (workgroup b: samples b, b + G, ...)
+  int Sq, Sr;          // S / G, S % G: workgroup b has Sq + (b < Sr) samples
+  int Gq, Gr;          // G / n, G % n: the (step, env) stride between a workgroup's samples
   float* slab;         // (G, SLAB)
   int layout;          // FrameLayout (FRAMES_RGB: (R, n, 3, 84, 84), planes [0, R, G, B];
                        // FRAMES_STACK: (R, n, 4, 84, 84))
@@ -144,11 +147,27 @@ __device__ inline void prefetch_a(const ConvBwdArgs& a, int s, PrefetchA& r) {
 // dwords 4q..4q+3 of the row on threads 0..503; q = 5 holds the row's last
 // dword (20), loaded as dwords 17..20 so no read passes the row.  The plane
 // base is uniform (scalar address + one offset VGPR per item).
-__device__ inline void prefetch_x(const ConvBwdArgs& a, int64_t step0, int s, PrefetchX& r) {
+// The ring slots of a sample without a division in the per-sample loop: sample s = t * n + e is carried as
+// (s, t, e) and stepped by the workgroup's stride G = Gq * n + Gr with one carry; r0 = ctl[STEP] mod R is reduced
+// once per workgroup; the sample's slot (r0 + t < 2 R) and the three planes before it (rs + R - 3 + c < 2 R)
+// wrap with a compare and subtract.
+struct Sample {
+  int s, t, e;
+};
+__device__ inline Sample sample_first(const ConvBwdArgs& a, int s) {
+  const int t = (int)fd_div32(a.dn, (uint32_t)s);
+  return Sample{s, t, s - t * a.n};
+}
+__device__ inline Sample sample_next(const ConvBwdArgs& a, const Sample& c) {   // s + G
+  const int e = c.e + a.Gr;
+  const bool carry = e >= a.n;
+  return Sample{c.s + a.G, c.t + a.Gq + (carry ? 1 : 0), carry ? e - a.n : e};
+}
+
+__device__ inline void prefetch_x(const ConvBwdArgs& a, int r0, const Sample& sm, PrefetchX& r) {
   const int tid = threadIdx.x;
-  const int t = s / a.n, e = s - t * a.n;
-  const int64_t ks = step0 + t;
-  const int rs = (int)(ks % a.R);
+  const int e = sm.e;
+  const int rs = fd_wrap(r0 + sm.t, a.R);
   // a lane-varying address keeps the load a vector load that nothing waits
   // for until commit_x broadcasts lane 0 (a uniform one would be moved to an
   // SGPR right after the load, i.e. waited for at once)
@@ -158,9 +177,7 @@ __device__ inline void prefetch_x(const ConvBwdArgs& a, int64_t step0, int s, Pr
   const int off = y * 84 + (q < 5 ? 16 * q : 68);
 #pragma unroll
   for (int c = 0; c < PX; ++c) {
-    const int64_t pl = a.layout == FRAMES_STACK ? ((int64_t)rs * a.n + e) * 4 + c
-                       : a.layout == FRAMES_RGB ? ((int64_t)rs * a.n + e) * 3 + (c > 0 ? c - 1 : 0)
-                                                : (int64_t)((rs + a.R - 3 + c) % a.R) * a.n + e;
+    const int64_t pl = ring_plane(a.layout, rs, a.R, a.n, e, c);
     const uint32_t* src = reinterpret_cast<const uint32_t*>(a.frames + pl * PLANE + off);
     r.x[c] = make_uint4(src[0], src[1], src[2], src[3]);
   }
@@ -312,10 +329,11 @@ conv_bwd_kernel(ConvBwdArgs a) {
   const int G = a.G;
   PrefetchA pa;
   PrefetchX px_;
-  const int64_t step0 = a.ctl[CTL_STEP];
   prefetch_a(a, blockIdx.x, pa);
-  prefetch_x(a, step0, blockIdx.x, px_);
   dma_a1(a, blockIdx.x, lds);
+  Sample sm = sample_first(a, blockIdx.x);
+  const int r0 = (int)fd_mod64(a.dR, (uint64_t)a.ctl[CTL_STEP]);   // after the loads that do not need it
+  prefetch_x(a, r0, sm, px_);
   for (int s = blockIdx.x; s < a.S; s += G) {
     lds_barrier();                 // B0: the previous sample is done with every region
     commit_a(pa, lds, b2a);
@@ -323,9 +341,11 @@ conv_bwd_kernel(ConvBwdArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this sample's a1 DMA has landed
     lds_barrier();                 // B1
     {
-      const int sn = min(s + G, a.S - 1);   // unconditional: the registers are redefined here
-      prefetch_a(a, sn, pa);                // in flight during (1)-(3)
-      prefetch_x(a, step0, sn, px_);
+      // unconditional: the registers are redefined here (past the workgroup's last sample: that sample again,
+      // a valid address whose data nothing reads)
+      if (s + G < a.S) sm = sample_next(a, sm);
+      prefetch_a(a, sm.s, pa);              // in flight during (1)-(3)
+      prefetch_x(a, r0, sm, px_);
     }
     // ---- (1) conv2 weight gradient; wave w: n-tiles (ic) 2w, 2w+1 x both m-tiles.  k-step ks, lane
     // (col, g): positions p = 32 ks + 8 g + j, j = 0..7.  A: da2 planes row oc = 16 mt + col, one b128 a
@@ -573,19 +593,17 @@ __device__ inline void commit_d2_da(const float (&r)[8], uint8_t* lds, int ty, f
 }
 
 // prefetch_x with the Y thread index ty (0..511); r0 = the window's first step modulo the ring length
-__device__ inline void prefetch_x_ws(const ConvBwdArgs& a, int r0, int s, int ty_, PrefetchX& r) {
+__device__ inline void prefetch_x_ws(const ConvBwdArgs& a, int r0, const Sample& sm, int ty_, PrefetchX& r) {
   const int ty = opaque(ty_);
-  const int t = s / a.n, e = s - t * a.n;
-  const int rs = (r0 + t) % a.R;
+  const int e = sm.e;
+  const int rs = fd_wrap(r0 + sm.t, a.R);
   r.nv = a.nvalid[(int64_t)rs * a.n + min(e + (ty & 63), a.n - 1)];
   const int it = ty < 504 ? ty : 0;
   const int y = it / 6, q = it - 6 * (it / 6);
   const int off = y * 84 + (q < 5 ? 16 * q : 68);
 #pragma unroll
   for (int c = 0; c < PX; ++c) {
-    const int64_t pl = a.layout == FRAMES_STACK ? ((int64_t)rs * a.n + e) * 4 + c
-                       : a.layout == FRAMES_RGB ? ((int64_t)rs * a.n + e) * 3 + (c > 0 ? c - 1 : 0)
-                                                : (int64_t)((rs + a.R - 3 + c) % a.R) * a.n + e;
+    const int64_t pl = ring_plane(a.layout, rs, a.R, a.n, e, c);
     const uint32_t* src = reinterpret_cast<const uint32_t*>(a.frames + pl * PLANE + off);
     r.x[c] = make_uint4(src[0], src[1], src[2], src[3]);
   }
@@ -669,9 +687,8 @@ conv_bwd_ws_kernel(ConvBwdArgs a) {
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: SGPR values
   const int g = lane >> 4, col = lane & 15;
-  const int b = blockIdx.x, G = a.G;
-  const int n = (a.S - 1 - b) / G + 1;   // samples b, b + G, ... of this workgroup
-  auto smp = [&](int k) { return b + min(k, n - 1) * G; };
+  const int b = blockIdx.x;
+  const int n = a.Sq + (b < a.Sr ? 1 : 0);   // samples b, b + G, ... of this workgroup: (S - 1 - b) / G + 1
   // zero once: the da2 [oc][p] planes (positions past 80 stay 0) and the 4 rows after a1 channel 15; the
   // da1 pad columns X 20..23 after the W2 staging (below)
   for (int i = tid; i < 3 * DAP / 16; i += NT2) reinterpret_cast<uint4*>(lds + LW_DA)[i] = make_uint4(0, 0, 0, 0);
@@ -819,10 +836,11 @@ conv_bwd_ws_kernel(ConvBwdArgs a) {
     float pa[8];
     PrefetchX pxr;
     CB_STAMP(1, 15, 0);
-    dma_a1_wave(a, smp(0), lds, wy, lane);
-    load_da2(a, smp(0), ty, pa);
-    const int r0 = (int)(a.ctl[CTL_STEP] % a.R);   // after the loads that do not need it
-    prefetch_x_ws(a, r0, smp(0), ty, pxr);
+    dma_a1_wave(a, b, lds, wy, lane);
+    load_da2(a, b, ty, pa);
+    Sample sm = sample_first(a, b);   // the sample the prefetches are at: s_0, then s_{k+1} in P_k / Q_k
+    const int r0 = (int)fd_mod64(a.dR, (uint64_t)a.ctl[CTL_STEP]);   // after the loads that do not need it
+    prefetch_x_ws(a, r0, sm, ty, pxr);
     CB_STAMP(1, 15, 1);
     lds_barrier();   // #0
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -834,16 +852,17 @@ conv_bwd_ws_kernel(ConvBwdArgs a) {
     for (int k = 0; k < n; ++k) {
       // ---- P_k
       CB_STAMP(1, k, 0);
-      load_da2(a, smp(k + 1), ty, pa);   // for Q_k
+      if (k + 1 < n) sm = sample_next(a, sm);   // (after the last sample: that sample again, nothing reads it)
+      load_da2(a, sm.s, ty, pa);   // for Q_k
       commit_x_ws(pxr, lds, ty);
       step1_wave(lds, wy, lane, acc1);
-      prefetch_x_ws(a, r0, smp(k + 1), ty, pxr);   // after (1): its registers are not live across it
+      prefetch_x_ws(a, r0, sm, ty, pxr);   // after (1): its registers are not live across it
       CB_STAMP(1, k, 1);
       lds_barrier();
       // ---- Q_k
       CB_STAMP(1, k, 2);
       if (k + 1 < n) {
-        dma_a1_wave(a, smp(k + 1), lds, wy, lane);
+        dma_a1_wave(a, sm.s, lds, wy, lane);
         commit_d2_da(pa, lds, ty, b2a);
         CB_STAMP(1, k, 5);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // a1 of s_{k+1} has landed
@@ -956,12 +975,13 @@ static_assert(RED_BLOCKS + 64 <= NORM_MAX_PARTS, "the folded norm's partials fit
 int conv_bwd_blocks(int S) { return S < 256 ? S : 256; }
 int64_t conv_bwd_slab_floats(int S) { return (int64_t)conv_bwd_blocks(S) * SLAB; }
 
-hipError_t launch_conv_bwd(const uint8_t* frames, const uint8_t* nvalid, const int64_t* ctl, int n, int R, int S,
-                           const float* a1, const float* da2, const float* W2, float* slab, float* gW2, float* gb2,
+hipError_t launch_conv_bwd(const uint8_t* frames, const uint8_t* nvalid, const int64_t* ctl, const FastDiv& n,
+                           const FastDiv& R, int S, const float* a1, const float* da2, const float* W2, float* slab, float* gW2, float* gb2,
                            float* gW1, float* gb1, hipStream_t s, bool reduce, int layout, const NormFold& nf) {
   if (S <= 0) return hipSuccess;
   const int G = conv_bwd_blocks(S);
-  ConvBwdArgs a{frames, nvalid, ctl, n, R, a1, da2, W2, S, G, slab, layout};
+  const int ni = (int)n.d;
+  ConvBwdArgs a{frames, nvalid, ctl, ni, (int)R.d, n, R, a1, da2, W2, S, G, S / G, S % G, G / ni, G % ni, slab, layout};
   static const char* ws = getenv("ARL_CB_WS");   // "0": the 512-thread kernel (the bitwise test arm)
   if (ws != nullptr && ws[0] == '0')
     hipLaunchKernelGGL(conv_bwd_kernel, dim3(G), dim3(NT), 0, s, a);

@@ -85,7 +85,8 @@ struct ConvFwdArgs {
   const uint8_t* frames;
   const uint8_t* nvalid;
   const int64_t* ctl;
-  int n, R, t;          // obs step = ctl[STEP] + t; env = blockIdx.x
+  int n, t;             // obs step = ctl[STEP] + t; env = blockIdx.x
+  FastDiv R;            // the ring length as the divisor of the obs step (fastdiv.hpp)
   const float* W1;      // (16, 4, 8, 8); RGB nets (16, 3, 8, 8) for input planes 1..3
   const float* b1;
   const float* W2;      // (32, 16, 4, 4)
@@ -162,6 +163,9 @@ __global__ void __launch_bounds__(NT * EPW)
 conv_fwd_kernel(ConvFwdArgs a) {
   using LY = Lay<EPW>;
   __shared__ __attribute__((aligned(16))) uint8_t lds[LY::END];
+  // the step counter's load goes out first: its round trip bounds the prologue's dependent chain (ring slot ->
+  // nvalid -> screens), and everything up to its first use below is issued underneath it
+  const int64_t step = a.ctl[CTL_STEP];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, col = lane & 15;
@@ -180,8 +184,32 @@ conv_fwd_kernel(ConvFwdArgs a) {
   // conv2 runs transposed too (mfma_x6_t): lane (g, col) holds oc 16 nt + 4 g + r of position 16 m + col
   const float bias2[4] = {a.b2[16 * (w8 & 1) + 4 * g], a.b2[16 * (w8 & 1) + 4 * g + 1], a.b2[16 * (w8 & 1) + 4 * g + 2],
                           a.b2[16 * (w8 & 1) + 4 * g + 3]};
-  const int64_t ks = a.ctl[CTL_STEP] + a.t;
-  const int rs = (int)(ks % a.R);
+  // the weights next (EPW = 2: slot 0 loads (and splits) W1 only, slot 1 W2 only, wave-uniform): like the
+  // biases they do not depend on the step counter, so they are in flight while its load returns
+  float4 w1a, w1b, w2v[4];
+  if (EPW == 1 || el == 0) w1_load(a.W1, rgb, t8, w1a, w1b);
+  if (EPW == 1 || el == 1) w2_load(a.W2, t8, w2v);
+  // ring slot of the obs step: the device counter reduced by the host's constants of R (straight-line
+  // scalar code); the planes before it wrap with a compare (rs + R - 3 + c < 2 R)
+  const int R = (int)a.R.d;
+  const int rs = (int)fd_mod64(a.R, (uint64_t)(step + a.t));
+  // ---- stage: every global load in flight at once (the weights above, nvalid, all
+  // four ring planes whatever nvalid says, back to back once rs is known), then bf16
+  // conversion / splitting into LDS; planes older than the last reset are zeroed there
+  int nv = a.nvalid[(int64_t)rs * a.n + e];
+  constexpr int NX = (4 * V + NT - 1) / NT;  // 4
+  uint4 xv[NX];
+#pragma unroll
+  for (int j = 0; j < NX; ++j) {
+    const int i = t8 + NT * j;
+    // past the fourth plane: reload its last 16 bytes (every thread issues NX loads)
+    const int c = i < 4 * V ? i / V : 3, oo = i < 4 * V ? i - c * V : V - 1;
+    // RGB: conv plane 0 is the zero pad (c - 1 < 0 reads plane 0 and is zeroed below, nvalid = 3)
+    xv[j] = reinterpret_cast<const uint4*>(a.frames + ring_plane(a.layout, rs, R, a.n, e, c) * PLANE)[oo];
+  }
+  // nvalid's first use stays below the screen loads (the scheduler otherwise lifts 4 - nv between them, and
+  // the wait for it -- vmcnt(0), the weights included -- holds the remaining screen loads back)
+  asm volatile("" : "+v"(nv) : : "memory");
   // conv1 tiles w, w + 8, w + 16 (and 24 on wave 0): 25 tiles over 8 waves in one
   // pass, 3-4 independent accumulator chains per wave (per-tile k order s = 0..7)
   constexpr int TJ = 4;
@@ -220,27 +248,7 @@ conv_fwd_kernel(ConvFwdArgs a) {
     wm = lds_load<bf16x8>(lds, off + W1P);
     wl = lds_load<bf16x8>(lds, off + 2 * W1P);
   };
-  // ---- stage: every global load in flight at once (nvalid, the weights, all
-  // four ring planes whatever nvalid says), then bf16 conversion / splitting
-  // into LDS; planes older than the last reset are zeroed here
-  const int nv = a.nvalid[(int64_t)rs * a.n + e];
-  // EPW = 2: slot 0 loads (and splits) W1 only, slot 1 W2 only (wave-uniform)
-  float4 w1a, w1b, w2v[4];
-  if (EPW == 1 || el == 0) w1_load(a.W1, rgb, t8, w1a, w1b);
-  if (EPW == 1 || el == 1) w2_load(a.W2, t8, w2v);
-  constexpr int NX = (4 * V + NT - 1) / NT;  // 4
-  uint4 xv[NX];
-#pragma unroll
-  for (int j = 0; j < NX; ++j) {
-    const int i = t8 + NT * j;
-    // past the fourth plane: reload its last 16 bytes (every thread issues NX loads)
-    const int c = i < 4 * V ? i / V : 3, oo = i < 4 * V ? i - c * V : V - 1;
-    // RGB: conv plane 0 is the zero pad (c - 1 < 0 reads plane 0 and is zeroed below, nvalid = 3)
-    xv[j] = reinterpret_cast<const uint4*>(
-        a.frames + (a.layout == FRAMES_STACK ? ((int64_t)rs * a.n + e) * 4 + c
-                    : a.layout == FRAMES_RGB ? ((int64_t)rs * a.n + e) * 3 + (c > 0 ? c - 1 : 0)
-                                             : (int64_t)((rs + a.R - 3 + c) % a.R) * a.n + e) * PLANE)[oo];
-  }
+  // ---- the loads above -> LDS
 #pragma unroll
   for (int j = 0; j < NX; ++j) {
     const int i = t8 + NT * j;
@@ -362,13 +370,13 @@ conv_fwd_kernel(ConvFwdArgs a) {
   }
 }
 
-hipError_t launch_conv_fwd(const uint8_t* frames, const uint8_t* nvalid, const int64_t* ctl, int n, int R, int t,
-                           const float* W1, const float* b1, const float* W2, const float* b2, float* a1, float* a2,
+hipError_t launch_conv_fwd(const uint8_t* frames, const uint8_t* nvalid, const int64_t* ctl, int n, const FastDiv& R,
+                           int t, const float* W1, const float* b1, const float* W2, const float* b2, float* a1, float* a2,
                            hipStream_t s, int layout, int e0, int ne, uint32_t* a2m) {
   if (n <= 0) return hipSuccess;
   if (ne < 0) ne = n;
   if (ne <= 0) return hipSuccess;
-  ConvFwdArgs a{frames, nvalid, ctl, n, R, t, W1, b1, W2, b2, a1, a2, layout, e0, e0 + ne, a2m};
+  ConvFwdArgs a{frames, nvalid, ctl, n, t, R, W1, b1, W2, b2, a1, a2, layout, e0, e0 + ne, a2m};
   // two envs a workgroup (16 waves sharing the weight planes) in nets of >= 512 envs, whether the
   // launch covers all of them or one env group's range (C4 0.513 -> 0.503 ms, C3 1.227 -> 1.212 ms at
   // two groups, profiles/r03/r3k); ARL_CONV_EPW=1 / 2 forces one form (A/B timing)

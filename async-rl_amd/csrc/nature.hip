@@ -42,15 +42,17 @@ __device__ inline float phi_scale(uint32_t b) { return div255((float)b); }
 // (t - t0) * n + e (window step t, env e); m = s * 400 + p; k = ic*64 + ky*8 + kx.
 struct RingIm2col {
   const uint8_t* __restrict__ frames; const uint8_t* __restrict__ nvalid; const int64_t* __restrict__ ctl;
-  int n, R, t0;
+  FastDiv dn, dR; int t0;   // n and R as divisors (fastdiv.hpp): no runtime-divisor / or % per element
   // byte address of (m, k) with k % 4 == 0 handled by the caller; null = zero plane
   __device__ const uint8_t* addr(int m, int k) const {
+    const int n = (int)dn.d, R = (int)dR.d;
     const int s = m / NP1, p = m - s * NP1;
-    const int tt = s / n, e = s - tt * n;
-    const int rs = (int)((ctl[CTL_STEP] + t0 + tt) % R);
+    const int tt = (int)fd_div32(dn, (uint32_t)s), e = s - tt * n;
+    // the counter reduced once (uniform), then window-local offsets below 2 R: t0 + tt <= t_max = R - 4
+    const int rs = fd_wrap((int)fd_mod64(dR, (uint64_t)ctl[CTL_STEP]) + t0 + tt, R);
     const int ic = k >> 6;
     if (ic < 4 - (int)nvalid[(int64_t)rs * n + e]) return nullptr;
-    const int slot = (rs + R - 3 + ic) % R;
+    const int slot = fd_wrap(rs + R - 3 + ic, R);
     const int oy = p / 20, ox = p - oy * 20, ky = (k >> 3) & 7, kx = k & 7;
     return frames + ((int64_t)slot * n + e) * PLANE + (4 * oy + ky) * 84 + 4 * ox + kx;
   }
@@ -152,8 +154,8 @@ hipError_t conv1_fwd_ring(const Net& net, int t, float* a1, hipStream_t s) {
   const int n = net.N;
   const float* P = net.p;
   return launch_gemm<64, 32, 32, 2, 2, GK, GK>(
-      RingIm2col{net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid), net.at<int64_t>(net.w_ctl), n,
-                 net.R, t},
+      RingIm2col{net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid), net.at<int64_t>(net.w_ctl), net.dN,
+                 net.dR, t},
       WeightT{P + net.o_c1W, 256}, EpiConv{a1, P + net.o_c1b, NC1, NP1}, n * NP1, NC1, 256, 1, s);
 }
 
@@ -202,8 +204,8 @@ hipError_t conv_bwd(Net& net, hipStream_t s) {
                                                    EpiT2Class<NC1>{da1, a1, py, px}, S * 100, NC1, NC2 * 4, 1, s)));
   }
   // conv1: dW1 / db1 straight from the frame ring (the window's T steps)
-  RingIm2col ring{net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid), net.at<int64_t>(net.w_ctl), n,
-                  net.R, 0};
+  RingIm2col ring{net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid), net.at<int64_t>(net.w_ctl), net.dN,
+                  net.dR, 0};
   ARL_TRY((launch_gemm<32, 64, 32, 2, 2, GK, GM>(ConvDyT{da1, NC1, NP1}, OnesCol<RingIm2col>{ring, 256},
                                                  EpiSlab{slab, NC1, 257}, NC1, 257, S * NP1, pl.c1_w, s)));
   return launch_reduce_grad(slab, pl.c1_w, NC1, 257, MapDense{G, net.o_c1W, net.o_c1b, -1, 256}, s);

@@ -161,6 +161,7 @@ bool net_init(Net& net, int arch, int n_actions, int n_envs, int t_max, int env_
   if (t_max < 1 || t_max > 64) { err = "t_max must be in [1, 64]"; return false; }
   if ((int64_t)t_max * n_envs * C1_P >= (int64_t)1 << 31) { err = "t_max * n_envs too large"; return false; }
   net.arch = arch; net.A = n_actions; net.N = n_envs; net.T = t_max; net.R = t_max + 4;
+  net.dR = fd_make((uint32_t)net.R); net.dN = fd_make((uint32_t)net.N);
   net.env_offset = env_offset; net.seed = seed;
   const bool NAT = arch == ARCH_FF_NATURE;
   net.hid = NAT ? NHID : HID;
@@ -371,7 +372,7 @@ hipError_t net_act(Net& net, int t, int mode, hipStream_t s, int e0, int ne) {
     ARL_TRY(stamp(net, STAGE_CONV_FWD, s));
   } else if (!(part & ACT_AFTER_CONV)) {
     ARL_TRY(launch_conv_fwd(net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid),
-                            net.at<int64_t>(net.w_ctl), n, net.R, t, P + net.o_c1W, P + net.o_c1b, P + net.o_c2W,
+                            net.at<int64_t>(net.w_ctl), n, net.dR, t, P + net.o_c1W, P + net.o_c1b, P + net.o_c2W,
                             P + net.o_c2b, a1_bwd, a2, s, net.layout, e0, ne, mask_bwd));
     ARL_TRY(stamp(net, STAGE_CONV_FWD, s));
   }
@@ -503,7 +504,7 @@ static hipError_t conv_backward(Net& net, hipStream_t s, const NormFold& nf) {
   const int S = net.T * net.N;
   float* slab = net.at<float>(net.w_slab);
   ARL_TRY(launch_conv_bwd(net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid), net.at<int64_t>(net.w_ctl),
-                          net.N, net.R, S, net.at<float>(net.w_a1), net.at<float>(net.w_da2), net.p + net.o_c2W, slab,
+                          net.dN, net.dR, S, net.at<float>(net.w_a1), net.at<float>(net.w_da2), net.p + net.o_c2W, slab,
                           net.g + net.o_c2W, net.g + net.o_c2b, net.g + net.o_c1W, net.g + net.o_c1b, s,
                           /*reduce=*/false, net.layout));
   ARL_TRY(stamp(net, STAGE_CONV_BWD, s));
@@ -637,7 +638,7 @@ hipError_t net_stage(Net& net, int stage, int t, hipStream_t s) {
   switch (stage) {
     case STAGE_CONV_FWD:
       return launch_conv_fwd(net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid),
-                             net.at<int64_t>(net.w_ctl), n, net.R, t, P + net.o_c1W, P + net.o_c1b, P + net.o_c2W,
+                             net.at<int64_t>(net.w_ctl), n, net.dR, t, P + net.o_c1W, P + net.o_c1b, P + net.o_c2W,
                              P + net.o_c2b, net.at<float>(net.w_a1) + (int64_t)t * n * A1, a2 + (int64_t)t * n * A2,
                              s, net.layout, 0, -1, a2_mask(net, t));
     case STAGE_FC_FWD:   // as in net_act: FF (and the LSTM's XRED gate kernel) reduce the partials downstream
@@ -655,7 +656,7 @@ hipError_t net_stage(Net& net, int stage, int t, hipStream_t s) {
       return fc_backward(net, s);
     case STAGE_CONV_BWD:
       return launch_conv_bwd(net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid),
-                             net.at<int64_t>(net.w_ctl), n, net.R, S, net.at<float>(net.w_a1),
+                             net.at<int64_t>(net.w_ctl), net.dN, net.dR, S, net.at<float>(net.w_a1),
                              net.at<float>(net.w_da2), P + net.o_c2W, slab, G + net.o_c2W, G + net.o_c2b,
                              G + net.o_c1W, G + net.o_c1b, s, /*reduce=*/false, net.layout);
     case STAGE_RETURNS:   // the LEARN_RETURNS launch (returns + loss gradient + heads dh), default coefficients

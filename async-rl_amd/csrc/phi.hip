@@ -134,19 +134,20 @@ phi_stack_kernel(const uint8_t* __restrict__ pairs, const uint8_t* __restrict__ 
 // In-loop ring: the new screen of obs step k = ctl[0] + t goes to slot k % R;
 // nvalid[slot][e] = reset ? 1 : min(nvalid[prev slot][e] + 1, 4).  Also
 // ingests the reward / done that arrived with this obs (a3c.py:69-70,75):
-// rewards[t-1], dones[t-1] (t >= 1) and reset_flags[t].
+// rewards[t-1], dones[t-1] (t >= 1) and reset_flags[t].  Both residues (k mod R, k mod pool_len) come from
+// ring_slots (phi_ops.hpp): the host's FastDiv constants, no runtime-divisor % ahead of the frame loads; the
+// previous slot is slot + R - 1 wrapped with a compare.
 template <bool EP>   // EP: with the episode statistics (launched when a.episodes != null)
 __global__ void __launch_bounds__(256)
 phi_ring_kernel(RingArgs a) {
   __shared__ PhiShared sh;
   const int e = a.e0 + blockIdx.y;
   const int64_t k = a.ctl[CTL_STEP] + a.t;
-  const int slot = (int)(k % a.R);
-  const int64_t pidx = k % a.pool_len;
-  const uint8_t* pr = a.pair_pool + (pidx * a.n + e) * (int64_t)(2 * FRAME_BYTES);
-  uint8_t* dst = a.frames + ((int64_t)slot * a.n + e) * PLANE;
+  const RingSlots rs = ring_slots(a, k);
+  const uint8_t* pr = a.pair_pool + (rs.pidx * a.n + e) * (int64_t)(2 * FRAME_BYTES);
+  uint8_t* dst = a.frames + ((int64_t)rs.slot * a.n + e) * PLANE;
   phi_band(pr, pr + FRAME_BYTES, dst, blockIdx.x * BAND, a.mode, sh);
-  if (blockIdx.x == 0 && threadIdx.x == 0) ring_obs_store<EP>(a, e, k, ring_obs_load(a, e, k));
+  if (blockIdx.x == 0 && threadIdx.x == 0) ring_obs_store<EP>(a, e, k, rs.slot, ring_obs_load(a, e, rs));
 }
 
 // ---------------------------------------------------------------- RGB (Doom)
@@ -169,7 +170,8 @@ struct RgbCoef {
 // `pstride` bytes) or, with OUT_F32, f32 / 255 (plane stride 84*84 floats)
 template <bool OUT_F32>
 __device__ inline void rgb_band(const uint8_t* __restrict__ img, int H, int W, void* __restrict__ out,
-                                int64_t pstride, int dy0, int mode, RgbCoef& cf, uint8_t* rows) {
+                                int64_t pstride, int dy0, int mode, RgbCoef& cf, uint8_t* rows,
+                                const FastDiv& dchunks) {
   const int tid = threadIdx.x;
   if (tid < DST) {
     int o, a0, a1;
@@ -184,12 +186,13 @@ __device__ inline void rgb_band(const uint8_t* __restrict__ img, int H, int W, v
   // LDS-DMA (global_load_lds_dwordx4): chunk i = (row r, 16-byte column c)
   // lands at rows + 16 i, one 1 KB wave instruction at a time, all in flight
   // before the single wait
-  const int rb = W * 3, chunks = rb / 16;   // W % 16 == 0 (checked by the host)
+  // W % 16 == 0 (checked by the host); dchunks: the host's FastDiv of chunks (no runtime-divisor / per lane)
+  const int rb = W * 3, chunks = (int)dchunks.d;
   const int total = 2 * RGB_BAND * chunks, lane = tid & 63;
   for (int it = tid >> 6; it * 64 < total; it += 4) {
     const int i = it * 64 + lane;
     if (i < total) {
-      const int r = i / chunks, c = i - r * chunks;
+      const int r = (int)fd_div32(dchunks, (uint32_t)i), c = i - r * chunks;
       int sy = cf.yofs[r >> 1] + (r & 1);
       if (sy > H - 1) sy = H - 1;
       __builtin_amdgcn_global_load_lds(img + (size_t)sy * rb + 16 * c,
@@ -236,11 +239,12 @@ __device__ inline void rgb_band(const uint8_t* __restrict__ img, int H, int W, v
 
 // batched train_a3c_doom.phi: imgs (n, H, W, 3) -> out (n, 3, 84, 84) f32
 __global__ void __launch_bounds__(256)
-rgb_phi_kernel(const uint8_t* __restrict__ imgs, int H, int W, float* __restrict__ out, int mode) {
+rgb_phi_kernel(const uint8_t* __restrict__ imgs, int H, int W, float* __restrict__ out, int mode, FastDiv dchunks) {
   extern __shared__ __attribute__((aligned(16))) uint8_t rgb_rows[];
   __shared__ RgbCoef cf;
   const int64_t e = blockIdx.y;
-  rgb_band<true>(imgs + e * H * W * 3, H, W, out + e * 3 * PLANE, 0, blockIdx.x * RGB_BAND, mode, cf, rgb_rows);
+  rgb_band<true>(imgs + e * H * W * 3, H, W, out + e * 3 * PLANE, 0, blockIdx.x * RGB_BAND, mode, cf, rgb_rows,
+                 dchunks);
 }
 
 // In-loop ring for RGB nets: the 3 planes of obs step k go to slot k % R
@@ -253,11 +257,12 @@ rgb_ring_kernel(RingArgs a) {
   __shared__ RgbCoef cf;
   const int e = a.e0 + blockIdx.y;
   const int64_t k = a.ctl[CTL_STEP] + a.t;
-  const int slot = (int)(k % a.R);
-  const int64_t pidx = k % a.pool_len;
-  const uint8_t* img = a.pair_pool + (pidx * a.n + e) * (int64_t)a.H * a.W * 3;
+  const RingSlots rs = ring_slots(a, k);
+  const int slot = rs.slot;
+  const int64_t pidx = rs.pidx;
+  const uint8_t* img =a.pair_pool + (pidx * a.n + e) * (int64_t)a.H * a.W * 3;
   uint8_t* dst = a.frames + ((int64_t)slot * a.n + e) * 3 * PLANE;
-  rgb_band<false>(img, a.H, a.W, dst, PLANE, blockIdx.x * RGB_BAND, a.mode, cf, rgb_rows);
+  rgb_band<false>(img, a.H, a.W, dst, PLANE, blockIdx.x * RGB_BAND, a.mode, cf, rgb_rows, a.dchunks);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     const uint8_t d = a.done_pool ? a.done_pool[pidx * a.n + e] : 0;
     const bool rs = a.force_reset || d != 0;
@@ -284,8 +289,9 @@ __global__ void __launch_bounds__(256)
 stack_ring_kernel(RingArgs a) {
   const int e = a.e0 + blockIdx.x;
   const int64_t k = a.ctl[CTL_STEP] + a.t;
-  const int slot = (int)(k % a.R);
-  const int64_t pidx = k % a.pool_len;
+  const RingSlots rs = ring_slots(a, k);
+  const int slot = rs.slot;
+  const int64_t pidx = rs.pidx;
   if (a.pair_pool != nullptr) {
     const int64_t sb = (int64_t)4 * PLANE * a.esize;   // bytes per stack (uint8 screens / f32 states)
     const int V = (int)(sb / 16);                       // 1764 / 7056 uint4
@@ -472,15 +478,18 @@ hipError_t launch_stack_ring(const RingArgs& a, hipStream_t s) {
 }
 
 static size_t rgb_lds(int W) { return (size_t)2 * RGB_BAND * W * 3; }
+static FastDiv rgb_chunks(int W) { return fd_make((uint32_t)(W * 3 / 16)); }   // 16-byte chunks of a source row
 
 hipError_t launch_rgb_phi(const uint8_t* imgs, int64_t n, int H, int W, float* out, int mode, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(rgb_phi_kernel, dim3(RGB_NBANDS, (unsigned)n), dim3(256), rgb_lds(W), s, imgs, H, W, out,
-                     mode);
+                     mode, rgb_chunks(W));
   return hipGetLastError();
 }
 
-hipError_t launch_rgb_ring(const RingArgs& a, hipStream_t s) {
+hipError_t launch_rgb_ring(const RingArgs& a_, hipStream_t s) {
+  RingArgs a = a_;
+  a.dchunks = rgb_chunks(a.W);
   const dim3 grid(RGB_NBANDS, (unsigned)(a.ne < 0 ? a.n : a.ne));
   if (a.episodes != nullptr) hipLaunchKernelGGL(rgb_ring_kernel<true>, grid, dim3(256), rgb_lds(a.W), s, a);
   else hipLaunchKernelGGL(rgb_ring_kernel<false>, grid, dim3(256), rgb_lds(a.W), s, a);

@@ -93,9 +93,19 @@ struct RingObs {
   int nv;      // nvalid of this observation
   float r;
 };
-__device__ inline RingObs ring_obs_load(const RingArgs& a, int e, int64_t k) {
-  const int64_t pidx = k % a.pool_len;
-  const int pslot = (int)((k + a.R - 1) % a.R);
+// The two residues of an observation's step k = ctl[STEP] + t: its ring slot k mod R and its pool entry
+// k mod pool_len, through the host's FastDiv constants (straight-line scalar code; the kernels compute them
+// once and hand them on, the slot before wraps with a compare)
+struct RingSlots {
+  int slot;
+  int64_t pidx;
+};
+__device__ inline RingSlots ring_slots(const RingArgs& a, int64_t k) {
+  return RingSlots{(int)fd_mod64(a.dR, (uint64_t)k), (int64_t)fd_mod64(a.dpool, (uint64_t)k)};
+}
+__device__ inline RingObs ring_obs_load(const RingArgs& a, int e, const RingSlots& rs) {
+  const int64_t pidx = rs.pidx;
+  const int pslot = fd_wrap(rs.slot + a.R - 1, a.R);
   RingObs o;
   o.done = a.done_pool ? a.done_pool[pidx * a.n + e] : 0;
   o.r = (a.t >= 1 && a.reward_pool) ? a.reward_pool[pidx * a.n + e] : 0.f;
@@ -147,8 +157,7 @@ __device__ inline void episode_ingest(const RingArgs& a, int e, int64_t k, float
 }
 
 template <bool EP>
-__device__ inline void ring_obs_store(const RingArgs& a, int e, int64_t k, const RingObs& o) {
-  const int slot = (int)(k % a.R);
+__device__ inline void ring_obs_store(const RingArgs& a, int e, int64_t k, int slot, const RingObs& o) {
   a.nvalid[(int64_t)slot * a.n + e] = (uint8_t)o.nv;
   a.reset_flags[(int64_t)a.t * a.n + e] = (a.force_reset || o.done != 0) ? 1 : 0;
   if (a.t >= 1) {

@@ -29,11 +29,14 @@ namespace {
 // t0 + tt, env e), m = s * 400 + p, k = ic * 64 + ky * 8 + kx; the state of
 // obs step k sits in slot k % R (k = ctl[STEP] + t).
 struct StatesIm2col {
-  const float* __restrict__ frames; const int64_t* __restrict__ ctl; int n, R, t0;
+  const float* __restrict__ frames; const int64_t* __restrict__ ctl;
+  FastDiv dn, dR; int t0;   // n and R as divisors (fastdiv.hpp): no runtime-divisor / or % per element
   __device__ const float* addr(int m, int k) const {
+    const int n = (int)dn.d;
     const int s = m / C1_P, p = m - s * C1_P;
-    const int tt = s / n, e = s - tt * n;
-    const int slot = (int)((ctl[CTL_STEP] + t0 + tt) % R);
+    const int tt = (int)fd_div32(dn, (uint32_t)s), e = s - tt * n;
+    // the counter reduced once (uniform), then a window-local offset: t0 + tt <= t_max = R - 4
+    const int slot = fd_wrap((int)fd_mod64(dR, (uint64_t)ctl[CTL_STEP]) + t0 + tt, (int)dR.d);
     const int ic = k >> 6, ky = (k >> 3) & 7, kx = k & 7;
     const int oy = p / 20, ox = p - oy * 20;
     return frames + (((int64_t)slot * n + e) * 4 + ic) * PLANE + (4 * oy + ky) * 84 + 4 * ox + kx;
@@ -68,7 +71,7 @@ hipError_t states_conv_fwd(const Net& net, int t, float* a1, float* a2, hipStrea
   const int n = net.N;
   const float* P = net.p;
   ARL_TRY((launch_gemm<64, 16, 32, 4, 1, GK, GS>(
-      StatesIm2col{net.at<float>(net.w_frames), net.at<int64_t>(net.w_ctl), n, net.R, t}, WeightT{P + net.o_c1W, 256},
+      StatesIm2col{net.at<float>(net.w_frames), net.at<int64_t>(net.w_ctl), net.dN, net.dR, t}, WeightT{P + net.o_c1W, 256},
       EpiConv{a1, P + net.o_c1b, C1_OC, C1_P}, n * C1_P, C1_OC, 256, 1, s)));
   return launch_gemm<32, 32, 32, 2, 2, GS, GK>(Im2col<C1_OC, 20, 4, 2, 9>{a1}, WeightT{P + net.o_c2W, C1_OC * 16},
                                                EpiConv{a2, P + net.o_c2b, C2_OC, C2_P}, n * C2_P, C2_OC, C1_OC * 16, 1,
@@ -100,7 +103,7 @@ hipError_t states_conv_bwd(Net& net, hipStream_t s) {
                                                    s)));
   }
   // conv1: dW1 / db1 straight from the state ring (the window's T steps)
-  const StatesIm2col ring{net.at<float>(net.w_frames), net.at<int64_t>(net.w_ctl), n, net.R, 0};
+  const StatesIm2col ring{net.at<float>(net.w_frames), net.at<int64_t>(net.w_ctl), net.dN, net.dR, 0};
   ARL_TRY((launch_gemm<32, 64, 32, 2, 2, GK, GM>(ConvDyT{da1, C1_OC, C1_P}, OnesCol<StatesIm2col>{ring, 256},
                                                  EpiSlab{slab, C1_OC, 257}, C1_OC, 257, S * C1_P, pl.c1_w, s)));
   return launch_reduce_grad(slab, pl.c1_w, C1_OC, 257, MapDense{G, net.o_c1W, net.o_c1b, -1, 256}, s);
