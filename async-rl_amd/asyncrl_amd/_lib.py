@@ -109,6 +109,13 @@ SIGNATURES = {
     "arl_episode_stats": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "arl_net_set_window_stats": (c_int, [c_void_p, c_int]),
     "arl_window_stats_reset": (c_int, [c_void_p, c_void_p]),
+    "arl_catch_state_bytes": (c_i64, [c_i64]),
+    "arl_catch_reset": (c_int, [c_void_p, c_i64, c_int, c_u64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "arl_catch_step": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_int, c_u64, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
+    "arl_net_set_env": (c_int, [c_void_p, c_int, c_void_p]),
+    "arl_env_reset": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "arl_env_step": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
@@ -132,6 +139,8 @@ ACT_AFTER_CONV = 8
 ENV_GROUP_ALIGN = 32   # arl_observe_envs / arl_act_envs: e0 % ENV_GROUP_ALIGN == 0
 LEARN_RETURNS, LEARN_TRUNK, LEARN_CONV = range(3)
 POOL_FRAMES, POOL_REWARDS, POOL_DONES = range(3)   # arl_net_set_pool kinds
+ENV_CATCH = 1          # ARL_ENV_CATCH: arl_net_set_env kind, the device-resident Catch
+CATCH_STATE_INTS = 8   # int32 per env and half of its state: [bx, by, vx, px, episode, steps_in_episode, 0, 0]
 CTL_ADAM_T = 3         # ARL_CTL_ADAM_T: the control block's count of Adam updates made (buffer "ctl", int64[16])
 EPISODE_LOG = 8        # ARL_EPISODE_LOG: episodes per env the device-side episode log keeps
 # the 8 doubles of arl_episode_stats, in order

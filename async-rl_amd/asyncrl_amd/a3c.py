@@ -455,6 +455,11 @@ class A3C:
         capturable when first=False): T x (phi, forward, sample), bootstrap,
         learn, [all-reduce], clip + RMSProp, advance.
 
+        With a device env attached (net.set_env) every path also steps it
+        after each of the T sampled actions, on the stream of the chain that
+        sampled them, into the pool entry the next observation reads: the
+        pools are then written, and the loop runs without the host.
+
         env_groups=G > 1 splits the envs into G contiguous ranges whose T + 1
         forward steps run as independent chains on G streams (envs are
         independent until the learner sums their gradients); chain g starts
@@ -536,6 +541,13 @@ class A3C:
         net, T = self.net, self.t_max
         ev = None
         stagger = envs is not None   # env groups: chain g starts after chain g-1's first kernel
+
+        def env_step(t):
+            """An attached device env answers the actions of step t < T with the
+            pool entry the chain's next observation reads."""
+            if net.env is not None and t < T:
+                net.env_step(t, pair_pool, reward_pool, done_pool, pool_len, stream=stream, envs=envs)
+
         for t in range(T + 1):
             obs = t > 0 or first
             if stagger and ev is None:
@@ -545,12 +557,14 @@ class A3C:
                     ev = torch.cuda.Event()
                     ev.record(stream)
                     net.act(t, stream=stream, envs=envs)
+                    env_step(t)
                     yield ev
                     continue
                 net.act(t, mode=1 | ACT_CONV_ONLY, stream=stream, envs=envs)
                 ev = torch.cuda.Event()
                 ev.record(stream)
                 net.act(t, mode=1 | ACT_AFTER_CONV, stream=stream, envs=envs)
+                env_step(t)
                 yield ev
                 continue
             if obs:
@@ -558,6 +572,7 @@ class A3C:
                                 resize_mode=self.resize_mode, stream=stream, envs=envs)
             else:
                 net.act(t, stream=stream, envs=envs)
+            env_step(t)
             yield None
 
     def finish_window(self, stream=None, conv=None):

@@ -14,7 +14,10 @@ phi pre-stage is the GPU kernel, so the adapter stops at the raw frame pair:
   VecALE         N of them stepped by host worker threads (the emulator
                  releases the GIL in act()) into pinned host buffers, copied
                  to the device asynchronously, in the (n, 2, 210, 160, 3)
-                 uint8 / reward / terminal layout A3C.act takes.
+                 uint8 / reward / terminal layout A3C.act takes;
+  DeviceCatch    no emulator at all: a small game whose transition and render
+                 are one HIP kernel (csrc/catch.hip), so the loop env -> phi ->
+                 forward -> sample -> env closes on the device.
 
 Batched convention: a step whose action ends the episode returns
 done = 1, the reward of that step, and the FIRST pair of the next episode
@@ -27,6 +30,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
+
+from ._lib import CATCH_STATE_INTS, check, lib, ptr, stream_handle
 
 SCREEN = (210, 160, 3)
 
@@ -196,6 +201,76 @@ class VecALE:
 
     def close(self):
         self.pool.shutdown(wait=True)
+
+
+class DeviceCatch:
+    """Catch on the device (include/asyncrl_hip.h, "device environment"): the
+    env of the closed actor-learner loop.  It owns the double-buffered env state
+    (2, n, 8) int32; one kernel launch per env-step moves every env and renders
+    its 210x160x3 frame pair.  Two ways to run it:
+
+    * attached to a net -- net.set_env(env), net.env_reset(*pools, pool_len),
+      then A3C.run_window(*pools, pool_len, first=True) and on: the window steps
+      the env from the actions it sampled, with no host work per step
+      (make_pools builds the pools; seed and env_offset must be the net's);
+    * granular, VecALE's surface -- reset() / step(actions) -> (pairs, r, d)
+      device tensors (n, 2, 210, 160, 3) uint8 / (n,) f32 / (n,) uint8, so
+      A3C.act_batch and evaluation.run_episodes take it unchanged.
+
+    Actions: 2 = right, 3 = left, anything else a no-op (n_actions >= 4).  Every
+    episode lasts 14 env-steps and returns +1 (caught) or -1."""
+
+    envs = ()        # no host emulators behind it (evaluation.run_episodes walks this)
+
+    def __init__(self, n_envs: int, device=None, seed: int = 0, env_offset: int = 0):
+        if n_envs < 1:
+            raise ValueError("DeviceCatch: n_envs must be >= 1")
+        self.n, self.seed, self.env_offset = n_envs, seed, env_offset
+        self.device = torch.device(device if device is not None else "cuda")
+        self.state = torch.zeros(lib.arl_catch_state_bytes(n_envs) // 4, dtype=torch.int32,
+                                 device=self.device).view(2, n_envs, CATCH_STATE_INTS)
+        self.parity = 0          # the state half the granular calls read next
+        self._out = None
+
+    number_of_actions = 4
+
+    def make_pools(self, pool_len: int):
+        """(pairs, rewards, dones) pools of pool_len >= 2 entries, zeroed."""
+        if pool_len < 2:
+            raise ValueError("DeviceCatch: pool_len must be >= 2")
+        return (torch.zeros((pool_len, self.n, 2) + SCREEN, dtype=torch.uint8, device=self.device),
+                torch.zeros((pool_len, self.n), dtype=torch.float32, device=self.device),
+                torch.zeros((pool_len, self.n), dtype=torch.uint8, device=self.device))
+
+    def _buffers(self):
+        if self._out is None:
+            self._out = (torch.empty((self.n, 2) + SCREEN, dtype=torch.uint8, device=self.device),
+                         torch.empty(self.n, dtype=torch.float32, device=self.device),
+                         torch.empty(self.n, dtype=torch.uint8, device=self.device))
+        return self._out
+
+    def reset(self, stream=None):
+        """Episode 0 of every env (arl_catch_reset) -> (pairs, r = 0, d = 0)."""
+        pairs, r, d = self._buffers()
+        self.parity = 0
+        check(lib.arl_catch_reset(ptr(self.state), self.n, self.env_offset, self.seed, self.parity, ptr(pairs), ptr(r),
+                                  ptr(d), stream_handle(stream)), "arl_catch_reset")
+        return pairs, r, d
+
+    def step(self, actions, stream=None):
+        """One env-step of every env (arl_catch_step); actions: (n,) integers.
+        The returned tensors are rewritten by the next call."""
+        a = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
+        if a.shape != (self.n,):
+            raise ValueError(f"DeviceCatch.step: need {self.n} actions")
+        pairs, r, d = self._buffers()
+        check(lib.arl_catch_step(ptr(self.state), self.parity, ptr(a), self.n, self.env_offset, self.seed, ptr(pairs),
+                                 ptr(r), ptr(d), stream_handle(stream)), "arl_catch_step")
+        self.parity ^= 1
+        return pairs, r, d
+
+    def close(self):
+        pass
 
 
 class _null:

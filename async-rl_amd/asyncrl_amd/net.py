@@ -16,8 +16,8 @@ import weakref
 import numpy as np
 import torch
 
-from ._lib import (ARCH_FF, ARCH_FF_NATURE, ARCH_LSTM, ARCH_RGB, ARCH_STACK, ARCH_STATES, CTL_ADAM_T, ENV_GROUP_ALIGN,
-                   EPISODE_LOG, EPISODE_STAT_FIELDS, FWD_KEEP_STATE, POOL_DONES, POOL_FRAMES, POOL_REWARDS,
+from ._lib import (ARCH_FF, ARCH_FF_NATURE, ARCH_LSTM, ARCH_RGB, ARCH_STACK, ARCH_STATES, CTL_ADAM_T, ENV_CATCH,
+                   ENV_GROUP_ALIGN, EPISODE_LOG, EPISODE_STAT_FIELDS, FWD_KEEP_STATE, POOL_DONES, POOL_FRAMES, POOL_REWARDS,
                    RESIZE_SCALAR, STAGE_HOST, STAGE_NAMES, WINDOW_LOG, WINDOW_STAT_FIELDS, WINDOW_STAT_NAMES, check,
                    lib, ptr, stream_handle)
 
@@ -446,6 +446,41 @@ class DeviceNet:
     def window_stats(self, last: int = 1, stream=None) -> list:
         """window_stats_raw as a list of dicts (window_stats_dict), oldest first."""
         return [window_stats_dict(r) for r in self.window_stats_raw(last, stream)]
+
+    # ------------------------------------------------------------ device environment
+    env = None        # the attached DeviceCatch (set_env), else None
+
+    def set_env(self, env=None):
+        """Attach a device-resident env (envs.DeviceCatch; arl_net_set_env) built
+        for this net's n_envs, seed and env_offset, or detach with None.  While
+        attached, run_window steps it after every act(t), t < t_max, and the
+        pools handed to the window are written.  A captured window keeps the
+        env it was captured with."""
+        if env is None:
+            check(lib.arl_net_set_env(self._h, ENV_CATCH, None), "arl_net_set_env")
+            self.env = None
+            return
+        if (env.n, env.seed, env.env_offset) != (self.n_envs, self.seed, self.env_offset):
+            raise ValueError("set_env: the env must be built with the net's n_envs, seed and env_offset")
+        check(lib.arl_net_set_env(self._h, ENV_CATCH, ptr(env.state)), "arl_net_set_env")
+        self.env = env
+
+    def env_reset(self, pair_pool, reward_pool, done_pool, pool_len: int, stream=None):
+        """Episode 0 of every env into pool entry (step counter) % pool_len
+        (arl_env_reset); the window that follows runs with first=True."""
+        check_pools(pool_len, pair_pool, reward_pool, done_pool)
+        self.set_pools(pair_pool, reward_pool, done_pool)
+        check(lib.arl_env_reset(self._h, ptr(pair_pool), ptr(reward_pool), ptr(done_pool), pool_len,
+                                stream_handle(stream)), "arl_env_reset")
+
+    def env_step(self, t: int, pair_pool, reward_pool, done_pool, pool_len: int, stream=None, envs=None):
+        """One env-step from row t of the actions buffer into the pool entry
+        observe(t + 1) reads (arl_env_step); envs=(e0, ne): only that range."""
+        check_pools(pool_len, pair_pool, reward_pool, done_pool)
+        self.set_pools(pair_pool, reward_pool, done_pool)
+        e0, ne = envs if envs is not None else (0, self.n_envs)
+        check(lib.arl_env_step(self._h, t, e0, ne, ptr(pair_pool), ptr(reward_pool), ptr(done_pool), pool_len,
+                               stream_handle(stream)), "arl_env_step")
 
     def reset_state(self, e0: int = 0, n: int | None = None, stream=None):
         """LSTM: the pi_and_v recurrent state of rows [e0, e0 + n) -> None (arl_reset_state)."""

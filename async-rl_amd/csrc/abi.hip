@@ -463,6 +463,112 @@ int arl_act(arl_net* h, int t, void* s) {
   return hip_status(arl::net_act(h->net, t, 1, S(s)), "act");
 }
 
+// ---------------------------------------------------------------- device environment
+int64_t arl_catch_state_bytes(int64_t n_envs) {
+  return n_envs < 0 ? -1 : 2 * n_envs * arl::CATCH_STATE_INTS * (int64_t)sizeof(int32_t);
+}
+
+// the granular calls: explicit pointers, one pool entry, the parity from the host
+static int catch_granular(const char* who, int32_t* state, int parity, const int32_t* actions, bool step, int64_t n,
+                          int env_offset, uint64_t seed, uint8_t* pair, float* reward, uint8_t* done, void* s) {
+  const std::string w = who;
+  if (n < 0 || n > 65535) return fail(ARL_EINVAL, w + ": n out of [0, 65535]");
+  if (parity != 0 && parity != 1) return fail(ARL_EINVAL, w + ": parity must be 0 or 1");
+  if (n == 0) return ARL_OK;
+  if (!state || !pair || !reward || !done || (step && !actions)) return fail(ARL_EINVAL, w + ": null pointer");
+  if (!aligned(state, 16) || !aligned(pair, 16) || !aligned(reward, 4) || (step && !aligned(actions, 4)))
+    return fail(ARL_EINVAL, w + ": state and frames 16-byte aligned, rewards and actions 4-byte aligned");
+  arl::CatchArgs a{};
+  a.state = state;
+  a.actions = step ? actions : nullptr;
+  a.ctl = nullptr;
+  a.t = parity;
+  a.dpool = arl::fd_make(1u);
+  a.pair_pool = pair;
+  a.reward_pool = reward;
+  a.done_pool = done;
+  a.n = (int)n;
+  a.e0 = 0;
+  a.ne = -1;
+  a.env_offset = env_offset;
+  a.seed_lo = (uint32_t)seed;
+  a.seed_hi = (uint32_t)(seed >> 32);
+  return hip_status(arl::launch_catch(a, S(s)), who);
+}
+
+int arl_catch_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, int parity, uint8_t* pair_out,
+                    float* reward_out, uint8_t* done_out, void* s) {
+  return catch_granular("catch_reset", state, parity, nullptr, false, n, env_offset, seed, pair_out, reward_out,
+                        done_out, s);
+}
+
+int arl_catch_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
+                   uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* s) {
+  return catch_granular("catch_step", state, parity_in, actions, true, n, env_offset, seed, pair_out, reward_out,
+                        done_out, s);
+}
+
+int arl_net_set_env(arl_net* h, int kind, int32_t* state) {
+  if (!h) return fail(ARL_EINVAL, "null net");
+  if (kind != ARL_ENV_CATCH) return fail(ARL_EINVAL, "set_env: unknown env kind");
+  if (!state) {   // detach
+    h->net.env_state = nullptr;
+    return ARL_OK;
+  }
+  const arl::Net& n = h->net;
+  if (n.rgb || n.stack || n.states)
+    return fail(ARL_ESTATE, "set_env: the env renders frame pairs (FF / LSTM / FF_NATURE nets without a frames flag)");
+  if (n.A < 4) return fail(ARL_EINVAL, "set_env: Catch needs n_actions >= 4 (NOOP / FIRE / RIGHT / LEFT)");
+  if (!aligned(state, 16)) return fail(ARL_EINVAL, "set_env: state must be 16-byte aligned");
+  h->net.env_state = state;
+  return ARL_OK;
+}
+
+// validates an env launch of a bound net and fills its arguments (0 = ok); step == false: the reset
+static int env_args(arl_net* h, bool step, int t, int e0, int ne, uint8_t* pair_pool, float* reward_pool,
+                    uint8_t* done_pool, int64_t pool_len, arl::CatchArgs& a) {
+  arl::Net& n = h->net;
+  if (!n.env_state) return fail(ARL_ESTATE, "env: no env attached (arl_net_set_env)");
+  if (step && (t < 0 || t >= n.T)) return fail(ARL_EINVAL, "env_step: t out of [0, t_max)");
+  if (pool_len < 2 || pool_len > INT32_MAX) return fail(ARL_EINVAL, "env: pool_len out of [2, 2^31 - 1]");
+  if (!pair_pool || !reward_pool || !done_pool) return fail(ARL_EINVAL, "env: the env writes all three pools");
+  if (!aligned(pair_pool, 16) || !aligned(reward_pool, 4))
+    return fail(ARL_EINVAL, "env: the frame pool must be 16-byte aligned, the reward pool 4-byte aligned");
+  if (n.N > 65535) return fail(ARL_EINVAL, "env: n_envs > 65535");
+  if (int rc = check_pool(h, ARL_POOL_FRAMES, pair_pool, pool_len, (int64_t)arl::PAIR * n.N, "frame")) return rc;
+  if (int rc = check_pool(h, ARL_POOL_REWARDS, reward_pool, pool_len, 4 * (int64_t)n.N, "reward")) return rc;
+  if (int rc = check_pool(h, ARL_POOL_DONES, done_pool, pool_len, (int64_t)n.N, "done")) return rc;
+  a = arl::CatchArgs{};
+  a.state = n.env_state;
+  a.actions = step ? n.at<int32_t>(n.w_act) + (int64_t)t * n.N : nullptr;
+  a.ctl = n.at<int64_t>(n.w_ctl);
+  a.t = step ? t : 0;
+  a.dpool = arl::fd_make((uint32_t)pool_len);
+  a.pair_pool = pair_pool;
+  a.reward_pool = reward_pool;
+  a.done_pool = done_pool;
+  a.n = n.N;
+  a.e0 = e0;
+  a.ne = ne;
+  a.env_offset = n.env_offset;
+  a.seed_lo = (uint32_t)n.seed;
+  a.seed_hi = (uint32_t)(n.seed >> 32);
+  return 0;
+}
+
+static int env_launch(const arl::Net& n, const arl::CatchArgs& a, void* s, const char* what) {
+  hipError_t e = arl::launch_catch(a, S(s));
+  if (e == hipSuccess) e = arl::stamp(n, arl::STAGE_OTHER, S(s));
+  return hip_status(e, what);
+}
+
+int arl_env_reset(arl_net* h, uint8_t* pair_pool, float* reward_pool, uint8_t* done_pool, int64_t pool_len, void* s) {
+  NEED_BOUND(h);
+  arl::CatchArgs a;
+  if (int rc = env_args(h, false, 0, 0, -1, pair_pool, reward_pool, done_pool, pool_len, a)) return rc;
+  return env_launch(h->net, a, s, "env_reset");
+}
+
 int arl_act_mode(arl_net* h, int t, int mode, void* s) {
   NEED_BOUND(h);
   if (t < 0 || t > h->net.T) return fail(ARL_EINVAL, "act: t out of [0, t_max]");
@@ -492,6 +598,15 @@ int arl_observe_envs(arl_net* h, int t, int e0, int ne, const uint8_t* pool, int
     H = W = 0;
   }
   return observe_common(h, t, pool, reward_pool, done_pool, pool_len, force_reset, mode, H, W, s, e0, ne);
+}
+
+int arl_env_step(arl_net* h, int t, int e0, int ne, uint8_t* pair_pool, float* reward_pool, uint8_t* done_pool,
+                 int64_t pool_len, void* s) {
+  NEED_BOUND(h);
+  if (int rc = check_env_range(h->net, e0, ne)) return rc;
+  arl::CatchArgs a;
+  if (int rc = env_args(h, true, t, e0, ne, pair_pool, reward_pool, done_pool, pool_len, a)) return rc;
+  return env_launch(h->net, a, s, "env_step");
 }
 
 int arl_act_envs(arl_net* h, int t, int e0, int ne, int mode, void* s) {
@@ -615,6 +730,14 @@ int arl_run_window(arl_net* h, const uint8_t* pair_pool, const float* reward_poo
     arl::RingArgs a;
     if (int rc = ring_args(h, 0, pair_pool, reward_pool, done_pool, pool_len, 0, resize_mode, 0, 0, 0, -1, a)) return rc;
   }
+  // an attached env steps after every act(t), t < T, into the pools the next observation reads (so it writes
+  // them: the signature keeps the observing calls' const)
+  const bool env = n.env_state != nullptr;
+  arl::CatchArgs ea;
+  if (env)
+    if (int rc = env_args(h, true, 0, 0, -1, const_cast<uint8_t*>(pair_pool), const_cast<float*>(reward_pool),
+                          const_cast<uint8_t*>(done_pool), pool_len, ea))
+      return rc;
   // FF: the learner's returns + heads backward run in the bootstrap step's policy launch
   const bool fuse_was = n.fuse_returns;
   const arl::Net::ReturnsCfg ret_was = n.ret;
@@ -636,6 +759,15 @@ int arl_run_window(arl_net* h, const uint8_t* pair_pool, const float* reward_poo
       n.fuse_returns = fuse_was;
       n.ret = ret_was;
       return hip_status(e, "run_window: act");
+    }
+    if (env && t < n.T) {
+      ea.t = t;
+      ea.actions = n.at<int32_t>(n.w_act) + (int64_t)t * n.N;
+      if (const int rc = env_launch(n, ea, s, "run_window: env_step")) {
+        n.fuse_returns = fuse_was;
+        n.ret = ret_was;
+        return rc;
+      }
     }
   }
   n.fuse_returns = fuse_was;

@@ -134,6 +134,26 @@ hipError_t launch_episode_reset(char* block, int n, hipStream_t s);
 // envs in a fixed order (phi.hip episode_reduce_kernel); clear: also zero the cumulative per-env arrays
 hipError_t launch_episode_reduce(char* block, int n, double* out8, int clear, hipStream_t s);
 
+// Device-resident Catch (catch.hip; the header's "device environment"): one launch = one env-step (or the
+// reset) of envs [e0, e0 + ne): transition + render into pool entry (k + 1) % pool_len (reset: k % pool_len),
+// k = ctl[CTL_STEP] + t read on the device; the state half read is k & 1, the half written (k + 1) & 1.
+constexpr int CATCH_STATE_INTS = 8;   // [bx, by, vx, px, episode, steps_in_episode, 0, 0]
+struct CatchArgs {
+  int32_t* state;            // (2, n, CATCH_STATE_INTS), 16-byte aligned
+  const int32_t* actions;    // (n): the actions of observation k; null: reset (episode 0 into half k & 1)
+  const int64_t* ctl;        // the control block; null: k = t (the granular calls: t = the parity, pool_len 1)
+  int64_t t;
+  FastDiv dpool;             // pool_len as a divisor of the step counter, filled by the host
+  uint8_t* pair_pool;        // (pool_len, n, 2, 210, 160, 3)
+  float* reward_pool;        // (pool_len, n)
+  uint8_t* done_pool;        // (pool_len, n)
+  int n;
+  int e0 = 0, ne = -1;       // env range of this launch: e0 + blockIdx.y, ne envs (-1: all n)
+  int env_offset = 0;
+  uint32_t seed_lo = 0, seed_hi = 0;
+};
+hipError_t launch_catch(const CatchArgs& a, hipStream_t s);
+
 // RGB (Doom) observations, train_a3c_doom.py:21-23 / doom_env.py:47
 constexpr int RGB_MAX_W = 2048;   // staged source rows: 12 x W x 3 bytes of LDS
 hipError_t launch_rgb_phi(const uint8_t* imgs, int64_t n, int H, int W, float* out, int mode, hipStream_t s);
@@ -197,6 +217,9 @@ struct Net {
   // in ms, the update count in ctl[CTL_ADAM_T]) instead of rmsprop_kernel
   float* adam_m = nullptr;
   double adam_beta1 = 0.9, adam_beta2 = 0.999;
+  // arl_net_set_env: non-null = a device-resident Catch steps from the actions buffer (arl_env_step, and
+  // arl_run_window after every arl_act(t), t < T); its double-buffered state (2, N, CATCH_STATE_INTS)
+  int32_t* env_state = nullptr;
   int64_t eval_draws = 0;  // sampling forward_states calls so far (Philox stream 1 counter)
   // clip norm folded into the learner's conv reduce (arl_net_set_norm_fold; only valid when
   // nothing changes the gradient between arl_learn and the update, e.g. no all-reduce):

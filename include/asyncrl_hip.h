@@ -550,6 +550,88 @@ int arl_episode_stats(arl_net* net, double* out8_device, int clear, void* stream
 int arl_net_set_window_stats(arl_net* net, int on);
 int arl_window_stats_reset(arl_net* net, void* stream);
 
+/* ------------------------------------------------------------------ device environment */
+
+/* A device-resident Catch, so that the actor-learner loop closes without the
+ * host: env -> phi -> forward -> sample -> env -> ... -> update, eagerly or as
+ * one replayed graph.  An extension (the reference's envs are host emulators,
+ * ale.py / doom_env.py); additions to ABI 4.  One launch per env-step does the
+ * transition and the render of real 210 x 160 x 3 frame pairs into the pools
+ * arl_observe reads, with the reward and done the learner ingests.
+ *
+ * The game (exact in integer arithmetic; tests/catch_ref.py restates it).
+ * Screen 210 rows x 160 columns, RGB uint8, HWC, black.  Paddle 16 x 4 on rows
+ * 190..193, colour (200, 72, 72), left edge px in [0, 144].  Ball 8 x 8, colour
+ * (236, 236, 236), left edge bx in [0, 152], top edge by; a pixel inside both
+ * takes the ball's colour.  Action 2 moves right, 3 left, every other value is
+ * a no-op (Breakout's NOOP / FIRE / RIGHT / LEFT; any n_actions >= 4).
+ * One env-step is up to 4 emulator frames; frame f = 0..3:
+ *   1. right: px = min(px + 3, 144); left: px = max(px - 3, 0)
+ *   2. bx += vx; bx < 0: bx = -bx, vx = -vx; else bx > 152: bx = 304 - bx, vx = -vx
+ *   3. by += 3
+ *   4. by + 8 >= 190: the episode ends in this frame and the skip loop breaks
+ *      (ale.py:111-139); reward +1 if bx + 8 > px && bx < px + 16, else -1.
+ * Non-terminal step: reward 0.0f, done 0, pair[0] = the screen after frame 4,
+ * pair[1] = the screen after frame 3 (the order arl_observe documents).
+ * Terminal step: reward +-1.0f, done 1, the env starts its next episode at once
+ * and both frames of the pair are that episode's first screen (the reference's
+ * episode start, ale.py:141-161; the terminal screen is never shown).
+ * Episode start (the per-env episode counter starts at 0 and advances at every
+ * terminal): by = 18, px = 72, steps_in_episode = 0, and with (w0, w1, ., .) =
+ * philox4x32_10(counter = (env_offset + e, episode, 0, 2), key = (seed &
+ * 0xffffffff, seed >> 32)): bx = w0 % 153, vx = (int)(w1 % 5) - 2.  Counter
+ * word 3 = 2 is a stream beside 0 (window draws) and 1 (pi_and_v draws).
+ * Every episode lasts 14 env-steps; the optimal return is +1, a uniform random
+ * policy scores about -0.70.
+ *
+ * Env state: caller-owned device memory, (2, n_envs, 8) int32, 16-byte aligned,
+ * [bx, by, vx, px, episode, steps_in_episode, 0, 0] per env, double-buffered by
+ * the parity of the global observation index: the launch for observation
+ * k -> k + 1 reads half k & 1 and writes half (k + 1) & 1.  Every workgroup of
+ * an env recomputes the transition from the old half and one of them writes the
+ * new half, the reward and the done, so no workgroup reads a word another
+ * workgroup of its launch writes.
+ *
+ * Granular calls (no net): arl_catch_state_bytes(n_envs) = the state's size;
+ * arl_catch_reset: episode 0 of every env into half `parity`, the first screens
+ * (twice) into pair_out (n, 2, 210, 160, 3), rewards 0.0f (n,), dones 0 (n,);
+ * arl_catch_step: one env-step from actions (n,) int32 and half parity_in into
+ * half 1 - parity_in and the outputs.  n <= 65535; ARL_EINVAL for a null or
+ * misaligned pointer (state, frames 16 bytes) or a parity other than 0 / 1. */
+#define ARL_ENV_CATCH 1
+int64_t arl_catch_state_bytes(int64_t n_envs);
+int arl_catch_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, int parity, uint8_t* pair_out,
+                    float* reward_out, uint8_t* done_out, void* stream);
+int arl_catch_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
+                   uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* stream);
+
+/* Attached to a net (host state of the handle, like arl_net_set_adam; works on
+ * an unbound handle): arl_net_set_env(net, ARL_ENV_CATCH, state) with state as
+ * above for the net's n_envs, its env_offset and seed; state == NULL detaches.
+ * Only frame-pair nets (FF, LSTM, FF_NATURE without the RGB / STACK / STATES
+ * flags), else ARL_ESTATE; n_actions < 4 or a misaligned state: ARL_EINVAL.
+ *
+ * arl_env_reset: the reset into pool entry ctl[CTL_STEP] % pool_len and state
+ * half ctl[CTL_STEP] & 1, both read on the device; the window that follows runs
+ * with first != 0.  arl_env_step: steps envs [e0, e0 + ne) (the range rules of
+ * arl_observe_envs, so env-group chains on several streams stay independent)
+ * from row t of the workspace's "actions" buffer, 0 <= t < t_max, into entry
+ * (k + 1) % pool_len, k = ctl[CTL_STEP] + t: what arl_observe(t + 1) reads.
+ * While an env is attached, arl_run_window issues the step itself after each
+ * arl_act(t), t < t_max (writing the pools it takes as const).  A captured
+ * window keeps the env it was captured with.
+ *
+ * The pools are written here: all three are needed, each inside a registered
+ * pool (arl_net_set_pool) with room for pool_len entries, and pool_len >= 2;
+ * otherwise ARL_EINVAL before any launch.  ARL_ESTATE without an attached env
+ * or on an unbound net.  With no env attached every other call makes exactly
+ * the launches it made before, with the same arguments. */
+int arl_net_set_env(arl_net* net, int kind, int32_t* state);
+int arl_env_reset(arl_net* net, uint8_t* pair_pool, float* reward_pool, uint8_t* done_pool, int64_t pool_len,
+                  void* stream);
+int arl_env_step(arl_net* net, int t, int e0, int ne, uint8_t* pair_pool, float* reward_pool, uint8_t* done_pool,
+                 int64_t pool_len, void* stream);
+
 /* ------------------------------------------------------------------ granular ops */
 
 /* RMSpropAsync.update_one (rmsprop_async.py:23-38) on flat f32 arrays, with

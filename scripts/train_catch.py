@@ -1,0 +1,108 @@
+#!/usr/bin/env python
+"""Closed-loop training on the device-resident Catch (asyncrl_amd.DeviceCatch): the learner has to learn.
+
+env -> phi -> forward -> sample -> env -> ... -> update runs on the device with no host work per step: window 0
+eagerly (first=True), then one captured window replayed.  Every --report windows the learning curve is read
+from the device-side episode statistics (A3C.episode_stats(clear=True): the episodes completed since the
+last read) together with the newest per-window record (A3C.window_stats).  The optimum is +1 per episode, a
+uniform random policy scores about -0.70.
+
+Defaults are the reference's hyperparameters (RMSpropAsync lr 7e-4, alpha 0.99, eps 0.1, clip 40, beta 0.01,
+gamma 0.99) on the FF model with 256 envs; the batched learner sums the gradient of all envs, so --batch-loss
+mean, --opt adam and --gae-lambda are there to try.  One JSON line at the end (and --out FILE).
+
+    python scripts/train_catch.py [--windows 4000] [--report 200] [--envs 256] [--seed 0] [--lr 7e-4]
+                                  [--opt rmsprop|adam] [--batch-loss sum|mean] [--gae-lambda 1.0] [--arch ff|lstm]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "async-rl_amd"))
+
+import asyncrl_amd as pkg  # noqa: E402
+
+
+def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", batch_loss="sum", gae_lambda=1.0,
+          arch="ff", beta=1e-2, eps=None, device="cuda:0", log=print):
+    """Returns the curve: one dict per report with the window count, the episodes completed since the last
+    report and their mean return, and the newest window record's entropy / value / gradient norm."""
+    dev = torch.device(device)
+    T, A, P = 5, 4, 2
+    model = (pkg.A3CFF if arch == "ff" else pkg.A3CLSTM)(A, n_envs=envs, t_max=T, seed=seed, init_seed=seed,
+                                                         device=dev, frames="pairs")
+    if opt == "adam":
+        optimizer = pkg.Adam(alpha=lr, eps=1e-8 if eps is None else eps).setup(model)
+    else:
+        optimizer = pkg.RMSpropAsync(lr=lr, eps=1e-1 if eps is None else eps, alpha=0.99).setup(model)
+    optimizer.add_hook(pkg.GradientClipping(40))
+    agent = pkg.A3C(model, optimizer, T, 0.99, beta=beta, batch_loss=batch_loss, gae_lambda=gae_lambda,
+                    collectives=False)
+    net = model.net
+    net.set_episode_stats(True)
+    net.set_window_stats(True)
+    env = pkg.DeviceCatch(envs, device=dev, seed=seed)
+    pools = env.make_pools(P)
+    net.set_env(env)
+    stream = torch.cuda.Stream(device=dev)
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        net.env_reset(*pools, P, stream=stream)
+        agent.run_window(*pools, P, first=True, stream=stream)
+        stream.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=stream):
+            agent.run_window(*pools, P, stream=stream)
+    curve, done = [], 1
+    t0 = time.perf_counter()
+    while done < windows:
+        k = min(report, windows - done)
+        with torch.cuda.stream(stream):
+            for _ in range(k):
+                graph.replay()
+            done += k
+            ep = agent.episode_stats(clear=True, stream=stream)
+            ws = agent.window_stats(1, stream=stream)[0]
+        row = {"windows": done, "episodes": ep["episodes"], "mean_return": ep["mean"], "entropy": ws["entropy"],
+               "value_mean": ws["value_mean"], "grad_norm": ws["grad_norm"], "pi_loss": ws["pi_loss"],
+               "v_loss": ws["v_loss"], "seconds": time.perf_counter() - t0}
+        curve.append(row)
+        log("windows %6d  episodes %6d  return %+.3f  entropy %.3f  v %+.3f  |g| %9.3f  pi_loss %+10.3f  "
+            "v_loss %9.3f  %.1fs" % (done, row["episodes"], row["mean_return"], row["entropy"], row["value_mean"],
+                                     row["grad_norm"], row["pi_loss"], row["v_loss"], row["seconds"]))
+    return curve
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=256)
+    ap.add_argument("--windows", type=int, default=4000)
+    ap.add_argument("--report", type=int, default=200)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--lr", type=float, default=7e-4)
+    ap.add_argument("--opt", choices=("rmsprop", "adam"), default="rmsprop")
+    ap.add_argument("--batch-loss", choices=("sum", "mean"), default="sum")
+    ap.add_argument("--gae-lambda", type=float, default=1.0)
+    ap.add_argument("--beta", type=float, default=1e-2)
+    ap.add_argument("--eps", type=float, default=None)
+    ap.add_argument("--arch", choices=("ff", "lstm"), default="ff")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    cfg = {k: v for k, v in vars(a).items() if k != "out"}
+    curve = train(**cfg)
+    out = {"config": cfg, "curve": curve, "final_mean_return": curve[-1]["mean_return"] if curve else None}
+    print(json.dumps(out), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
