@@ -113,6 +113,10 @@ SIGNATURES = {
     "arl_catch_reset": (c_int, [c_void_p, c_i64, c_int, c_u64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "arl_catch_step": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_int, c_u64, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
+    "arl_breakout_state_bytes": (c_i64, [c_i64]),
+    "arl_breakout_reset": (c_int, [c_void_p, c_i64, c_int, c_u64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "arl_breakout_step": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_int, c_u64, c_int, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
     "arl_net_set_env": (c_int, [c_void_p, c_int, c_void_p]),
     "arl_env_reset": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "arl_env_step": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
@@ -141,6 +145,10 @@ LEARN_RETURNS, LEARN_TRUNK, LEARN_CONV = range(3)
 POOL_FRAMES, POOL_REWARDS, POOL_DONES = range(3)   # arl_net_set_pool kinds
 ENV_CATCH = 1          # ARL_ENV_CATCH: arl_net_set_env kind, the device-resident Catch
 CATCH_STATE_INTS = 8   # int32 per env and half of its state: [bx, by, vx, px, episode, steps_in_episode, 0, 0]
+ENV_BREAKOUT = 2       # ARL_ENV_BREAKOUT: the device-resident Breakout
+ENV_GAME_OVER_ONLY = 0x100   # ARL_ENV_GAME_OVER_ONLY, or'ed into the Breakout kind: a life loss is not a terminal
+BREAKOUT_STATE_INTS = 16     # [bx, by, vx, vy, px, lives, serves, steps_in_episode, game, game_steps, score,
+                             #  bricks_left, b0, b1, b2, b3]
 CTL_ADAM_T = 3         # ARL_CTL_ADAM_T: the control block's count of Adam updates made (buffer "ctl", int64[16])
 EPISODE_LOG = 8        # ARL_EPISODE_LOG: episodes per env the device-side episode log keeps
 # the 8 doubles of arl_episode_stats, in order

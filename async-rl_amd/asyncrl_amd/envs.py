@@ -17,7 +17,9 @@ phi pre-stage is the GPU kernel, so the adapter stops at the raw frame pair:
                  uint8 / reward / terminal layout A3C.act takes;
   DeviceCatch    no emulator at all: a small game whose transition and render
                  are one HIP kernel (csrc/catch.hip), so the loop env -> phi ->
-                 forward -> sample -> env closes on the device.
+                 forward -> sample -> env closes on the device;
+  DeviceBreakout the same for Breakout (csrc/breakout.hip): bricks, lives,
+                 rewards of 1, 4 and 7, episodes of different lengths.
 
 Batched convention: a step whose action ends the episode returns
 done = 1, the reward of that step, and the FIRST pair of the next episode
@@ -31,7 +33,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from ._lib import CATCH_STATE_INTS, check, lib, ptr, stream_handle
+from ._lib import (BREAKOUT_STATE_INTS, CATCH_STATE_INTS, ENV_BREAKOUT, ENV_CATCH, ENV_GAME_OVER_ONLY, check,
+                   lib, ptr, stream_handle)
 
 SCREEN = (210, 160, 3)
 
@@ -221,6 +224,7 @@ class DeviceCatch:
     episode lasts 14 env-steps and returns +1 (caught) or -1."""
 
     envs = ()        # no host emulators behind it (evaluation.run_episodes walks this)
+    kind = ENV_CATCH   # what DeviceNet.set_env hands arl_net_set_env
 
     def __init__(self, n_envs: int, device=None, seed: int = 0, env_offset: int = 0):
         if n_envs < 1:
@@ -237,7 +241,7 @@ class DeviceCatch:
     def make_pools(self, pool_len: int):
         """(pairs, rewards, dones) pools of pool_len >= 2 entries, zeroed."""
         if pool_len < 2:
-            raise ValueError("DeviceCatch: pool_len must be >= 2")
+            raise ValueError(f"{type(self).__name__}: pool_len must be >= 2")
         return (torch.zeros((pool_len, self.n, 2) + SCREEN, dtype=torch.uint8, device=self.device),
                 torch.zeros((pool_len, self.n), dtype=torch.float32, device=self.device),
                 torch.zeros((pool_len, self.n), dtype=torch.uint8, device=self.device))
@@ -266,6 +270,60 @@ class DeviceCatch:
         pairs, r, d = self._buffers()
         check(lib.arl_catch_step(ptr(self.state), self.parity, ptr(a), self.n, self.env_offset, self.seed, ptr(pairs),
                                  ptr(r), ptr(d), stream_handle(stream)), "arl_catch_step")
+        self.parity ^= 1
+        return pairs, r, d
+
+    def close(self):
+        pass
+
+
+class DeviceBreakout:
+    """Breakout on the device (include/asyncrl_hip.h, "device environment"; the
+    rules are there): DeviceCatch's surface over a game with 120 bricks that
+    persist across lives, brick rewards of 1, 4 and 7 (raw, unclipped), five
+    lives and episodes of different lengths.  The state is (2, n, 16) int32.
+
+    life_loss_terminal=True (training, ale.py:98-99): done = life lost or game
+    over.  False (evaluation, a3c_ale.py:75-76; what evaluation.run_episodes
+    wants): done = game over only.  The two differ in nothing else."""
+
+    envs = ()
+    number_of_actions = 4
+
+    def __init__(self, n_envs: int, device=None, seed: int = 0, env_offset: int = 0, life_loss_terminal: bool = True):
+        if n_envs < 1:
+            raise ValueError("DeviceBreakout: n_envs must be >= 1")
+        self.n, self.seed, self.env_offset = n_envs, seed, env_offset
+        self.life_loss_terminal = bool(life_loss_terminal)
+        self.flags = 0 if self.life_loss_terminal else ENV_GAME_OVER_ONLY
+        self.kind = ENV_BREAKOUT | self.flags
+        self.device = torch.device(device if device is not None else "cuda")
+        self.state = torch.zeros(lib.arl_breakout_state_bytes(n_envs) // 4, dtype=torch.int32,
+                                 device=self.device).view(2, n_envs, BREAKOUT_STATE_INTS)
+        self.parity = 0          # the state half the granular calls read next
+        self._out = None
+
+    make_pools = DeviceCatch.make_pools
+    _buffers = DeviceCatch._buffers
+
+    def reset(self, stream=None):
+        """A new game of every env (arl_breakout_reset) -> (pairs, r = 0, d = 0)."""
+        pairs, r, d = self._buffers()
+        self.parity = 0
+        check(lib.arl_breakout_reset(ptr(self.state), self.n, self.env_offset, self.seed, self.parity, ptr(pairs),
+                                     ptr(r), ptr(d), stream_handle(stream)), "arl_breakout_reset")
+        return pairs, r, d
+
+    def step(self, actions, stream=None):
+        """One env-step of every env (arl_breakout_step); actions: (n,) integers.
+        The returned tensors are rewritten by the next call."""
+        a = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
+        if a.shape != (self.n,):
+            raise ValueError(f"DeviceBreakout.step: need {self.n} actions")
+        pairs, r, d = self._buffers()
+        check(lib.arl_breakout_step(ptr(self.state), self.parity, ptr(a), self.n, self.env_offset, self.seed,
+                                    self.flags, ptr(pairs), ptr(r), ptr(d), stream_handle(stream)),
+              "arl_breakout_step")
         self.parity ^= 1
         return pairs, r, d
 

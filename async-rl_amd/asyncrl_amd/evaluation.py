@@ -28,6 +28,10 @@ on a VecALE of its own: every env's game is restarted and left mid-episode,
 so a training learner stepping the same envs would carry its frame ring,
 LSTM state and n-step bootstrap across an unrelated game without a terminal
 (the reference builds a fresh ALE per evaluation run, a3c_ale.py:75-76).
+A device-resident env goes through the same loop unchanged (it has no host
+emulators to switch, `envs = ()`), so its life-loss switch is the caller's:
+build `DeviceBreakout(n, life_loss_terminal=False)` for evaluation -- with the
+default a "run" would be a single life.  `DeviceCatch` has no lives.
 Host-side driver code; the per-step work is the device forward.
 """
 from __future__ import annotations

@@ -448,10 +448,11 @@ class DeviceNet:
         return [window_stats_dict(r) for r in self.window_stats_raw(last, stream)]
 
     # ------------------------------------------------------------ device environment
-    env = None        # the attached DeviceCatch (set_env), else None
+    env = None        # the attached DeviceCatch / DeviceBreakout (set_env), else None
 
     def set_env(self, env=None):
-        """Attach a device-resident env (envs.DeviceCatch; arl_net_set_env) built
+        """Attach a device-resident env (envs.DeviceCatch or envs.DeviceBreakout,
+        by its `kind`; arl_net_set_env) built
         for this net's n_envs, seed and env_offset, or detach with None.  While
         attached, run_window steps it after every act(t), t < t_max, and the
         pools handed to the window are written.  A captured window keeps the
@@ -462,7 +463,7 @@ class DeviceNet:
             return
         if (env.n, env.seed, env.env_offset) != (self.n_envs, self.seed, self.env_offset):
             raise ValueError("set_env: the env must be built with the net's n_envs, seed and env_offset")
-        check(lib.arl_net_set_env(self._h, ENV_CATCH, ptr(env.state)), "arl_net_set_env")
+        check(lib.arl_net_set_env(self._h, env.kind, ptr(env.state)), "arl_net_set_env")
         self.env = env
 
     def env_reset(self, pair_pool, reward_pool, done_pool, pool_len: int, stream=None):

@@ -468,9 +468,14 @@ int64_t arl_catch_state_bytes(int64_t n_envs) {
   return n_envs < 0 ? -1 : 2 * n_envs * arl::CATCH_STATE_INTS * (int64_t)sizeof(int32_t);
 }
 
-// the granular calls: explicit pointers, one pool entry, the parity from the host
-static int catch_granular(const char* who, int32_t* state, int parity, const int32_t* actions, bool step, int64_t n,
-                          int env_offset, uint64_t seed, uint8_t* pair, float* reward, uint8_t* done, void* s) {
+int64_t arl_breakout_state_bytes(int64_t n_envs) {
+  return n_envs < 0 ? -1 : 2 * n_envs * arl::BREAKOUT_STATE_INTS * (int64_t)sizeof(int32_t);
+}
+
+// the granular calls: explicit pointers, one pool entry, the parity from the host; kind: ARL_ENV_* | flags
+static int env_granular(const char* who, int kind, int32_t* state, int parity, const int32_t* actions, bool step,
+                        int64_t n, int env_offset, uint64_t seed, uint8_t* pair, float* reward, uint8_t* done,
+                        void* s) {
   const std::string w = who;
   if (n < 0 || n > 65535) return fail(ARL_EINVAL, w + ": n out of [0, 65535]");
   if (parity != 0 && parity != 1) return fail(ARL_EINVAL, w + ": parity must be 0 or 1");
@@ -493,24 +498,42 @@ static int catch_granular(const char* who, int32_t* state, int parity, const int
   a.env_offset = env_offset;
   a.seed_lo = (uint32_t)seed;
   a.seed_hi = (uint32_t)(seed >> 32);
+  if ((kind & ~ARL_ENV_GAME_OVER_ONLY) == ARL_ENV_BREAKOUT)
+    return hip_status(arl::launch_breakout(a, (kind & ARL_ENV_GAME_OVER_ONLY) != 0, S(s)), who);
   return hip_status(arl::launch_catch(a, S(s)), who);
 }
 
 int arl_catch_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, int parity, uint8_t* pair_out,
                     float* reward_out, uint8_t* done_out, void* s) {
-  return catch_granular("catch_reset", state, parity, nullptr, false, n, env_offset, seed, pair_out, reward_out,
-                        done_out, s);
+  return env_granular("catch_reset", ARL_ENV_CATCH, state, parity, nullptr, false, n, env_offset, seed, pair_out,
+                      reward_out, done_out, s);
 }
 
 int arl_catch_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
                    uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* s) {
-  return catch_granular("catch_step", state, parity_in, actions, true, n, env_offset, seed, pair_out, reward_out,
-                        done_out, s);
+  return env_granular("catch_step", ARL_ENV_CATCH, state, parity_in, actions, true, n, env_offset, seed, pair_out,
+                      reward_out, done_out, s);
+}
+
+int arl_breakout_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, int parity, uint8_t* pair_out,
+                       float* reward_out, uint8_t* done_out, void* s) {
+  return env_granular("breakout_reset", ARL_ENV_BREAKOUT, state, parity, nullptr, false, n, env_offset, seed, pair_out,
+                      reward_out, done_out, s);
+}
+
+int arl_breakout_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
+                      int flags, uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* s) {
+  if (flags & ~ARL_ENV_GAME_OVER_ONLY)
+    return fail(ARL_EINVAL, "breakout_step: flags must be 0 or ARL_ENV_GAME_OVER_ONLY");
+  return env_granular("breakout_step", ARL_ENV_BREAKOUT | flags, state, parity_in, actions, true, n, env_offset, seed,
+                      pair_out, reward_out, done_out, s);
 }
 
 int arl_net_set_env(arl_net* h, int kind, int32_t* state) {
   if (!h) return fail(ARL_EINVAL, "null net");
-  if (kind != ARL_ENV_CATCH) return fail(ARL_EINVAL, "set_env: unknown env kind");
+  if (kind != ARL_ENV_CATCH && (kind & ~ARL_ENV_GAME_OVER_ONLY) != ARL_ENV_BREAKOUT)
+    return fail(ARL_EINVAL,
+                "set_env: unknown env kind (ARL_ENV_CATCH, or ARL_ENV_BREAKOUT [| ARL_ENV_GAME_OVER_ONLY])");
   if (!state) {   // detach
     h->net.env_state = nullptr;
     return ARL_OK;
@@ -518,9 +541,10 @@ int arl_net_set_env(arl_net* h, int kind, int32_t* state) {
   const arl::Net& n = h->net;
   if (n.rgb || n.stack || n.states)
     return fail(ARL_ESTATE, "set_env: the env renders frame pairs (FF / LSTM / FF_NATURE nets without a frames flag)");
-  if (n.A < 4) return fail(ARL_EINVAL, "set_env: Catch needs n_actions >= 4 (NOOP / FIRE / RIGHT / LEFT)");
+  if (n.A < 4) return fail(ARL_EINVAL, "set_env: the env needs n_actions >= 4 (NOOP / FIRE / RIGHT / LEFT)");
   if (!aligned(state, 16)) return fail(ARL_EINVAL, "set_env: state must be 16-byte aligned");
   h->net.env_state = state;
+  h->net.env_kind = kind;
   return ARL_OK;
 }
 
@@ -557,7 +581,9 @@ static int env_args(arl_net* h, bool step, int t, int e0, int ne, uint8_t* pair_
 }
 
 static int env_launch(const arl::Net& n, const arl::CatchArgs& a, void* s, const char* what) {
-  hipError_t e = arl::launch_catch(a, S(s));
+  hipError_t e = (n.env_kind & ~ARL_ENV_GAME_OVER_ONLY) == ARL_ENV_BREAKOUT
+                     ? arl::launch_breakout(a, (n.env_kind & ARL_ENV_GAME_OVER_ONLY) != 0, S(s))
+                     : arl::launch_catch(a, S(s));
   if (e == hipSuccess) e = arl::stamp(n, arl::STAGE_OTHER, S(s));
   return hip_status(e, what);
 }

@@ -154,6 +154,12 @@ struct CatchArgs {
 };
 hipError_t launch_catch(const CatchArgs& a, hipStream_t s);
 
+// Device-resident Breakout (breakout.hip): the same launch shape and arguments as Catch's, over a state of
+// (2, n, BREAKOUT_STATE_INTS); game_over_only: a life loss is not a terminal (ARL_ENV_GAME_OVER_ONLY)
+constexpr int BREAKOUT_STATE_INTS = 16;   // [bx, by, vx, vy, px, lives, serves, steps_in_episode, game, game_steps,
+                                          //  score, bricks_left, b0, b1, b2, b3]
+hipError_t launch_breakout(const CatchArgs& a, bool game_over_only, hipStream_t s);
+
 // RGB (Doom) observations, train_a3c_doom.py:21-23 / doom_env.py:47
 constexpr int RGB_MAX_W = 2048;   // staged source rows: 12 x W x 3 bytes of LDS
 hipError_t launch_rgb_phi(const uint8_t* imgs, int64_t n, int H, int W, float* out, int mode, hipStream_t s);
@@ -217,9 +223,11 @@ struct Net {
   // in ms, the update count in ctl[CTL_ADAM_T]) instead of rmsprop_kernel
   float* adam_m = nullptr;
   double adam_beta1 = 0.9, adam_beta2 = 0.999;
-  // arl_net_set_env: non-null = a device-resident Catch steps from the actions buffer (arl_env_step, and
-  // arl_run_window after every arl_act(t), t < T); its double-buffered state (2, N, CATCH_STATE_INTS)
+  // arl_net_set_env: non-null = a device-resident env steps from the actions buffer (arl_env_step, and
+  // arl_run_window after every arl_act(t), t < T); its double-buffered state (2, N, CATCH_STATE_INTS or
+  // BREAKOUT_STATE_INTS) and the kind it was attached as (ARL_ENV_*, with ARL_ENV_GAME_OVER_ONLY or'ed in)
   int32_t* env_state = nullptr;
+  int env_kind = 0;
   int64_t eval_draws = 0;  // sampling forward_states calls so far (Philox stream 1 counter)
   // clip norm folded into the learner's conv reduce (arl_net_set_norm_fold; only valid when
   // nothing changes the gradient between arl_learn and the update, e.g. no all-reduce):

@@ -605,9 +605,86 @@ int arl_catch_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, in
 int arl_catch_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
                    uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* stream);
 
+/* A device-resident Breakout, the second device environment: the game the
+ * reference's published numbers are about, with what Catch lacks -- episodes
+ * of different lengths (terminals out of phase between envs), rewards above 1
+ * (clip_reward has work to do), lives (the reference's
+ * treat_life_lost_as_terminal, ale.py:96-131) and bricks that persist across
+ * an episode boundary.  Same launch shape, pools and state protocol as Catch;
+ * additions to ABI 4.
+ *
+ * The game (exact in integer arithmetic; tests/breakout_ref.py restates it).
+ * Screen 210 rows x 160 columns, RGB uint8, HWC, black.
+ * Bricks: 6 rows x 20 columns, each 8 wide and 6 tall; brick (r, c) covers
+ *   columns 8c .. 8c+7 and rows 57+6r .. 62+6r.  Bit i = 20r + c lives in four
+ *   uint32 words: word i >> 5, bit i & 31.  Row colours, r = 0..5: (200,72,72),
+ *   (198,108,58), (180,122,48), (162,162,42), (72,160,72), (66,72,200).  Row
+ *   values: 7, 7, 4, 4, 1, 1.
+ * Paddle: 16 x 4 on rows 190..193, colour (200,72,72), px in [0, 144].
+ * Ball: 4 x 4, colour (236,236,236), bx in [0, 156]; a ball pixel covers
+ *   anything under it.
+ * Actions: 2 = right, 3 = left, anything else a no-op (n_actions >= 4).  There
+ *   is no FIRE: the ball serves itself.
+ * Serve: by = 100, vy = +4, and with (w0, w1, ., .) = philox4x32_10(counter =
+ *   (env_offset + e, serves, 0, 3), key = (seed & 0xffffffff, seed >> 32)):
+ *   bx = w0 % 157, vx = (-2, -1, 1, 2)[w1 % 4]; then serves += 1.  serves
+ *   counts every serve of the env and starts at 0.  Counter word 3 = 3 is a
+ *   stream beside 0 (window draws), 1 (pi_and_v draws) and 2 (Catch).
+ * New game: all 120 bricks present, lives = 5, px = 72, game_steps = 0,
+ *   score = 0, then a serve.
+ * One env-step is up to 4 frames; frame f does, in order:
+ *   1. right: px = min(px + 3, 144); left: px = max(px - 3, 0)
+ *   2. bx += vx; bx < 0: bx = -bx, vx = -vx; else bx > 156: bx = 312 - bx,
+ *      vx = -vx
+ *   3. by += vy; by < 32: by = 64 - by, vy = -vy
+ *   4. brick test: cx = bx + 2, cy = by if vy < 0 else by + 3; if
+ *      57 <= cy < 93: r = (cy - 57) / 6, c = cx >> 3; if the bit is set: clear
+ *      it, reward += value[r], vy = -vy, bricks_left -= 1
+ *   5. paddle test, only if vy > 0 && by + 4 >= 190: if bx + 4 > px &&
+ *      bx < px + 16: by = 372 - by, vy = -vy, vx = (-2,-1,1,2)[clamp(bx + 2 -
+ *      px, 0, 15) >> 2]; otherwise a life is lost: lives -= 1
+ *   6. the skip loop breaks in the frame where a life is lost or
+ *      bricks_left == 0 (ale.py:111-139).
+ * After the frames: game_steps += 1, score += reward.  The game is over when
+ * lives == 0 || bricks_left == 0 || game_steps >= 1000; a new game then starts
+ * at once (game += 1).  On a life loss that does not end the game the ball is
+ * re-served at once; bricks, lives, score and px are kept.  In both cases both
+ * frames of the pair are the first screen after the serve (Catch's rule: the
+ * losing screen is never shown).  Otherwise pair[0] is the screen after frame
+ * 4 and pair[1] the screen after frame 3.
+ * Done: by default a life loss is terminal (ale.py:98-99): done = life lost ||
+ * game over.  With ARL_ENV_GAME_OVER_ONLY done = game over only (the
+ * reference's evaluation env, a3c_ale.py:75-76).  The two modes differ in
+ * nothing but the done byte and steps_in_episode (which counts the env-steps
+ * since the last done); state, rewards and frames are identical.  The reward
+ * is the raw float sum of the step's brick values (it can be 14): clipping is
+ * the learner's business (clip_reward), the episode statistics count it raw.
+ * A uniform random policy scores about 0.15 per life (88 % of lives score 0,
+ * a life lasts 6 env-steps and more); tracking the ball scores hundreds per
+ * game and runs into the 1000-step cap.
+ *
+ * Env state: caller-owned device memory, (2, n_envs, 16) int32, 16-byte
+ * aligned, [bx, by, vx, vy, px, lives, serves, steps_in_episode, game,
+ * game_steps, score, bricks_left, b0, b1, b2, b3] per env, double-buffered by
+ * the parity of the observation index exactly as Catch's.
+ *
+ * Granular calls: Catch's trio; arl_breakout_step takes flags = 0 or
+ * ARL_ENV_GAME_OVER_ONLY (anything else: ARL_EINVAL). */
+#define ARL_ENV_BREAKOUT 2
+#define ARL_ENV_GAME_OVER_ONLY 0x100
+int64_t arl_breakout_state_bytes(int64_t n_envs);
+int arl_breakout_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, int parity, uint8_t* pair_out,
+                       float* reward_out, uint8_t* done_out, void* stream);
+int arl_breakout_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
+                      int flags, uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* stream);
+
 /* Attached to a net (host state of the handle, like arl_net_set_adam; works on
- * an unbound handle): arl_net_set_env(net, ARL_ENV_CATCH, state) with state as
- * above for the net's n_envs, its env_offset and seed; state == NULL detaches.
+ * an unbound handle): arl_net_set_env(net, kind, state) with kind =
+ * ARL_ENV_CATCH, ARL_ENV_BREAKOUT or ARL_ENV_BREAKOUT | ARL_ENV_GAME_OVER_ONLY
+ * (any other value, the flag on Catch included: ARL_EINVAL) and state as above
+ * for that env, the net's n_envs, its env_offset and seed; state == NULL
+ * detaches.  arl_env_reset, arl_env_step and arl_run_window launch the
+ * attached kind.
  * Only frame-pair nets (FF, LSTM, FF_NATURE without the RGB / STACK / STATES
  * flags), else ARL_ESTATE; n_actions < 4 or a misaligned state: ARL_EINVAL.
  *
@@ -619,7 +696,7 @@ int arl_catch_step(int32_t* state, int parity_in, const int32_t* actions, int64_
  * (k + 1) % pool_len, k = ctl[CTL_STEP] + t: what arl_observe(t + 1) reads.
  * While an env is attached, arl_run_window issues the step itself after each
  * arl_act(t), t < t_max (writing the pools it takes as const).  A captured
- * window keeps the env it was captured with.
+ * window keeps the env, and the flag, it was captured with.
  *
  * The pools are written here: all three are needed, each inside a registered
  * pool (arl_net_set_pool) with room for pool_len entries, and pool_len >= 2;

@@ -1,8 +1,9 @@
 #!/usr/bin/env python
-"""What the device-resident Catch costs: the env-step kernel as a store stream, and the closed loop in a window.
+"""What the device-resident envs cost: the env-step kernel as a store stream, and the closed loop in a window.
 
 Three measurements, arms interleaved within every round (one process, one device):
-  step     arl_env_step alone at 512 envs (C4, FF) and 1,024 envs (C3's frames, LSTM): microseconds per launch
+  step     arl_env_step alone, Catch's ("env_step") and Breakout's ("breakout_step", from the reset state: all 120
+           bricks to render) at 512 envs (C4, FF) and 1,024 envs (C3's frames, LSTM): microseconds per launch
            over back-to-back launches between two events, and the store rate on the 201,600 x n bytes it writes;
            beside it arl_stream_copy of the same byte count, every mode, whose best is the yardstick
            (a copy moves each byte twice, so its rate is quoted on bytes written, as the env's is);
@@ -12,9 +13,11 @@ Three measurements, arms interleaved within every round (one process, one device
            observation's share.  Run once per library build (ASYNCRL_HIP_LIB), processes alternating, to A/B a
            change of the render's stores with the launch that reads them timed in both arms (how plain stores
            were chosen over non-temporal ones: DESIGN.md, "Device environment").
+--env breakout attaches DeviceBreakout instead of DeviceCatch in the window and handoff measurements.
 One JSON line (and --out FILE).
 
-    python scripts/device_env_cost.py [--rounds 5] [--launches 40] [--windows 200] [--only step,window,handoff]
+    python scripts/device_env_cost.py [--env catch|breakout] [--rounds 5] [--launches 40] [--windows 200]
+                                      [--only step,window,handoff]
 """
 import argparse
 import json
@@ -47,7 +50,7 @@ def timed_us(fn, launches, stream):
     return 1e3 * a.elapsed_time(b) / launches
 
 
-def setup(kind, n, dev, stream, P=2):
+def setup(kind, n, dev, stream, P=2, game="catch"):
     T, A = 5, 4
     model = (pkg.A3CFF if kind == "ff" else pkg.A3CLSTM)(A, n_envs=n, t_max=T, seed=1234, init_seed=0, device=dev,
                                                          frames="pairs")
@@ -55,7 +58,7 @@ def setup(kind, n, dev, stream, P=2):
     opt.add_hook(pkg.GradientClipping(40))
     opt.anneal_total_steps, opt.n_total_envs = 8 * 10 ** 7, n
     agent = pkg.A3C(model, opt, T, 0.99, beta=1e-2, collectives=False)
-    env = pkg.DeviceCatch(n, device=dev, seed=1234)
+    env = (pkg.DeviceBreakout if game == "breakout" else pkg.DeviceCatch)(n, device=dev, seed=1234)
     pools = env.make_pools(P)
     net = model.net
     net.set_env(env)
@@ -72,7 +75,9 @@ def measure_step(kind, n, dev, stream, rounds, launches):
     src = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     dst = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     h = stream_handle(stream)
-    arms = {"env_step": lambda: net.env_step(0, *pools, 2, stream=stream)}
+    _, bnet, benv, bpools = setup(kind, n, dev, stream, game="breakout")
+    arms = {"env_step": lambda: net.env_step(0, *pools, 2, stream=stream),
+            "breakout_step": lambda: bnet.env_step(0, *bpools, 2, stream=stream)}
     for mode, blocks in ((0, 2048), (1, 2048), (2, 1), (3, 1)):
         arms["copy_mode%d" % mode] = (lambda m=mode, b=blocks: check(
             lib.arl_stream_copy(ptr(src), ptr(dst), nbytes, b, m, h), "arl_stream_copy"))
@@ -81,16 +86,18 @@ def measure_step(kind, n, dev, stream, rounds, launches):
         for k, fn in arms.items():
             us[k].append(timed_us(fn, launches, stream))
     med = {k: float(np.median(v)) for k, v in us.items()}
-    best = min((k for k in med if k != "env_step"), key=med.get)
+    best = min((k for k in med if k.startswith("copy")), key=med.get)
     rate = {k: nbytes / (1e-6 * v) / 1e12 for k, v in med.items()}     # TB/s of bytes written
     return {"kind": kind, "n_envs": n, "bytes_written": nbytes, "median_us": {k: round(v, 2) for k, v in med.items()},
             "write_TBps": {k: round(v, 3) for k, v in rate.items()}, "best_copy": best,
             "env_over_best_copy_rate": round(rate["env_step"] / rate[best], 3),
+            "breakout_over_best_copy_rate": round(rate["breakout_step"] / rate[best], 3),
+            "breakout_over_catch_time": round(med["breakout_step"] / med["env_step"], 3),
             "us": {k: [round(x, 2) for x in v] for k, v in us.items()}}
 
 
-def measure_window(dev, stream, rounds, windows):
-    agent, net, env, pools = setup("ff", 512, dev, stream)
+def measure_window(dev, stream, rounds, windows, game="catch"):
+    agent, net, env, pools = setup("ff", 512, dev, stream, game=game)
     graphs = {}
     for name in ("closed_loop", "detached"):
         net.set_env(env if name == "closed_loop" else None)
@@ -113,14 +120,14 @@ def measure_window(dev, stream, rounds, windows):
             torch.cuda.synchronize()
             ms[name].append(1e3 * (time.perf_counter() - t0) / windows)
     med = {k: float(np.median(v)) for k, v in ms.items()}
-    return {"shape": "c4", "n_envs": 512, "replays_per_round": windows,
+    return {"shape": "c4", "env": game, "n_envs": 512, "replays_per_round": windows,
             "median_window_ms": {k: round(v, 5) for k, v in med.items()},
             "env_cost_us_per_window": round(1e3 * (med["closed_loop"] - med["detached"]), 2),
             "window_ms": {k: [round(x, 5) for x in v] for k, v in ms.items()}}
 
 
-def measure_handoff(dev, stream, rounds, launches):
-    agent, net, env, pools = setup("ff", 512, dev, stream)
+def measure_handoff(dev, stream, rounds, launches, game="catch"):
+    agent, net, env, pools = setup("ff", 512, dev, stream, game=game)
 
     def step():
         net.env_step(0, *pools, 2, stream=stream)
@@ -134,13 +141,14 @@ def measure_handoff(dev, stream, rounds, launches):
         us["env_step"].append(timed_us(step, launches, stream))
         us["env_step_then_observe"].append(timed_us(step_observe, launches, stream))
     med = {k: float(np.median(v)) for k, v in us.items()}
-    return {"n_envs": 512, "median_us": {k: round(v, 2) for k, v in med.items()},
+    return {"env": game, "n_envs": 512, "median_us": {k: round(v, 2) for k, v in med.items()},
             "observe_after_env_us": round(med["env_step_then_observe"] - med["env_step"], 2),
             "us": {k: [round(x, 2) for x in v] for k, v in us.items()}}
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--env", choices=("catch", "breakout"), default="catch")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--launches", type=int, default=40)
     ap.add_argument("--windows", type=int, default=200)
@@ -156,9 +164,9 @@ def main():
         out["step"] = [measure_step("ff", 512, dev, stream, a.rounds, a.launches),
                        measure_step("lstm", 1024, dev, stream, a.rounds, a.launches)]
     if "window" in only:
-        out["window"] = measure_window(dev, stream, a.rounds, a.windows)
+        out["window"] = measure_window(dev, stream, a.rounds, a.windows, a.env)
     if "handoff" in only:
-        out["handoff"] = measure_handoff(dev, stream, a.rounds, a.launches)
+        out["handoff"] = measure_handoff(dev, stream, a.rounds, a.launches, a.env)
     print(json.dumps(out), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

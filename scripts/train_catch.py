@@ -1,18 +1,22 @@
 #!/usr/bin/env python
-"""Closed-loop training on the device-resident Catch (asyncrl_amd.DeviceCatch): the learner has to learn.
+"""Closed-loop training on a device-resident env (asyncrl_amd.DeviceCatch, or DeviceBreakout with --env breakout):
+the learner has to learn.
 
 env -> phi -> forward -> sample -> env -> ... -> update runs on the device with no host work per step: window 0
 eagerly (first=True), then one captured window replayed.  Every --report windows the learning curve is read
 from the device-side episode statistics (A3C.episode_stats(clear=True): the episodes completed since the
 last read) together with the newest per-window record (A3C.window_stats).  The optimum is +1 per episode, a
-uniform random policy scores about -0.70.
+uniform random policy scores about -0.70.  With --env breakout an episode is a life (a life loss is terminal, as
+the reference trains), the return is the raw, unclipped sum of its brick values, and a uniform random policy
+scores about 0.14 per life.
 
 Defaults are the reference's hyperparameters (RMSpropAsync lr 7e-4, alpha 0.99, eps 0.1, clip 40, beta 0.01,
 gamma 0.99) on the FF model with 256 envs; the batched learner sums the gradient of all envs, so --batch-loss
 mean, --opt adam and --gae-lambda are there to try.  One JSON line at the end (and --out FILE).
 
-    python scripts/train_catch.py [--windows 4000] [--report 200] [--envs 256] [--seed 0] [--lr 7e-4]
-                                  [--opt rmsprop|adam] [--batch-loss sum|mean] [--gae-lambda 1.0] [--arch ff|lstm]
+    python scripts/train_catch.py [--env catch|breakout] [--windows 4000] [--report 200] [--envs 256] [--seed 0]
+                                  [--lr 7e-4] [--opt rmsprop|adam] [--batch-loss sum|mean] [--gae-lambda 1.0]
+                                  [--arch ff|lstm]
 """
 import argparse
 import json
@@ -29,7 +33,7 @@ import asyncrl_amd as pkg  # noqa: E402
 
 
 def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", batch_loss="sum", gae_lambda=1.0,
-          arch="ff", beta=1e-2, eps=None, device="cuda:0", log=print):
+          arch="ff", beta=1e-2, eps=None, device="cuda:0", log=print, env="catch"):
     """Returns the curve: one dict per report with the window count, the episodes completed since the last
     report and their mean return, and the newest window record's entropy / value / gradient norm."""
     dev = torch.device(device)
@@ -46,9 +50,9 @@ def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", ba
     net = model.net
     net.set_episode_stats(True)
     net.set_window_stats(True)
-    env = pkg.DeviceCatch(envs, device=dev, seed=seed)
-    pools = env.make_pools(P)
-    net.set_env(env)
+    game = (pkg.DeviceBreakout if env == "breakout" else pkg.DeviceCatch)(envs, device=dev, seed=seed)
+    pools = game.make_pools(P)
+    net.set_env(game)
     stream = torch.cuda.Stream(device=dev)
     stream.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(stream):
@@ -80,6 +84,7 @@ def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", ba
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--env", choices=("catch", "breakout"), default="catch")
     ap.add_argument("--envs", type=int, default=256)
     ap.add_argument("--windows", type=int, default=4000)
     ap.add_argument("--report", type=int, default=200)
