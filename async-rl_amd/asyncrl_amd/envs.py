@@ -206,37 +206,23 @@ class VecALE:
         self.pool.shutdown(wait=True)
 
 
-class DeviceCatch:
-    """Catch on the device (include/asyncrl_hip.h, "device environment"): the
-    env of the closed actor-learner loop.  It owns the double-buffered env state
-    (2, n, 8) int32; one kernel launch per env-step moves every env and renders
-    its 210x160x3 frame pair.  Two ways to run it:
-
-    * attached to a net -- net.set_env(env), net.env_reset(*pools, pool_len),
-      then A3C.run_window(*pools, pool_len, first=True) and on: the window steps
-      the env from the actions it sampled, with no host work per step
-      (make_pools builds the pools; seed and env_offset must be the net's);
-    * granular, VecALE's surface -- reset() / step(actions) -> (pairs, r, d)
-      device tensors (n, 2, 210, 160, 3) uint8 / (n,) f32 / (n,) uint8, so
-      A3C.act_batch and evaluation.run_episodes take it unchanged.
-
-    Actions: 2 = right, 3 = left, anything else a no-op (n_actions >= 4).  Every
-    episode lasts 14 env-steps and returns +1 (caught) or -1."""
+class _DeviceEnv:
+    """What the device envs share: the double-buffered state, the pools and
+    the granular reset() / step().  A subclass gives `kind`, `STATE_INTS`,
+    `_state_bytes` and the library's two calls, `_reset` and `_step`."""
 
     envs = ()        # no host emulators behind it (evaluation.run_episodes walks this)
-    kind = ENV_CATCH   # what DeviceNet.set_env hands arl_net_set_env
+    number_of_actions = 4
 
     def __init__(self, n_envs: int, device=None, seed: int = 0, env_offset: int = 0):
         if n_envs < 1:
-            raise ValueError("DeviceCatch: n_envs must be >= 1")
+            raise ValueError(f"{type(self).__name__}: n_envs must be >= 1")
         self.n, self.seed, self.env_offset = n_envs, seed, env_offset
         self.device = torch.device(device if device is not None else "cuda")
-        self.state = torch.zeros(lib.arl_catch_state_bytes(n_envs) // 4, dtype=torch.int32,
-                                 device=self.device).view(2, n_envs, CATCH_STATE_INTS)
+        self.state = torch.zeros(self._state_bytes(n_envs) // 4, dtype=torch.int32,
+                                 device=self.device).view(2, n_envs, self.STATE_INTS)
         self.parity = 0          # the state half the granular calls read next
         self._out = None
-
-    number_of_actions = 4
 
     def make_pools(self, pool_len: int):
         """(pairs, rewards, dones) pools of pool_len >= 2 entries, zeroed."""
@@ -254,22 +240,22 @@ class DeviceCatch:
         return self._out
 
     def reset(self, stream=None):
-        """Episode 0 of every env (arl_catch_reset) -> (pairs, r = 0, d = 0)."""
+        """The first episode of every env -> (pairs, r = 0, d = 0)."""
         pairs, r, d = self._buffers()
         self.parity = 0
-        check(lib.arl_catch_reset(ptr(self.state), self.n, self.env_offset, self.seed, self.parity, ptr(pairs), ptr(r),
-                                  ptr(d), stream_handle(stream)), "arl_catch_reset")
+        self._reset(ptr(self.state), self.n, self.env_offset, self.seed, self.parity, ptr(pairs), ptr(r), ptr(d),
+                    stream_handle(stream))
         return pairs, r, d
 
     def step(self, actions, stream=None):
-        """One env-step of every env (arl_catch_step); actions: (n,) integers.
-        The returned tensors are rewritten by the next call."""
+        """One env-step of every env; actions: (n,) integers.  The returned
+        tensors are rewritten by the next call."""
         a = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
         if a.shape != (self.n,):
-            raise ValueError(f"DeviceCatch.step: need {self.n} actions")
+            raise ValueError(f"{type(self).__name__}.step: need {self.n} actions")
         pairs, r, d = self._buffers()
-        check(lib.arl_catch_step(ptr(self.state), self.parity, ptr(a), self.n, self.env_offset, self.seed, ptr(pairs),
-                                 ptr(r), ptr(d), stream_handle(stream)), "arl_catch_step")
+        self._step(ptr(self.state), self.parity, ptr(a), self.n, self.env_offset, self.seed, ptr(pairs), ptr(r),
+                   ptr(d), stream_handle(stream))
         self.parity ^= 1
         return pairs, r, d
 
@@ -277,7 +263,35 @@ class DeviceCatch:
         pass
 
 
-class DeviceBreakout:
+class DeviceCatch(_DeviceEnv):
+    """Catch on the device (include/asyncrl_hip.h, "device environment"): the
+    env of the closed actor-learner loop.  It owns the double-buffered env state
+    (2, n, 8) int32; one kernel launch per env-step moves every env and renders
+    its 210x160x3 frame pair.  Two ways to run it:
+
+    * attached to a net -- net.set_env(env), net.env_reset(*pools, pool_len),
+      then A3C.run_window(*pools, pool_len, first=True) and on: the window steps
+      the env from the actions it sampled, with no host work per step
+      (make_pools builds the pools; seed and env_offset must be the net's);
+    * granular, VecALE's surface -- reset() / step(actions) -> (pairs, r, d)
+      device tensors (n, 2, 210, 160, 3) uint8 / (n,) f32 / (n,) uint8, so
+      A3C.act_batch and evaluation.run_episodes take it unchanged.
+
+    Actions: 2 = right, 3 = left, anything else a no-op (n_actions >= 4).  Every
+    episode lasts 14 env-steps and returns +1 (caught) or -1."""
+
+    kind = ENV_CATCH   # what DeviceNet.set_env hands arl_net_set_env
+    STATE_INTS = CATCH_STATE_INTS
+    _state_bytes = staticmethod(lib.arl_catch_state_bytes)
+
+    def _reset(self, *args):
+        check(lib.arl_catch_reset(*args), "arl_catch_reset")
+
+    def _step(self, *args):
+        check(lib.arl_catch_step(*args), "arl_catch_step")
+
+
+class DeviceBreakout(_DeviceEnv):
     """Breakout on the device (include/asyncrl_hip.h, "device environment"; the
     rules are there): DeviceCatch's surface over a game with 120 bricks that
     persist across lives, brick rewards of 1, 4 and 7 (raw, unclipped), five
@@ -287,48 +301,20 @@ class DeviceBreakout:
     over.  False (evaluation, a3c_ale.py:75-76; what evaluation.run_episodes
     wants): done = game over only.  The two differ in nothing else."""
 
-    envs = ()
-    number_of_actions = 4
+    STATE_INTS = BREAKOUT_STATE_INTS
+    _state_bytes = staticmethod(lib.arl_breakout_state_bytes)
 
     def __init__(self, n_envs: int, device=None, seed: int = 0, env_offset: int = 0, life_loss_terminal: bool = True):
-        if n_envs < 1:
-            raise ValueError("DeviceBreakout: n_envs must be >= 1")
-        self.n, self.seed, self.env_offset = n_envs, seed, env_offset
+        super().__init__(n_envs, device, seed, env_offset)
         self.life_loss_terminal = bool(life_loss_terminal)
         self.flags = 0 if self.life_loss_terminal else ENV_GAME_OVER_ONLY
         self.kind = ENV_BREAKOUT | self.flags
-        self.device = torch.device(device if device is not None else "cuda")
-        self.state = torch.zeros(lib.arl_breakout_state_bytes(n_envs) // 4, dtype=torch.int32,
-                                 device=self.device).view(2, n_envs, BREAKOUT_STATE_INTS)
-        self.parity = 0          # the state half the granular calls read next
-        self._out = None
 
-    make_pools = DeviceCatch.make_pools
-    _buffers = DeviceCatch._buffers
+    def _reset(self, *args):
+        check(lib.arl_breakout_reset(*args), "arl_breakout_reset")
 
-    def reset(self, stream=None):
-        """A new game of every env (arl_breakout_reset) -> (pairs, r = 0, d = 0)."""
-        pairs, r, d = self._buffers()
-        self.parity = 0
-        check(lib.arl_breakout_reset(ptr(self.state), self.n, self.env_offset, self.seed, self.parity, ptr(pairs),
-                                     ptr(r), ptr(d), stream_handle(stream)), "arl_breakout_reset")
-        return pairs, r, d
-
-    def step(self, actions, stream=None):
-        """One env-step of every env (arl_breakout_step); actions: (n,) integers.
-        The returned tensors are rewritten by the next call."""
-        a = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
-        if a.shape != (self.n,):
-            raise ValueError(f"DeviceBreakout.step: need {self.n} actions")
-        pairs, r, d = self._buffers()
-        check(lib.arl_breakout_step(ptr(self.state), self.parity, ptr(a), self.n, self.env_offset, self.seed,
-                                    self.flags, ptr(pairs), ptr(r), ptr(d), stream_handle(stream)),
-              "arl_breakout_step")
-        self.parity ^= 1
-        return pairs, r, d
-
-    def close(self):
-        pass
+    def _step(self, state, parity, actions, n, env_offset, seed, *out):   # the flags go before the outputs
+        check(lib.arl_breakout_step(state, parity, actions, n, env_offset, seed, self.flags, *out), "arl_breakout_step")
 
 
 class _null:

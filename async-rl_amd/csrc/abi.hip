@@ -464,13 +464,13 @@ int arl_act(arl_net* h, int t, void* s) {
 }
 
 // ---------------------------------------------------------------- device environment
-int64_t arl_catch_state_bytes(int64_t n_envs) {
-  return n_envs < 0 ? -1 : 2 * n_envs * arl::CATCH_STATE_INTS * (int64_t)sizeof(int32_t);
+static int64_t env_state_bytes(int kind, int64_t n_envs) {
+  return n_envs < 0 ? -1 : 2 * n_envs * arl::env_state_ints(kind) * (int64_t)sizeof(int32_t);
 }
 
-int64_t arl_breakout_state_bytes(int64_t n_envs) {
-  return n_envs < 0 ? -1 : 2 * n_envs * arl::BREAKOUT_STATE_INTS * (int64_t)sizeof(int32_t);
-}
+int64_t arl_catch_state_bytes(int64_t n_envs) { return env_state_bytes(ARL_ENV_CATCH, n_envs); }
+
+int64_t arl_breakout_state_bytes(int64_t n_envs) { return env_state_bytes(ARL_ENV_BREAKOUT, n_envs); }
 
 // the granular calls: explicit pointers, one pool entry, the parity from the host; kind: ARL_ENV_* | flags
 static int env_granular(const char* who, int kind, int32_t* state, int parity, const int32_t* actions, bool step,
@@ -483,7 +483,7 @@ static int env_granular(const char* who, int kind, int32_t* state, int parity, c
   if (!state || !pair || !reward || !done || (step && !actions)) return fail(ARL_EINVAL, w + ": null pointer");
   if (!aligned(state, 16) || !aligned(pair, 16) || !aligned(reward, 4) || (step && !aligned(actions, 4)))
     return fail(ARL_EINVAL, w + ": state and frames 16-byte aligned, rewards and actions 4-byte aligned");
-  arl::CatchArgs a{};
+  arl::EnvArgs a{};
   a.state = state;
   a.actions = step ? actions : nullptr;
   a.ctl = nullptr;
@@ -498,9 +498,7 @@ static int env_granular(const char* who, int kind, int32_t* state, int parity, c
   a.env_offset = env_offset;
   a.seed_lo = (uint32_t)seed;
   a.seed_hi = (uint32_t)(seed >> 32);
-  if ((kind & ~ARL_ENV_GAME_OVER_ONLY) == ARL_ENV_BREAKOUT)
-    return hip_status(arl::launch_breakout(a, (kind & ARL_ENV_GAME_OVER_ONLY) != 0, S(s)), who);
-  return hip_status(arl::launch_catch(a, S(s)), who);
+  return hip_status(arl::launch_env(kind, a, S(s)), who);
 }
 
 int arl_catch_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, int parity, uint8_t* pair_out,
@@ -531,7 +529,7 @@ int arl_breakout_step(int32_t* state, int parity_in, const int32_t* actions, int
 
 int arl_net_set_env(arl_net* h, int kind, int32_t* state) {
   if (!h) return fail(ARL_EINVAL, "null net");
-  if (kind != ARL_ENV_CATCH && (kind & ~ARL_ENV_GAME_OVER_ONLY) != ARL_ENV_BREAKOUT)
+  if (!arl::env_kind_ok(kind))
     return fail(ARL_EINVAL,
                 "set_env: unknown env kind (ARL_ENV_CATCH, or ARL_ENV_BREAKOUT [| ARL_ENV_GAME_OVER_ONLY])");
   if (!state) {   // detach
@@ -550,7 +548,7 @@ int arl_net_set_env(arl_net* h, int kind, int32_t* state) {
 
 // validates an env launch of a bound net and fills its arguments (0 = ok); step == false: the reset
 static int env_args(arl_net* h, bool step, int t, int e0, int ne, uint8_t* pair_pool, float* reward_pool,
-                    uint8_t* done_pool, int64_t pool_len, arl::CatchArgs& a) {
+                    uint8_t* done_pool, int64_t pool_len, arl::EnvArgs& a) {
   arl::Net& n = h->net;
   if (!n.env_state) return fail(ARL_ESTATE, "env: no env attached (arl_net_set_env)");
   if (step && (t < 0 || t >= n.T)) return fail(ARL_EINVAL, "env_step: t out of [0, t_max)");
@@ -562,7 +560,7 @@ static int env_args(arl_net* h, bool step, int t, int e0, int ne, uint8_t* pair_
   if (int rc = check_pool(h, ARL_POOL_FRAMES, pair_pool, pool_len, (int64_t)arl::PAIR * n.N, "frame")) return rc;
   if (int rc = check_pool(h, ARL_POOL_REWARDS, reward_pool, pool_len, 4 * (int64_t)n.N, "reward")) return rc;
   if (int rc = check_pool(h, ARL_POOL_DONES, done_pool, pool_len, (int64_t)n.N, "done")) return rc;
-  a = arl::CatchArgs{};
+  a = arl::EnvArgs{};
   a.state = n.env_state;
   a.actions = step ? n.at<int32_t>(n.w_act) + (int64_t)t * n.N : nullptr;
   a.ctl = n.at<int64_t>(n.w_ctl);
@@ -580,17 +578,15 @@ static int env_args(arl_net* h, bool step, int t, int e0, int ne, uint8_t* pair_
   return 0;
 }
 
-static int env_launch(const arl::Net& n, const arl::CatchArgs& a, void* s, const char* what) {
-  hipError_t e = (n.env_kind & ~ARL_ENV_GAME_OVER_ONLY) == ARL_ENV_BREAKOUT
-                     ? arl::launch_breakout(a, (n.env_kind & ARL_ENV_GAME_OVER_ONLY) != 0, S(s))
-                     : arl::launch_catch(a, S(s));
+static int env_launch(const arl::Net& n, const arl::EnvArgs& a, void* s, const char* what) {
+  hipError_t e = arl::launch_env(n.env_kind, a, S(s));
   if (e == hipSuccess) e = arl::stamp(n, arl::STAGE_OTHER, S(s));
   return hip_status(e, what);
 }
 
 int arl_env_reset(arl_net* h, uint8_t* pair_pool, float* reward_pool, uint8_t* done_pool, int64_t pool_len, void* s) {
   NEED_BOUND(h);
-  arl::CatchArgs a;
+  arl::EnvArgs a;
   if (int rc = env_args(h, false, 0, 0, -1, pair_pool, reward_pool, done_pool, pool_len, a)) return rc;
   return env_launch(h->net, a, s, "env_reset");
 }
@@ -630,7 +626,7 @@ int arl_env_step(arl_net* h, int t, int e0, int ne, uint8_t* pair_pool, float* r
                  int64_t pool_len, void* s) {
   NEED_BOUND(h);
   if (int rc = check_env_range(h->net, e0, ne)) return rc;
-  arl::CatchArgs a;
+  arl::EnvArgs a;
   if (int rc = env_args(h, true, t, e0, ne, pair_pool, reward_pool, done_pool, pool_len, a)) return rc;
   return env_launch(h->net, a, s, "env_step");
 }
@@ -759,7 +755,7 @@ int arl_run_window(arl_net* h, const uint8_t* pair_pool, const float* reward_poo
   // an attached env steps after every act(t), t < T, into the pools the next observation reads (so it writes
   // them: the signature keeps the observing calls' const)
   const bool env = n.env_state != nullptr;
-  arl::CatchArgs ea;
+  arl::EnvArgs ea;
   if (env)
     if (int rc = env_args(h, true, 0, 0, -1, const_cast<uint8_t*>(pair_pool), const_cast<float*>(reward_pool),
                           const_cast<uint8_t*>(done_pool), pool_len, ea))

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/asyncrl_hip.h"
 #include "fastdiv.hpp"
 
 namespace arl {
@@ -134,12 +135,15 @@ hipError_t launch_episode_reset(char* block, int n, hipStream_t s);
 // envs in a fixed order (phi.hip episode_reduce_kernel); clear: also zero the cumulative per-env arrays
 hipError_t launch_episode_reduce(char* block, int n, double* out8, int clear, hipStream_t s);
 
-// Device-resident Catch (catch.hip; the header's "device environment"): one launch = one env-step (or the
-// reset) of envs [e0, e0 + ne): transition + render into pool entry (k + 1) % pool_len (reset: k % pool_len),
-// k = ctl[CTL_STEP] + t read on the device; the state half read is k & 1, the half written (k + 1) & 1.
-constexpr int CATCH_STATE_INTS = 8;   // [bx, by, vx, px, episode, steps_in_episode, 0, 0]
-struct CatchArgs {
-  int32_t* state;            // (2, n, CATCH_STATE_INTS), 16-byte aligned
+// Device-resident envs (env_kernel.hpp, with the games in catch.hip and breakout.hip; the header's "device
+// environment"): one launch = one env-step (or the reset) of envs [e0, e0 + ne): transition + render into pool
+// entry (k + 1) % pool_len (reset: k % pool_len), k = ctl[CTL_STEP] + t read on the device; the state half read
+// is k & 1, the half written (k + 1) & 1.
+constexpr int CATCH_STATE_INTS = 8;       // [bx, by, vx, px, episode, steps_in_episode, 0, 0]
+constexpr int BREAKOUT_STATE_INTS = 16;   // [bx, by, vx, vy, px, lives, serves, steps_in_episode, game, game_steps,
+                                          //  score, bricks_left, b0, b1, b2, b3]
+struct EnvArgs {
+  int32_t* state;            // (2, n, the game's STATE_INTS), 16-byte aligned
   const int32_t* actions;    // (n): the actions of observation k; null: reset (episode 0 into half k & 1)
   const int64_t* ctl;        // the control block; null: k = t (the granular calls: t = the parity, pool_len 1)
   int64_t t;
@@ -151,14 +155,23 @@ struct CatchArgs {
   int e0 = 0, ne = -1;       // env range of this launch: e0 + blockIdx.y, ne envs (-1: all n)
   int env_offset = 0;
   uint32_t seed_lo = 0, seed_hi = 0;
+  int flags = 0;             // ARL_ENV_GAME_OVER_ONLY or 0, filled by launch_env from the kind (Catch ignores it)
 };
-hipError_t launch_catch(const CatchArgs& a, hipStream_t s);
+struct Catch;      // the games: catch.hip and breakout.hip each instantiate their launch_game
+struct Breakout;
+template <class Game> hipError_t launch_game(const EnvArgs& a, hipStream_t s);   // env_kernel.hpp
+extern template hipError_t launch_game<Catch>(const EnvArgs&, hipStream_t);
+extern template hipError_t launch_game<Breakout>(const EnvArgs&, hipStream_t);
 
-// Device-resident Breakout (breakout.hip): the same launch shape and arguments as Catch's, over a state of
-// (2, n, BREAKOUT_STATE_INTS); game_over_only: a life loss is not a terminal (ARL_ENV_GAME_OVER_ONLY)
-constexpr int BREAKOUT_STATE_INTS = 16;   // [bx, by, vx, vy, px, lives, serves, steps_in_episode, game, game_steps,
-                                          //  score, bricks_left, b0, b1, b2, b3]
-hipError_t launch_breakout(const CatchArgs& a, bool game_over_only, hipStream_t s);
+// The library's only look at an env kind (ARL_ENV_*, a Breakout's with an optional ARL_ENV_GAME_OVER_ONLY).
+constexpr bool env_is_breakout(int kind) { return (kind & ~ARL_ENV_GAME_OVER_ONLY) == ARL_ENV_BREAKOUT; }
+constexpr bool env_kind_ok(int kind) { return kind == ARL_ENV_CATCH || env_is_breakout(kind); }
+constexpr int env_state_ints(int kind) { return env_is_breakout(kind) ? BREAKOUT_STATE_INTS : CATCH_STATE_INTS; }
+inline hipError_t launch_env(int kind, const EnvArgs& a, hipStream_t s) {
+  EnvArgs f = a;
+  f.flags = kind & ARL_ENV_GAME_OVER_ONLY;
+  return env_is_breakout(kind) ? launch_game<Breakout>(f, s) : launch_game<Catch>(f, s);
+}
 
 // RGB (Doom) observations, train_a3c_doom.py:21-23 / doom_env.py:47
 constexpr int RGB_MAX_W = 2048;   // staged source rows: 12 x W x 3 bytes of LDS
@@ -224,8 +237,8 @@ struct Net {
   float* adam_m = nullptr;
   double adam_beta1 = 0.9, adam_beta2 = 0.999;
   // arl_net_set_env: non-null = a device-resident env steps from the actions buffer (arl_env_step, and
-  // arl_run_window after every arl_act(t), t < T); its double-buffered state (2, N, CATCH_STATE_INTS or
-  // BREAKOUT_STATE_INTS) and the kind it was attached as (ARL_ENV_*, with ARL_ENV_GAME_OVER_ONLY or'ed in)
+  // arl_run_window after every arl_act(t), t < T); its double-buffered state (2, N, env_state_ints(env_kind))
+  // and the kind it was attached as (ARL_ENV_*, with ARL_ENV_GAME_OVER_ONLY or'ed in)
   int32_t* env_state = nullptr;
   int env_kind = 0;
   int64_t eval_draws = 0;  // sampling forward_states calls so far (Philox stream 1 counter)

@@ -1,37 +1,22 @@
 // Device-resident Breakout: the second device environment (include/asyncrl_hip.h, "device environment"), the
-// game the reference's published numbers are about, in catch.hip's shape.  One launch per env-step does the
-// transition and the render: it reads the actions the policy sampled, steps every env's 16 integers (ball,
-// paddle, lives, the 120 brick bits, the counters), and writes the (frame 4, frame 3) pair, the raw reward and
-// the done flag into the pool entry the next arl_observe reads.
+// game the reference's published numbers are about, as the hooks of env_kernel.hpp's skeleton.  A state of 16
+// integers (ball, paddle, lives, the 120 brick bits, the counters) and the raw reward; the transition every
+// workgroup recomputes is four int4 loads and a few hundred integer ops on wave-uniform values, one Philox
+// block when a ball is served.
 //
-// As in catch.hip no workgroup reads a word another workgroup of its launch writes: the env state is
-// double-buffered, every workgroup of an env recomputes the transition from the OLD half (four int4 loads and
-// a few hundred integer ops on wave-uniform values, one Philox block when a ball is served), and only band 0's
-// thread 0 writes the new half, the reward and the done.
-//
-// The render is a pure store stream, 2 x 210 rows x 480 bytes per env as 16-byte plain stores.  Only chunks on
-// the 36 brick rows, the ball's 4 rows and the paddle's 4 rows decide bytes; every other chunk is a zero store.
-// The two screens of a pair can differ in their bricks (a brick hit in frame 4), so each carries its own brick
-// bits.  No LDS, no tables in memory (the row colours are three 48-bit constants shifted by the brick row),
-// no loads besides the state, the action and the step counter.  Grid (BANDS, envs), as Catch's (DESIGN.md
-// "Device environment" has the measurements).
+// Only chunks on the 36 brick rows, the ball's 4 rows and the paddle's 4 rows decide bytes; every other chunk
+// is a zero store.  The two screens of a pair can differ in their bricks (a brick hit in frame 4), so each
+// carries its own brick bits.  No tables in memory (the row colours are three 48-bit constants shifted by the
+// brick row).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "arl_internal.hpp"
+#include "env_kernel.hpp"
 #include "policy_rows.hpp"
 
 namespace arl {
 
 namespace {
-
-constexpr int SCREEN_H = 210, SCREEN_W = 160;
-constexpr int ROW_CHUNKS = SCREEN_W * 3 / 16;                  // 30 16-byte chunks a row
-constexpr int PAIR_CHUNKS = 2 * SCREEN_H * ROW_CHUNKS;         // 12,600
-constexpr int BANDS = 5;                                       // workgroups per env
-constexpr int BAND_CHUNKS = PAIR_CHUNKS / BANDS;               // 2,520
-static_assert(PAIR_CHUNKS % BANDS == 0, "bands tile the pair");
-static_assert(PAIR == PAIR_CHUNKS * 16, "frame pair bytes");
 
 // the game's constants (include/asyncrl_hip.h)
 constexpr int BRICK_ROWS = 6, BRICK_COLS = 20, BRICK_H = 6, BRICK_Y0 = 57, BRICK_Y1 = BRICK_Y0 + BRICK_ROWS * BRICK_H;
@@ -43,8 +28,6 @@ constexpr uint32_t ENV_STREAM = 3;   // Philox counter word 3, beside 0 (window)
 // (72,160,72) (66,72,200)
 constexpr uint64_t ROW_R = 0x4248a2b4c6c8ull, ROW_G = 0x48a0a27a6c48ull, ROW_B = 0xc8482a303a48ull;
 constexpr uint64_t FULL_LO = ~0ull, FULL_HI = (1ull << 56) - 1;   // 120 bricks: words 0..2 full, 24 bits of word 3
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // the 120 brick bits travel as two 64-bit halves (words b0 | b1 << 32 and b2 | b3 << 32) and are picked by
 // shifts alone: a word chosen by an index would be an array in memory
@@ -131,38 +114,43 @@ __device__ inline void new_game(EnvState& st, uint32_t env_id, uint32_t seed_lo,
   serve(st, env_id, seed_lo, seed_hi);
 }
 
-__device__ inline Screen screen_of(const EnvState& st) { return Screen{st.bx, st.by, st.px, st.blo, st.bhi}; }
+}  // namespace
 
-struct BreakoutArgs {
-  CatchArgs c;          // the same arguments hold; state is (2, n, BREAKOUT_STATE_INTS)
-  int game_over_only;   // ARL_ENV_GAME_OVER_ONLY: a life loss is not a terminal
-};
+struct Breakout {
+  static constexpr int STATE_INTS = BREAKOUT_STATE_INTS;
+  using State = EnvState;
+  using Screen = arl::Screen;
+  using Reward = int;   // the sum of brick values, cast where it is stored
 
-__global__ void __launch_bounds__(256)
-breakout_kernel(BreakoutArgs ba) {
-  const CatchArgs& a = ba.c;
-  const int e = a.e0 + blockIdx.y;
-  const bool reset = a.actions == nullptr;
-  const int64_t k = (a.ctl != nullptr ? a.ctl[CTL_STEP] : 0) + a.t;   // the observation the actions answer
-  const int64_t kout = reset ? k : k + 1;                             // the observation this launch produces
-  const uint32_t pidx = fd_mod64(a.dpool, (uint64_t)kout);
-  const uint32_t env_id = (uint32_t)(a.env_offset + e);
-
-  EnvState st;
-  Screen cur, prev;
-  int reward = 0;
-  bool done = false;
-  if (reset) {
-    st = EnvState{};
-    new_game(st, env_id, a.seed_lo, a.seed_hi);
-    cur = prev = screen_of(st);
-  } else {
-    const int4* old = reinterpret_cast<const int4*>(a.state + ((int64_t)(k & 1) * a.n + e) * BREAKOUT_STATE_INTS);
+  __device__ static State start(uint32_t env_id, uint32_t seed_lo, uint32_t seed_hi) {
+    State st{};
+    new_game(st, env_id, seed_lo, seed_hi);
+    return st;
+  }
+  __device__ static State load(const int4* old) {
     const int4 o0 = old[0], o1 = old[1], o2 = old[2], o3 = old[3];
-    const int act = a.actions[e];
-    st = EnvState{o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w, o2.x, o2.y, o2.z, o2.w,
-                  (uint64_t)(uint32_t)o3.x | (uint64_t)(uint32_t)o3.y << 32,
-                  (uint64_t)(uint32_t)o3.z | (uint64_t)(uint32_t)o3.w << 32};
+    return State{o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w, o2.x, o2.y, o2.z, o2.w,
+                 (uint64_t)(uint32_t)o3.x | (uint64_t)(uint32_t)o3.y << 32,
+                 (uint64_t)(uint32_t)o3.z | (uint64_t)(uint32_t)o3.w << 32};
+  }
+  __device__ static void store(int4* out, const State& st) {
+    out[0] = make_int4(st.bx, st.by, st.vx, st.vy);
+    out[1] = make_int4(st.px, st.lives, st.serves, st.steps);
+    out[2] = make_int4(st.game, st.game_steps, st.score, st.left);
+    out[3] = make_int4((int)(uint32_t)st.blo, (int)(uint32_t)(st.blo >> 32), (int)(uint32_t)st.bhi,
+                       (int)(uint32_t)(st.bhi >> 32));
+  }
+  __device__ static Screen screen_of(const State& st) { return Screen{st.bx, st.by, st.px, st.blo, st.bhi}; }
+  // (field by field: a select between the two structs would put them in scratch memory)
+  __device__ static Screen pick(bool second, const Screen& cur, const Screen& prev) {
+    return Screen{second ? prev.bx : cur.bx, second ? prev.by : cur.by, second ? prev.px : cur.px,
+                  second ? prev.blo : cur.blo, second ? prev.bhi : cur.bhi};
+  }
+  __device__ static u32x4 chunk(int r, int c, const Screen& s) { return breakout_chunk(r, c, s); }
+
+  // flags: ARL_ENV_GAME_OVER_ONLY (a life loss is not a terminal) or 0
+  __device__ static void step(State& st, int act, uint32_t env_id, uint32_t seed_lo, uint32_t seed_hi, int flags,
+                              Screen& cur, Screen& prev, Reward& reward, bool& done) {
     cur = prev = screen_of(st);
     bool lost = false;
     for (int f = 0; f < 4; ++f) {
@@ -198,7 +186,9 @@ breakout_kernel(BreakoutArgs ba) {
         if (st.bx + BALL > st.px && st.bx < st.px + PADDLE_W) {
           st.by = 2 * (PADDLE_Y - BALL) - st.by;
           st.vy = -st.vy;
-          st.vx = paddle_vx(min(max(st.bx + BALL / 2 - st.px, 0), PADDLE_W - 1) >> 2);
+          // (the clamp compiles to v_med3_i32, a vector op on a wave-uniform value: taken back to a scalar
+          // register at once, or the compiler may move the rest of the transition to the vector unit after it)
+          st.vx = __builtin_amdgcn_readfirstlane(paddle_vx(min(max(st.bx + BALL / 2 - st.px, 0), PADDLE_W - 1) >> 2));
         } else {
           st.lives -= 1;
           lost = true;
@@ -213,49 +203,17 @@ breakout_kernel(BreakoutArgs ba) {
     const bool over = st.lives == 0 || st.left == 0 || st.game_steps >= STEP_CAP;
     if (over) {   // the next game starts at once; its first screen twice, the last one is never shown
       st.game += 1;
-      new_game(st, env_id, a.seed_lo, a.seed_hi);
+      new_game(st, env_id, seed_lo, seed_hi);
       cur = prev = screen_of(st);
     } else if (lost) {   // bricks, lives, score and the paddle are kept
-      serve(st, env_id, a.seed_lo, a.seed_hi);
+      serve(st, env_id, seed_lo, seed_hi);
       cur = prev = screen_of(st);
     }
-    done = over || (lost && !ba.game_over_only);
+    done = over || (lost && !flags);
     if (done) st.steps = 0;
   }
+};
 
-  const int64_t row = (int64_t)pidx * a.n + e;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    int4* out = reinterpret_cast<int4*>(a.state + ((int64_t)(kout & 1) * a.n + e) * BREAKOUT_STATE_INTS);
-    out[0] = make_int4(st.bx, st.by, st.vx, st.vy);
-    out[1] = make_int4(st.px, st.lives, st.serves, st.steps);
-    out[2] = make_int4(st.game, st.game_steps, st.score, st.left);
-    out[3] = make_int4((int)(uint32_t)st.blo, (int)(uint32_t)(st.blo >> 32), (int)(uint32_t)st.bhi,
-                       (int)(uint32_t)(st.bhi >> 32));
-    a.reward_pool[row] = (float)reward;
-    a.done_pool[row] = done ? 1 : 0;
-  }
-
-  u32x4* dst = reinterpret_cast<u32x4*>(a.pair_pool + row * PAIR);
-  const int q0 = blockIdx.x * BAND_CHUNKS;
-#pragma unroll 2
-  for (int i = threadIdx.x; i < BAND_CHUNKS; i += 256) {
-    const int q = q0 + i, row2 = q / ROW_CHUNKS, c = q - row2 * ROW_CHUNKS;
-    const bool second = row2 >= SCREEN_H;   // pair[1]: the screen one frame earlier
-    // (field by field: a select between the two structs would put them in scratch memory)
-    const Screen s{second ? prev.bx : cur.bx, second ? prev.by : cur.by, second ? prev.px : cur.px,
-                   second ? prev.blo : cur.blo, second ? prev.bhi : cur.bhi};
-    dst[q] = breakout_chunk(second ? row2 - SCREEN_H : row2, c, s);   // plain stores, as Catch's
-  }
-}
-
-}  // namespace
-
-hipError_t launch_breakout(const CatchArgs& a, bool game_over_only, hipStream_t s) {
-  const int ne = a.ne < 0 ? a.n : a.ne;
-  if (ne <= 0) return hipSuccess;
-  hipLaunchKernelGGL(breakout_kernel, dim3(BANDS, (unsigned)ne), dim3(256), 0, s,
-                     BreakoutArgs{a, game_over_only ? 1 : 0});
-  return hipGetLastError();
-}
+template hipError_t launch_game<Breakout>(const EnvArgs&, hipStream_t);
 
 }  // namespace arl

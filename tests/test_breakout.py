@@ -3,7 +3,6 @@ invariants, the random-policy mean per life is the recorded constant, the two do
 in nothing but the done byte and the per-episode step counter, and the Breakout entry points of
 the C ABI validate their arguments on the host, before any launch (fake, never-dereferenced
 device pointers; no GPU here)."""
-import ctypes
 import os
 import re
 
@@ -12,6 +11,7 @@ import pytest
 
 import breakout_ref as B
 from conftest import ROOT
+from test_catch import make_net
 
 OK, EINVAL, ESTATE = 0, 1, 3
 ENV_CATCH, ENV_BREAKOUT, GAME_OVER_ONLY = 1, 2, 0x100
@@ -130,16 +130,6 @@ def test_granular_calls_validate():
     assert lib.arl_breakout_step(st, 0, ac, -1, 0, 0, 0, pr, rw, dn, None) == EINVAL
 
 
-def make_net(arch=0, A=4, N=4, T=5, bind=True):
-    from asyncrl_amd._lib import lib
-    h = ctypes.c_void_p()
-    assert lib.arl_net_create(ctypes.byref(h), arch, A, N, T, 0, 0) == 0
-    if bind:
-        fake = 1 << 40
-        assert lib.arl_net_bind(h, fake, fake, fake, fake) == 0
-    return h
-
-
 @pytest.mark.parametrize("bind", [False, True])
 def test_set_env_validation(bind):
     """Kind 2 and 2 | 0x100 attach to FF, LSTM and Nature nets with A >= 4, on an unbound and on a
@@ -183,11 +173,11 @@ def test_set_env_validation(bind):
     assert lib.arl_net_set_env(None, ENV_BREAKOUT, state) == EINVAL
 
 
-@pytest.mark.parametrize("kind", [ENV_BREAKOUT, ENV_BREAKOUT | GAME_OVER_ONLY])
+@pytest.mark.parametrize("kind", [ENV_CATCH, ENV_BREAKOUT, ENV_BREAKOUT | GAME_OVER_ONLY])
 def test_env_calls_fail_before_any_launch(kind):
-    """arl_env_reset / arl_env_step / arl_run_window with a Breakout attached: pool_len = 1,
-    unregistered or too short pools, a missing pool and t = t_max are ARL_EINVAL; no env attached
-    is ARL_ESTATE (Catch's checks, test_catch.py)."""
+    """arl_env_reset / arl_env_step / arl_run_window with an env of either game attached: pool_len = 1,
+    unregistered or too short pools, a missing pool and t = t_max are ARL_EINVAL; no env attached is
+    ARL_ESTATE."""
     from asyncrl_amd._lib import POOL_DONES, POOL_FRAMES, POOL_REWARDS, lib
     N, T = 4, 5
     h = make_net(0, 4, N, T)
@@ -205,6 +195,7 @@ def test_env_calls_fail_before_any_launch(kind):
         assert step() == ESTATE and b"no env" in lib.arl_last_error()
         assert lib.arl_env_reset(h, pairs, rew, done, 2, None) == ESTATE
         assert lib.arl_net_set_env(h, kind, state) == OK
+        # unregistered pools
         assert step() == EINVAL and b"not registered" in lib.arl_last_error()
         assert lib.arl_env_reset(h, pairs, rew, done, 2, None) == EINVAL
         assert window() == EINVAL
@@ -212,21 +203,26 @@ def test_env_calls_fail_before_any_launch(kind):
         assert step() == EINVAL and b"reward" in lib.arl_last_error()
         assert lib.arl_net_set_pool(h, POOL_REWARDS, rew, 3 * N * 4) == 0
         assert lib.arl_net_set_pool(h, POOL_DONES, done, 3 * N) == 0
+        # pool_len = 1 (and below): the env writes the entry after the one just read
         for bad in (1, 0, -3):
             assert step(L=bad) == EINVAL and b"pool_len" in lib.arl_last_error()
             assert lib.arl_env_reset(h, pairs, rew, done, bad, None) == EINVAL
         assert window(1) == EINVAL and b"pool_len" in lib.arl_last_error()
+        # pools too short for pool_len
         assert step(L=4) == EINVAL and b"exceeds" in lib.arl_last_error()
         assert lib.arl_env_reset(h, pairs, rew, done, 4, None) == EINVAL
         assert window(4) == EINVAL and b"exceeds" in lib.arl_last_error()
         assert lib.arl_net_set_pool(h, POOL_DONES, done, 2 * N) == 0            # only the done pool too short
         assert step(L=3) == EINVAL and b"done" in lib.arl_last_error()
         assert lib.arl_net_set_pool(h, POOL_DONES, done, 3 * N) == 0
+        # the env writes all three pools
         assert step(r=None) == EINVAL and step(d=None) == EINVAL and step(p=None) == EINVAL
         assert step(p=pairs + 8) == EINVAL                                       # misaligned frames
+        # t in [0, t_max); the env range rules of arl_observe_envs
         assert step(t=T) == EINVAL and b"t_max" in lib.arl_last_error()
         assert step(t=-1) == EINVAL
         assert step(e0=1, ne=3) == EINVAL and step(e0=0, ne=N + 1) == EINVAL and step(ne=0) == EINVAL
+        # detached again: the env calls are refused, the window is an ordinary one
         assert lib.arl_net_set_env(h, kind, None) == OK
         assert step() == ESTATE
     finally:

@@ -11,7 +11,6 @@ import catch_ref as C
 
 OK, EINVAL, ESTATE = 0, 1, 3
 ENV_CATCH = 1
-PAIR = 2 * 210 * 160 * 3
 
 
 def play(n, steps, policy, seed=11, env_offset=0):
@@ -75,6 +74,7 @@ def test_random_policy_mean_is_the_recorded_constant():
 
 
 def make_net(arch=0, A=4, N=4, T=5, bind=True):
+    """(test_breakout.py takes it from here; its test_env_calls_fail_before_any_launch covers both games)"""
     from asyncrl_amd._lib import lib
     h = ctypes.c_void_p()
     assert lib.arl_net_create(ctypes.byref(h), arch, A, N, T, 0, 0) == 0
@@ -111,60 +111,6 @@ def test_set_env_validation():
         finally:
             lib.arl_net_destroy(h)
     assert lib.arl_net_set_env(None, ENV_CATCH, state) == EINVAL
-
-
-def test_env_calls_fail_before_any_launch():
-    """arl_env_reset / arl_env_step / arl_run_window with an env attached: pool_len = 1, unregistered
-    or too short pools, a missing pool and t = t_max are ARL_EINVAL; no env attached is ARL_ESTATE."""
-    from asyncrl_amd._lib import POOL_DONES, POOL_FRAMES, POOL_REWARDS, lib
-    N, T = 4, 5
-    h = make_net(0, 4, N, T)
-    try:
-        fake = 1 << 40
-        pairs, rew, done, state = fake + (1 << 30), fake + (2 << 30), fake + (3 << 30), fake + (5 << 30)
-
-        def step(t=0, L=2, p=pairs, r=rew, d=done, e0=0, ne=N):
-            return lib.arl_env_step(h, t, e0, ne, p, r, d, L, None)
-
-        def window(L=2):
-            return lib.arl_run_window(h, pairs, rew, done, L, 1, 0, 0.99, 0.01, 0.5, 1, 7e-4, 0, 0, 0.99, 0.1, 40.0,
-                                      None)
-
-        assert step() == ESTATE and b"no env" in lib.arl_last_error()
-        assert lib.arl_env_reset(h, pairs, rew, done, 2, None) == ESTATE
-        assert lib.arl_net_set_env(h, ENV_CATCH, state) == OK
-        # unregistered pools
-        assert step() == EINVAL and b"not registered" in lib.arl_last_error()
-        assert lib.arl_env_reset(h, pairs, rew, done, 2, None) == EINVAL
-        assert window() == EINVAL
-        assert lib.arl_net_set_pool(h, POOL_FRAMES, pairs, 3 * N * PAIR) == 0
-        assert step() == EINVAL and b"reward" in lib.arl_last_error()
-        assert lib.arl_net_set_pool(h, POOL_REWARDS, rew, 3 * N * 4) == 0
-        assert lib.arl_net_set_pool(h, POOL_DONES, done, 3 * N) == 0
-        # pool_len = 1 (and below): the env writes the entry after the one just read
-        for bad in (1, 0, -3):
-            assert step(L=bad) == EINVAL and b"pool_len" in lib.arl_last_error()
-            assert lib.arl_env_reset(h, pairs, rew, done, bad, None) == EINVAL
-        assert window(1) == EINVAL and b"pool_len" in lib.arl_last_error()
-        # pools too short for pool_len
-        assert step(L=4) == EINVAL and b"exceeds" in lib.arl_last_error()
-        assert lib.arl_env_reset(h, pairs, rew, done, 4, None) == EINVAL
-        assert window(4) == EINVAL and b"exceeds" in lib.arl_last_error()
-        assert lib.arl_net_set_pool(h, POOL_DONES, done, 2 * N) == 0            # only the done pool too short
-        assert step(L=3) == EINVAL and b"done" in lib.arl_last_error()
-        assert lib.arl_net_set_pool(h, POOL_DONES, done, 3 * N) == 0
-        # the env writes all three pools
-        assert step(r=None) == EINVAL and step(d=None) == EINVAL and step(p=None) == EINVAL
-        assert step(p=pairs + 8) == EINVAL                                       # misaligned frames
-        # t in [0, t_max); the env range rules of arl_observe_envs
-        assert step(t=T) == EINVAL and b"t_max" in lib.arl_last_error()
-        assert step(t=-1) == EINVAL
-        assert step(e0=1, ne=3) == EINVAL and step(e0=0, ne=N + 1) == EINVAL and step(ne=0) == EINVAL
-        # detached again: the env calls are refused, the window is an ordinary one
-        assert lib.arl_net_set_env(h, ENV_CATCH, None) == OK
-        assert step() == ESTATE
-    finally:
-        lib.arl_net_destroy(h)
 
 
 def test_granular_calls_validate_and_symbols_are_exported():

@@ -12,14 +12,11 @@ import pytest
 import torch
 
 import breakout_ref as B
-from episode_replay import Replay, same_bits
+import device_env_loop as loop
+from device_env_loop import dev, run_windows
+from episode_replay import same_bits
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(x, gpu, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(x))
-    return (t if dtype is None else t.to(dtype)).to(gpu)
 
 
 def plant(env, ref, rows, half=None):
@@ -77,72 +74,14 @@ def fresh_state(n, seed, off):
 
 
 # ---------------------------------------------------------------- 2 - 4. the closed loop
-def make_agent(kind, A, n, T, P, gpu, seed=5, env=True, life_loss_terminal=True, window_stats=False):
-    """An agent at the reference's hyperparameters on `kind` ("ff" / "lstm"), its pools, and a
-    Breakout attached and reset (the window that follows runs with first=True)."""
-    from asyncrl_amd import A3C, A3CFF, A3CLSTM, DeviceBreakout, GradientClipping, RMSpropAsync
-    model = (A3CFF if kind == "ff" else A3CLSTM)(A, n_envs=n, t_max=T, seed=seed, init_seed=1, device=gpu,
-                                                 frames="pairs")
-    opt = RMSpropAsync(lr=7e-4, eps=1e-1, alpha=0.99).setup(model)
-    opt.add_hook(GradientClipping(40))
-    agent = A3C(model, opt, T, 0.99)
-    net = model.net
-    net.set_episode_stats(True)
-    if window_stats:
-        net.set_window_stats(True)
-    game = DeviceBreakout(n, device=gpu, seed=seed, life_loss_terminal=life_loss_terminal)
-    pools = game.make_pools(P)
-    if env:
-        net.set_env(game)
-        net.env_reset(*pools, P)
-    return agent, net, game, pools
+def make_agent(*args, **kw):
+    from asyncrl_amd import DeviceBreakout
+    return loop.make_agent(DeviceBreakout, *args, **kw)
 
 
-class LoopCheck:
-    """Replays the actions the policy sampled through breakout_ref and the episode replay."""
-
-    def __init__(self, n, seed=5, life_loss_terminal=True, keep=8):
-        self.ref = B.BreakoutRef(n, seed=seed, life_loss_terminal=life_loss_terminal)
-        self.obs = {0: self.ref.reset()}          # observation index -> (pairs, rewards, dones)
-        self.rp = Replay(n)
-        self.k, self.keep = 0, keep
-        self.slots = []                           # per window: (T, n) dones
-        self.rewards = []
-
-    def window(self, net):
-        """The window that just ran: its rewards / dones rows are what the env answers to its actions."""
-        T, n = net.t_max, net.n_envs
-        torch.cuda.synchronize()
-        acts = net.buffer("actions", torch.int32, (T + 1, n))[:T].cpu().numpy()
-        rew = net.buffer("rewards", torch.float32, (T, n)).cpu().numpy()
-        don = net.buffer("dones", torch.uint8, (T, n)).cpu().numpy()
-        assert acts.min() >= 0 and acts.max() < net.n_actions
-        for t in range(T):
-            _, r, d = out = self.ref.step(acts[t])
-            self.k += 1
-            self.obs[self.k] = out
-            self.obs.pop(self.k - self.keep, None)
-            self.rp.step(r, d, self.k)
-            assert same_bits(rew[t], r) and same_bits(don[t], d), (self.k, t)
-        self.slots.append(don.copy())
-        self.rewards.append(rew.copy())
-
-    def end(self, net, game, pools, P):
-        """The final state half, the pool entries left, the episode statistics."""
-        torch.cuda.synchronize()
-        assert same_bits(game.state[self.k & 1].cpu().numpy(), self.ref.state)
-        for k in range(self.k - min(P, self.keep) + 1, self.k + 1):
-            for pool, want in zip(pools, self.obs[k]):
-                assert same_bits(pool[k % P].cpu().numpy(), want), k
-        assert same_bits(net.episode_stats_raw(), self.rp.reduce())
-        assert self.rp.reduce()[0] >= 1
-
-
-def run_windows(agent, pools, P, windows, check=None, **kw):
-    for w in range(windows):
-        agent.run_window(*pools, P, first=(w == 0), **kw)
-        if check is not None:
-            check.window(agent.net)
+def LoopCheck(n, seed=5, life_loss_terminal=True, keep=8):
+    """A life lasts 6 env-steps or more: the runs here are long enough for one to end."""
+    return loop.LoopCheck(B.BreakoutRef(n, seed=seed, life_loss_terminal=life_loss_terminal), lambda k: 1, keep=keep)
 
 
 def test_closed_loop_window_one_call(gpu):
@@ -319,39 +258,9 @@ def test_detached_net_leaves_the_env_alone(gpu):
 
 
 # ---------------------------------------------------------------- 9. learning
-def learn_run(gpu, lr, windows, n=256, seed=0):
-    """Breakout from pixels, closed loop: FF, 256 envs, t_max 5, the reference's hyperparameters
-    (RMSpropAsync alpha 0.99, eps 0.1, clip 40, beta 0.01, gamma 0.99, rewards clipped for the
-    learner), window 0 eagerly and one captured window replayed.  Returns the episode statistics of
-    the last tenth of the run (an episode is a life, its return raw), and the parameters."""
-    from asyncrl_amd import A3C, A3CFF, DeviceBreakout, GradientClipping, RMSpropAsync
-    T, P = 5, 2
-    model = A3CFF(4, n_envs=n, t_max=T, seed=seed, init_seed=seed, device=gpu, frames="pairs")
-    opt = RMSpropAsync(lr=lr, eps=1e-1, alpha=0.99).setup(model)
-    opt.add_hook(GradientClipping(40))
-    agent = A3C(model, opt, T, 0.99, beta=1e-2)
-    net = model.net
-    net.set_episode_stats(True)
-    game = DeviceBreakout(n, device=gpu, seed=seed)
-    pools = game.make_pools(P)
-    net.set_env(game)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        net.env_reset(*pools, P, stream=s)
-        agent.run_window(*pools, P, first=True, stream=s)
-        s.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=s):
-            agent.run_window(*pools, P, stream=s)
-        tail = windows // 10
-        for _ in range(windows - 1 - tail):
-            g.replay()
-        net.episode_stats(clear=True, stream=s)
-        for _ in range(tail):
-            g.replay()
-        st = net.episode_stats_raw(stream=s)
-    return st, net.params.clone()
+def learn_run(gpu, lr, windows):
+    from asyncrl_amd import DeviceBreakout
+    return loop.learn_run(DeviceBreakout, gpu, lr, windows, raw=True)
 
 
 def test_the_learner_learns_breakout(gpu):

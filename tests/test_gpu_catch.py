@@ -10,14 +10,11 @@ import pytest
 import torch
 
 import catch_ref as C
-from episode_replay import Replay, same_bits
+import device_env_loop as loop
+from device_env_loop import dev, run_windows
+from episode_replay import same_bits
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(x, gpu, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(x))
-    return (t if dtype is None else t.to(dtype)).to(gpu)
 
 
 # ---------------------------------------------------------------- 1. granular parity
@@ -56,66 +53,14 @@ def test_granular_step_matches_the_restatement(gpu, n):
 
 
 # ---------------------------------------------------------------- 2 - 4. the closed loop
-def make_agent(kind, A, n, T, P, gpu, seed=5, env=True):
-    """An agent at the reference's hyperparameters on `kind` ("ff" / "lstm"), its pools, and a
-    Catch attached and reset (the window that follows runs with first=True)."""
-    from asyncrl_amd import A3C, A3CFF, A3CLSTM, DeviceCatch, GradientClipping, RMSpropAsync
-    model = (A3CFF if kind == "ff" else A3CLSTM)(A, n_envs=n, t_max=T, seed=seed, init_seed=1, device=gpu,
-                                                 frames="pairs")
-    opt = RMSpropAsync(lr=7e-4, eps=1e-1, alpha=0.99).setup(model)
-    opt.add_hook(GradientClipping(40))
-    agent = A3C(model, opt, T, 0.99)
-    net = model.net
-    net.set_episode_stats(True)
-    catch = DeviceCatch(n, device=gpu, seed=seed)
-    pools = catch.make_pools(P)
-    if env:
-        net.set_env(catch)
-        net.env_reset(*pools, P)
-    return agent, net, catch, pools
+def make_agent(*args, **kw):
+    from asyncrl_amd import DeviceCatch
+    return loop.make_agent(DeviceCatch, *args, **kw)
 
 
-class LoopCheck:
-    """Replays the actions the policy sampled through catch_ref and the episode replay."""
-
-    def __init__(self, n, seed=5):
-        self.ref = C.CatchRef(n, seed=seed)
-        self.obs = {0: self.ref.reset()}          # observation index -> (pairs, rewards, dones)
-        self.rp = Replay(n)
-        self.k = 0
-
-    def window(self, net):
-        """The window that just ran: its rewards / dones rows are what the env answers to its actions."""
-        T, n = net.t_max, net.n_envs
-        torch.cuda.synchronize()
-        acts = net.buffer("actions", torch.int32, (T + 1, n))[:T].cpu().numpy()
-        rew = net.buffer("rewards", torch.float32, (T, n)).cpu().numpy()
-        don = net.buffer("dones", torch.uint8, (T, n)).cpu().numpy()
-        assert acts.min() >= 0 and acts.max() < net.n_actions
-        for t in range(T):
-            _, r, d = out = self.ref.step(acts[t])
-            self.k += 1
-            self.obs[self.k] = out
-            self.obs.pop(self.k - 8, None)
-            self.rp.step(r, d, self.k)
-            assert same_bits(rew[t], r) and same_bits(don[t], d), (self.k, t)
-
-    def end(self, net, catch, pools, P):
-        """The final state half, the pool entries left, the episode statistics."""
-        torch.cuda.synchronize()
-        assert same_bits(catch.state[self.k & 1].cpu().numpy(), self.ref.state)
-        for k in range(self.k - min(P, 8) + 1, self.k + 1):
-            for pool, want in zip(pools, self.obs[k]):
-                assert same_bits(pool[k % P].cpu().numpy(), want), k
-        assert same_bits(net.episode_stats_raw(), self.rp.reduce())
-        assert self.rp.reduce()[0] >= net.n_envs * (self.k // C.EPISODE_STEPS)
-
-
-def run_windows(agent, pools, P, windows, check=None, **kw):
-    for w in range(windows):
-        agent.run_window(*pools, P, first=(w == 0), **kw)
-        if check is not None:
-            check.window(agent.net)
+def LoopCheck(n, seed=5):
+    """Every env finishes an episode each EPISODE_STEPS env-steps."""
+    return loop.LoopCheck(C.CatchRef(n, seed=seed), lambda k: n * (k // C.EPISODE_STEPS))
 
 
 def test_closed_loop_window_one_call(gpu):
@@ -202,38 +147,9 @@ def test_detached_net_leaves_the_env_alone(gpu):
 LEARN_WINDOWS = 2400      # twice the most any of three seeds needed on the MI355X (DESIGN.md "Device environment")
 
 
-def learn_run(gpu, lr, windows=LEARN_WINDOWS, n=256, seed=0):
-    """Catch from pixels, closed loop: FF, 256 envs, the reference's hyperparameters (RMSpropAsync
-    alpha 0.99, eps 0.1, clip 40, beta 0.01, gamma 0.99), window 0 eagerly and one captured window
-    replayed.  Returns the episode statistics of the last tenth of the run, and the parameters."""
-    from asyncrl_amd import A3C, A3CFF, DeviceCatch, GradientClipping, RMSpropAsync
-    T, P = 5, 2
-    model = A3CFF(4, n_envs=n, t_max=T, seed=seed, init_seed=seed, device=gpu, frames="pairs")
-    opt = RMSpropAsync(lr=lr, eps=1e-1, alpha=0.99).setup(model)
-    opt.add_hook(GradientClipping(40))
-    agent = A3C(model, opt, T, 0.99, beta=1e-2)
-    net = model.net
-    net.set_episode_stats(True)
-    catch = DeviceCatch(n, device=gpu, seed=seed)
-    pools = catch.make_pools(P)
-    net.set_env(catch)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        net.env_reset(*pools, P, stream=s)
-        agent.run_window(*pools, P, first=True, stream=s)
-        s.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=s):
-            agent.run_window(*pools, P, stream=s)
-        tail = windows // 10
-        for _ in range(windows - 1 - tail):
-            g.replay()
-        net.episode_stats(clear=True, stream=s)
-        for _ in range(tail):
-            g.replay()
-        st = net.episode_stats(stream=s)
-    return st, net.params.clone()
+def learn_run(gpu, lr):
+    from asyncrl_amd import DeviceCatch
+    return loop.learn_run(DeviceCatch, gpu, lr, LEARN_WINDOWS)
 
 
 def test_the_learner_learns_catch(gpu):
