@@ -7,7 +7,8 @@ touches a device.
 Every reduction over the window's S = t_max * n_envs samples is accumulated
 in float64 and rounded to float32 once, as oracle.gmm / oracle.gsum do, and
 comes with the oracle's per-element error scale (oracle._mag_mm / _mag_sum)
-for conftest.grads_match."""
+for conftest.grads_match.  The references of stages without such a reduction
+(conv_fwd, lstm_bptt, returns) return float64."""
 import numpy as np
 
 import oracle as O
@@ -151,21 +152,24 @@ class RingX:
       ring   frames (R, N, 84, 84): plane c = frames[(t - 3 + c) % R, e]
       stack  frames (R, N, 4, 84, 84): plane c of frames[t % R, e]
       rgb    frames (R, N, 3, 84, 84): the three planes of frames[t % R, e]
-    through O.PHI_LUT; ring / stack planes c < 4 - nvalid[t % R, e] are zero."""
+    through `lut` (O.PHI_LUT; PIXELS: the integer pixel values); ring / stack planes
+    c < 4 - nvalid[t % R, e] are zero.  steps: the window slots covered (t_max;
+    t_max + 1 takes in the bootstrap slot)."""
 
-    def __init__(self, frames, nvalid, n_envs, t_max, layout="ring"):
+    def __init__(self, frames, nvalid, n_envs, t_max, layout="ring", steps=None, lut=None):
         self.frames, self.nvalid, self.N, self.R, self.layout = frames, nvalid, n_envs, t_max + 4, layout
-        self.shape = (t_max * n_envs, 3 if layout == "rgb" else 4, 84, 84)
+        self.lut = O.PHI_LUT if lut is None else lut
+        self.shape = ((t_max if steps is None else steps) * n_envs, 3 if layout == "rgb" else 4, 84, 84)
 
     def __getitem__(self, sl):
         s = np.arange(self.shape[0])[sl]
         t, e = s // self.N, s % self.N
         if self.layout == "rgb":
-            return O.PHI_LUT[self.frames[t % self.R, e]]
+            return self.lut[self.frames[t % self.R, e]]
         if self.layout == "stack":
-            x = O.PHI_LUT[self.frames[t % self.R, e]]
+            x = self.lut[self.frames[t % self.R, e]]
         else:
-            x = np.stack([O.PHI_LUT[self.frames[(t - 3 + c) % self.R, e]] for c in range(4)], 1)
+            x = np.stack([self.lut[self.frames[(t - 3 + c) % self.R, e]] for c in range(4)], 1)
         keep = np.arange(4)[None, :] >= 4 - self.nvalid[t % self.R, e].astype(np.int32)[:, None]
         return np.where(keep[:, :, None, None], x, F32(0.0))
 
@@ -180,6 +184,142 @@ def pack_a2_mask(a2):
 def unpack_a2_mask(words):
     bits = (np.asarray(words, np.uint32)[..., None] >> np.arange(32, dtype=np.uint32)) & 1
     return bits.reshape(words.shape[:-1] + (A2,)).astype(bool)
+
+
+# ---------------------------------------------------------------- conv_fwd
+PIXELS = np.arange(256, dtype=F32)   # RingX(lut=PIXELS): the integer pixel values conv_fwd.hip multiplies
+TIE_REL = 1e-5                       # oracle.relu_mask's tie band: |z| < TIE_REL * max|z|
+
+
+def conv_fwd_ref(x, W1, b1, W2, b2, chunk=64):
+    """The conv_fwd stage in float64 from the f32 state x (an array, or RingX):
+    z1 = conv(x, W1, s4) + b1, a1 = max(z1, 0), z2 = conv(a1, W2, s2) + b2 on the
+    float64 a1, a2 = max(z2, 0); chunks of <= chunk samples.  Returns (a1, a2, z1,
+    z2), float64, (S, 16, 20, 20) and (S, 32, 9, 9)."""
+    S, C = x.shape[0], x.shape[1]
+    W1f, W2f = np.asarray(W1, F64).reshape(16, C * 64).T, np.asarray(W2, F64).reshape(32, 256).T
+    z1, z2 = np.empty((S, 16, 20, 20)), np.empty((S, 32, 9, 9))
+    for c0 in range(0, S, chunk):
+        xs = np.ascontiguousarray(x[c0:c0 + chunk])
+        n = xs.shape[0]
+        cols = O._im2col(xs, 8, 4)[0].reshape(-1, C * 64)
+        z = (np.asarray(cols, F64) @ W1f + np.asarray(b1, F64)).reshape(n, 20, 20, 16).transpose(0, 3, 1, 2)
+        z1[c0:c0 + n] = z
+        cols = O._im2col(np.maximum(z1[c0:c0 + n], 0.0), 4, 2)[0].reshape(-1, 256)
+        z2[c0:c0 + n] = (cols @ W2f + np.asarray(b2, F64)).reshape(n, 9, 9, 32).transpose(0, 3, 1, 2)
+    return np.maximum(z1, 0.0), np.maximum(z2, 0.0), z1, z2
+
+
+def tie_band(z, rel=TIE_REL):
+    """Pre-activations within rounding of 0, where either ReLU decision is a correct
+    f32 result (oracle.relu_mask's rule); the sign checks exempt them."""
+    return np.abs(z) < rel * np.abs(z).max()
+
+
+def split_bf16(w, planes=3):
+    """bf16split.hpp's split3 of f32 w: the first `planes` of the truncated pieces
+    h, m, l (w = h + m + l exactly), as f32 arrays."""
+    out, r = [], np.asarray(w, F32)
+    for _ in range(planes):
+        piece = (r.view(np.uint32) & np.uint32(0xFFFF0000)).view(F32)
+        out.append(piece)
+        r = r - piece   # exact
+    return out
+
+
+def conv1_split_model(xint, W1, b1, planes=3, chunk=64):
+    """A model of conv_fwd.hip's conv1 arithmetic: the integer pixels xint (RingX with
+    lut=PIXELS) times the first `planes` bf16 pieces of W1, each product exact, the
+    sums in f32 (piece h in one accumulator, m and l in a second, as mfma_x3_t),
+    1/255 applied to the sum, then the bias and the ReLU.  planes < 3: the mistake of
+    a dropped low split plane.  Returns a1 (S, 16, 20, 20), float32."""
+    S, C = xint.shape[0], xint.shape[1]
+    Wp = [p.reshape(16, C * 64).T.copy() for p in split_bf16(W1, planes)]
+    out = np.empty((S, 16, 20, 20), F32)
+    for c0 in range(0, S, chunk):
+        xs = np.ascontiguousarray(xint[c0:c0 + chunk])
+        n = xs.shape[0]
+        cols = O._im2col(xs, 8, 4)[0].reshape(-1, C * 64)
+        big, sml = cols @ Wp[0], np.zeros((cols.shape[0], 16), F32)
+        for p in Wp[:0:-1]:
+            sml = sml + cols @ p
+        z = ((big + sml).astype(F64) / 255.0).astype(F32) + np.asarray(b1, F32)   # div255: the IEEE quotient
+        out[c0:c0 + n] = np.maximum(z, F32(0)).reshape(n, 20, 20, 16).transpose(0, 3, 1, 2)
+    return out
+
+
+# ---------------------------------------------------------------- lstm_bptt
+def _sig(x):
+    return 1.0 / (1.0 + np.exp(-x))
+
+
+def lstm_bptt_ref(dG_t, Wl, reset_t, gates, c_t, c_prev, reset_prev, dH, dcn_in, first=False):
+    """The lstm_bptt stage, step t -> t - 1, in float64: dh = dG_t Wl, zeroed on rows
+    with reset_t; then F.lstm's backward of step t - 1 (lstm_cell_bwd_elem, net.hip)
+    with dh + dH and the carried dc: gates (n, 1024) interleaved four per unit (a, i,
+    f, o), c_t the cell after step t - 1, c_prev before it (read as 0 on rows with
+    reset_prev, whose dcn_out is 0).  first: the window's last step (no dh, no
+    carried dc; dG_t, Wl, reset_t, dcn_in unused).  Returns (dG_prev, dcn_out)."""
+    n = gates.shape[0]
+    dh, dc_in = np.asarray(dH, F64), 0.0
+    if not first:
+        dh = dh + mm64(dG_t, Wl) * (np.asarray(reset_t) == 0)[:, None]
+        dc_in = np.asarray(dcn_in, F64)
+    g = np.asarray(gates, F64).reshape(n, HID, 4)
+    a, i, f, o = np.tanh(g[..., 0]), _sig(g[..., 1]), _sig(g[..., 2]), _sig(g[..., 3])
+    rp = (np.asarray(reset_prev) != 0)[:, None]
+    tc = np.tanh(np.asarray(c_t, F64))
+    cp = np.where(rp, 0.0, np.asarray(c_prev, F64))
+    dc = dh * o * (1.0 - tc * tc) + dc_in
+    dG = np.stack([dc * i * (1.0 - a * a), dc * a * i * (1.0 - i), dc * cp * f * (1.0 - f), dh * tc * o * (1.0 - o)], -1)
+    return dG.reshape(n, GATES), np.where(rp, 0.0, dc * f)
+
+
+def lstm_bptt_chain_ref(Wl, reset, gates, cbuf, dH):
+    """The window's truncated BPTT (LEARN_TRUNK's cell launch and its T - 1 lstm_bptt
+    launches), t = T - 1 ... 0, in float64 throughout: reset (>= T, N), gates (>= T,
+    N, 1024), cbuf (>= T + 1, N, 256) with slot t the cell before step t, dH (T, N,
+    256).  Returns dG (T, N, 1024)."""
+    T = dH.shape[0]
+    dG = np.empty((T,) + gates.shape[1:], F64)
+    dG[T - 1], dcn = lstm_bptt_ref(None, None, None, gates[T - 1], cbuf[T], cbuf[T - 1], reset[T - 1], dH[T - 1], None,
+                                   first=True)
+    for t in range(T - 1, 0, -1):
+        dG[t - 1], dcn = lstm_bptt_ref(dG[t], Wl, reset[t], gates[t - 1], cbuf[t], cbuf[t - 1], reset[t - 1], dH[t - 1], dcn)
+    return dG
+
+
+# ---------------------------------------------------------------- returns
+def returns_heads_ref(rewards, dones, v, probs, logp, actions, Wpi, Wv, hfc=None, gamma=0.99, beta=0.01, vcoef=0.5,
+                      clip_reward=True):
+    """The returns stage (returns_heads_kernel, policy.hip) in float64 from the f32
+    buffers: oracle.returns_and_lossgrad's mathematics (R restarted at terminals,
+    rewards clipped to +-1) on rewards / dones (T, N), v (T + 1, N) with slot T the
+    bootstrap value, probs / logp (T, N, A), actions (T, N); the heads' backward
+    dh = dlogits Wpi + dv Wv, and with hfc (T, N, 256) dfc = dh * (hfc > 0).
+    Returns dlogits (T, N, A), dv (T, N), loss (N, 2) = per-env (pi, v) losses and
+    dh (or dfc) (T, N, 256)."""
+    T, N = rewards.shape
+    r = np.asarray(rewards, F64)
+    if clip_reward:
+        r = np.clip(r, -1.0, 1.0)
+    v, p, lp = np.asarray(v, F64), np.asarray(probs, F64), np.asarray(logp, F64)
+    R, Rs = v[T].copy(), np.empty((T, N))
+    for t in reversed(range(T)):
+        R = np.where(dones[t] != 0, 0.0, R) * gamma + r[t]
+        Rs[t] = R
+    adv = Rs - v[:T]
+    H = -(p * lp).sum(-1)
+    onehot = np.zeros_like(p)
+    np.put_along_axis(onehot, np.asarray(actions, np.int64)[..., None], 1.0, axis=2)
+    dlogits = -adv[..., None] * (onehot - p) + beta * p * (lp + H[..., None])
+    dv = vcoef * (v[:T] - Rs)
+    lp_a = np.take_along_axis(lp, np.asarray(actions, np.int64)[..., None], 2)[..., 0]
+    loss = np.stack([-(lp_a * adv + beta * H).sum(0), (vcoef * (v[:T] - Rs) ** 2 / 2).sum(0)], 1)
+    dh = dlogits @ np.asarray(Wpi, F64) + dv[..., None] * np.asarray(Wv, F64).reshape(-1)
+    if hfc is not None:
+        dh = dh * (np.asarray(hfc) > 0)
+    return dlogits, dv, loss, dh
 
 
 # ---------------------------------------------------------------- data recipes
@@ -262,6 +402,97 @@ def conv_data(n_envs, t_max, layout="ring", seed=0):
             "x": RingX(frames, nvalid, N, T, layout)}
 
 
+def conv_fwd_data(n_envs, layout="ring", seed=0):
+    """Operands of the conv_fwd stage on a t_max = 1 net (slots 0 and 1, a ring of 5):
+    frames and nvalid as conv_data (ring: nvalid from 1..4, a masked plane on env 0
+    of both slots), the two convs' weights and biases, and x: RingX over both
+    slots, sample t * n_envs + e; xint: the same with integer pixel values."""
+    rng = np.random.default_rng([seed, n_envs, 1, 6])
+    N, T, R = n_envs, 1, 5
+    planes = {"ring": (), "stack": (4,), "rgb": (3,)}[layout]
+    frames = rng.integers(0, 256, (R, N) + planes + (84, 84), dtype=np.uint8)
+    if layout == "ring":
+        nvalid = rng.integers(1, 5, (R, N)).astype(np.uint8)
+        nvalid[0, 0], nvalid[1, 0] = 2, 3
+    else:
+        nvalid = np.full((R, N), 4 if layout == "stack" else 3, np.uint8)
+    C = 3 if layout == "rgb" else 4
+    d = {"N": N, "T": T, "R": R, "layout": layout, "frames": frames, "nvalid": nvalid,
+         "W1": weight_like(rng, (16, C, 8, 8)), "W2": weight_like(rng, (32, 16, 4, 4))}
+    d["b1"], d["b2"] = rng.uniform(-1 / 16, 1 / 16, 16).astype(F32), rng.uniform(-1 / 16, 1 / 16, 32).astype(F32)
+    d["x"] = RingX(frames, nvalid, N, T, layout, steps=T + 1)
+    d["xint"] = RingX(frames, nvalid, N, T, layout, steps=T + 1, lut=PIXELS)
+    return d
+
+
+def bptt_data(n_envs, t_max, t, seed=0):
+    """Operands of one lstm_bptt step t -> t - 1.  reset is ~20 % ones at steps t and
+    t - 1, 1 on row 0 at step t and on the last row at step t - 1, 1 elsewhere;
+    every dG / gates / cbuf / dh slot the step must not read holds the sentinel,
+    as does c_prev (cbuf slot t - 1) on the rows with reset_{t-1}."""
+    rng = np.random.default_rng([seed, n_envs, t_max, t, 7])
+    N, T = n_envs, t_max
+    reset = np.ones((T + 1, N), np.uint8)
+    reset[t - 1:t + 1] = rng.random((2, N)) < 0.2
+    reset[t, 0] = reset[t - 1, N - 1] = 1
+    dG = np.full((T, N, GATES), SENTINEL, F32)
+    dG[t] = grad_like(rng, (N, GATES))
+    gates = np.full((T + 1, N, GATES), SENTINEL, F32)
+    gates[t - 1] = rng.standard_normal((N, GATES), F32)
+    cbuf = np.full((T + 2, N, HID), SENTINEL, F32)
+    cbuf[t - 1:t + 1] = rng.standard_normal((2, N, HID), F32)
+    cbuf[t - 1][reset[t - 1] != 0] = SENTINEL
+    dh = np.full((T, N, HID), SENTINEL, F32)
+    dh[t - 1] = rng.standard_normal((N, HID), F32) * F32(1e-3)
+    return {"N": N, "T": T, "t": t, "reset": reset, "dG": dG, "gates": gates, "cbuf": cbuf, "dh": dh,
+            "dcn": rng.standard_normal((N, HID), F32) * F32(1e-3), "Wl": weight_like(rng, (GATES, HID))}
+
+
+def bptt_chain_data(n_envs, t_max, seed=0):
+    """Operands of LEARN_TRUNK's BPTT chain on top of lstm_data / fc_data (finite
+    operands for the weight-gradient and FC launches that follow): gates and cbuf
+    of every step (cbuf slot 0 a sentinel on the rows reset at step 0, slots past
+    the window sentinels), the heads' dh, the lateral weight; hbuf slot T finite."""
+    rng = np.random.default_rng([seed, n_envs, t_max, 8])
+    N, T = n_envs, t_max
+    d = lstm_data(N, T, seed)
+    d["fc"] = fc_data(N, T, lstm=True, seed=seed)
+    d["hbuf"][T] = rng.standard_normal((N, HID), F32) * F32(0.5)
+    gates = np.full((T + 1, N, GATES), SENTINEL, F32)
+    gates[:T] = rng.standard_normal((T, N, GATES), F32)
+    cbuf = np.full((T + 2, N, HID), SENTINEL, F32)
+    cbuf[:T + 1] = rng.standard_normal((T + 1, N, HID), F32)
+    cbuf[0][d["reset"][0] != 0] = SENTINEL
+    d.update(gates=gates, cbuf=cbuf, dh=rng.standard_normal((T, N, HID), F32) * F32(1e-3),
+             Wl=weight_like(rng, (GATES, HID)))
+    return d
+
+
+def returns_data(t_max, n_actions, n_envs, lstm=False, seed=0):
+    """Operands of the returns stage: rewards a mix of 0, +-1 and values beyond +-1,
+    dones ~15 % with a terminal at step 0 of env 0 and at step T - 1 of the last
+    env, v with the bootstrap slot T, probs / logp of random logits (float64,
+    rounded once), actions, head weights, and hfc (slot T a sentinel; lstm: all of
+    it, the stage must not read it)."""
+    rng = np.random.default_rng([seed, t_max, n_actions, n_envs, 9])
+    T, A, N = t_max, n_actions, n_envs
+    rewards = rng.choice(np.array([0, 0, 1, -1, 0.5, 2.5, -3], F32), (T, N))
+    rewards[0, N - 1] = 2.5
+    dones = (rng.random((T, N)) < 0.15).astype(np.uint8)
+    if N > 1 and T > 1:
+        dones[T - 1, 0] = 0   # env 0's last steps reach the bootstrap value
+    dones[0, 0] = dones[T - 1, N - 1] = 1
+    z =rng.standard_normal((T, N, A)) * 2.0
+    z -= z.max(-1, keepdims=True)
+    lse = np.log(np.exp(z).sum(-1, keepdims=True))
+    hfc = act_like(rng, (T + 1, N, HID))
+    hfc[T if not lstm else slice(None)] = SENTINEL
+    return {"T": T, "A": A, "N": N, "rewards": rewards, "dones": dones, "v": rng.standard_normal((T + 1, N), F32),
+            "probs": np.exp(z - lse).astype(F32), "logp": (z - lse).astype(F32),
+            "actions": rng.integers(0, A, (T, N)).astype(np.int32), "hfc": hfc,
+            "Wpi": weight_like(rng, (A, HID)), "Wv": weight_like(rng, (1, HID))}
+
+
 # the cases of tests/test_gpu_stages.py, (n_envs, t_max); tests/test_stage_ref.py runs the
 # sensitivity check on the same list
 FC_CASES = [(1, 1), (43, 3), (109, 11), (240, 5), (241, 5), (400, 5)]
@@ -270,3 +501,12 @@ LSTM_CASES = [(1, 1), (43, 3), (256, 4), (205, 5), (400, 5)]
 CONV_CASES = [(1, 1), (255, 1), (257, 1), (52, 5), (67, 9), (513, 5)]
 CONV_LAYOUT_CASE = (52, 5)   # also run as rgb (DoomA3CFF) and stack
 LAUNCHES = 4                 # at Z > 1: launches in a row, each with fresh gradients
+# conv_fwd (n_envs, layout), each at slots 0 and 1 of a t_max = 1 net: from 512 envs two envs a workgroup
+CONV_FWD_CASES = [(1, "ring"), (5, "ring"), (512, "ring"), (513, "ring"), (5, "rgb"), (513, "rgb"), (5, "stack"),
+                  (513, "stack")]
+BPTT_CASES = [(n, t) for n in (1, 33, 64) for t in (1, 2)]   # (n_envs, t) on a t_max = 3 net
+BPTT_T = 3
+BPTT_CHAIN_CASES = [(37, 5), (1, 5)]
+# returns (t_max, n_actions, n_envs): one case for each returns_heads_kernel<AM, RB> and row-pass count
+RETURNS_CASES = [(1, 1, 1), (8, 4, 3), (8, 5, 3), (8, 8, 2), (8, 9, 2), (9, 4, 3), (32, 32, 2), (33, 6, 2), (64, 32, 2)]
+RETURNS_LSTM_CASE = (5, 6, 3)

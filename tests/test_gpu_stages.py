@@ -2,7 +2,11 @@
 the workspace, against the float64 references of tests/stage_ref.py -- at the
 window sizes where the backward kernels change shape: more than one job A
 sample range (the in-launch ticket reduce of fc_bwd.hip, for the FC layer and
-the LSTM gate weights) and more than one sample per conv_bwd.hip workgroup.
+the LSTM gate weights) and more than one sample per conv_bwd.hip workgroup;
+and the three hot-path stages whose outputs are intermediate in a window:
+conv_fwd (both LDS layouts, an idle env slot, three frame layouts, the a2
+mask), one lstm_bptt step and the learner's whole BPTT chain, and the returns
+launch in every instantiation the host picks, one and two row passes.
 
 Tolerances are the suite's own (conftest): reduced tensors grads_match(rtol =
 1e-5, rtol_elem = 1e-5) against the reference and its per-element scales,
@@ -254,3 +258,192 @@ def test_fc_fwd_lstm_gates_stages(gpu, n_envs):
     _close(get(net, "gates", (T + 1, N, R.GATES))[t], g, "gates")
     _close(get(net, "cbuf", (T + 2, N, R.HID))[t + 1], c, "cbuf")
     _close(get(net, "hbuf", (T + 2, N, R.HID))[t + 1], hn, "hbuf")
+
+
+# ------------------------------------------------------------------ conv_fwd
+MASK_PREFILL = 0x5A5A5A5A
+
+
+@pytest.mark.parametrize("n_envs,layout", R.CONV_FWD_CASES)
+def test_conv_fwd_stage(gpu, n_envs, layout):
+    """conv_fwd at slots 0 and 1 (the bootstrap slot) of a t_max = 1 net against
+    conv_fwd_ref: 1, 5 envs (one env a workgroup), 512 and 513 (two a workgroup; 513:
+    the last workgroup's second slot idle), the ring, RGB and stack frame layouts.
+    a1 / a2 at 1e-5 of the scale and a1 within a third of the error a dropped low
+    split plane of W1 makes (stage_ref.conv1_split_model); outside the tie band
+    the ReLU decisions and the a2_mask bits are the reference's; a2_mask is the
+    packed device a2 exactly; the other slot keeps its prefill."""
+    from asyncrl_amd import A3CFF, DoomA3CFF
+    d = R.conv_fwd_data(n_envs, layout)
+    N, T = n_envs, 1
+    if layout == "rgb":
+        net = DoomA3CFF(3, n_envs=N, t_max=T, init_seed=0).net
+    else:
+        net = A3CFF(4, n_envs=N, t_max=T, init_seed=0, frames="stacks" if layout == "stack" else "pairs").net
+    net.reset()
+    put(net, "frames", d["frames"], torch.uint8)
+    put(net, "nvalid", d["nvalid"], torch.uint8)
+    for name, key in (("0/0/W", "W1"), ("0/0/b", "b1"), ("0/1/W", "W2"), ("0/1/b", "b2")):
+        put_param(net, name, d[key])
+    a1r, a2r, z1, z2 = R.conv_fwd_ref(d["x"], d["W1"], d["b1"], d["W2"], d["b2"])
+    for t in (0, 1):
+        sl = slice(t * N, (t + 1) * N)
+        net.buffer("a1", f32).fill_(R.PREFILL)
+        net.buffer("a2", f32).fill_(R.PREFILL)
+        net.buffer("a2_mask", torch.int32).fill_(MASK_PREFILL)
+        net.run_stage("conv_fwd", t)
+        torch.cuda.synchronize()
+        a1 = get(net, "a1", (T + 1, N, 16, 20, 20))
+        a2 = get(net, "a2", (T + 1, N, 32, 9, 9))
+        words = net.buffer("a2_mask", torch.int32, (T + 1, N, R.A2W)).cpu().numpy().view(np.uint32)
+        e2 = close_normscaled(R.conv1_split_model(d["xint"][sl], d["W1"], d["b1"], 2), a1r[sl], RTOL)[1]
+        e1d, e2d = close_normscaled(a1[t], a1r[sl], RTOL)[1], close_normscaled(a2[t], a2r[sl], RTOL)[1]
+        print(f"conv_fwd {layout} N={N} t={t}: a1 {e1d:.3g} a2 {e2d:.3g} of the scale; a1 against the two-plane "
+              f"model's {e2:.3g}: {e1d / e2:.3g}")
+        for got, want, z, what in ((a1[t], a1r[sl], z1[sl], "a1"), (a2[t], a2r[sl], z2[sl], "a2")):
+            assert not (got == R.PREFILL).any(), (what, t)
+            _close(got, want, (what, t))
+            sure = ~R.tie_band(z)
+            assert (got[sure & (z < 0)] == 0).all() and (got[sure & (z > 0)] > 0).all(), (what, t)
+        assert e1d <= e2 / 3, (t, e1d, e2)
+        assert np.array_equal(words[t], R.pack_a2_mask(a2[t].reshape(N, R.A2))), t
+        sure = ~R.tie_band(z2[sl]).reshape(N, R.A2)
+        assert np.array_equal(R.unpack_a2_mask(words[t])[sure], (z2[sl] > 0).reshape(N, R.A2)[sure]), t
+        assert (a1[1 - t] == R.PREFILL).all() and (a2[1 - t] == R.PREFILL).all() and (words[1 - t] == MASK_PREFILL).all(), t
+
+
+# ------------------------------------------------------------------ lstm_bptt
+@pytest.mark.parametrize("n_envs,t", R.BPTT_CASES)
+def test_lstm_bptt_stage(gpu, n_envs, t):
+    """One BPTT step t -> t - 1 of a t_max = 3 LSTM net against lstm_bptt_ref: 1 env,
+    33 (the second 32-row tile holds one row, the rest clamped) and 64; ~20 % reset
+    rows at both steps, row 0 at step t and the last row at step t - 1 among them.
+    Every dG / gates / cbuf / dh slot the step must not read holds the sentinel, as
+    does c_prev of the rows reset at t - 1."""
+    from asyncrl_amd import A3CLSTM
+    d = R.bptt_data(n_envs, R.BPTT_T, t)
+    N, T = n_envs, R.BPTT_T
+    net = A3CLSTM(4, n_envs=N, t_max=T, init_seed=0, frames="pairs").net
+    net.reset()
+    dG0 = d["dG"].copy()
+    dG0[t - 1] = R.PREFILL
+    put(net, "dG", dG0)
+    for name in ("gates", "cbuf", "dh", "dcn"):
+        put(net, name, d[name])
+    put(net, "reset", d["reset"], torch.uint8)
+    put_param(net, "1/lateral/W", d["Wl"])
+    net.buffer("dhn", f32).fill_(R.PREFILL)
+    net.run_stage("lstm_bptt", t)
+    torch.cuda.synchronize()
+    dGr, dcr = R.lstm_bptt_ref(d["dG"][t], d["Wl"], d["reset"][t], d["gates"][t - 1], d["cbuf"][t], d["cbuf"][t - 1],
+                               d["reset"][t - 1], d["dh"][t - 1], d["dcn"])
+    dG, dcn = get(net, "dG", (T, N, R.GATES)), get(net, "dcn", (N, R.HID))
+    print(f"lstm_bptt N={N} t={t}: dG {close_normscaled(dG[t - 1], dGr, RTOL)[1]:.3g} dcn "
+          f"{close_normscaled(dcn, dcr, RTOL)[1]:.3g} of the scale")
+    assert not (dG[t - 1] == R.PREFILL).any()
+    _close(dG[t - 1], dGr, "dG")
+    _close(dcn, dcr, "dcn")
+    assert (dcn[d["reset"][t - 1] != 0] == 0).all()
+    assert np.array_equal(np.delete(dG, t - 1, 0), np.delete(d["dG"], t - 1, 0))
+    assert bool((net.buffer("dhn", f32) == R.PREFILL).all())
+
+
+@pytest.mark.parametrize("n_envs,t_max", R.BPTT_CHAIN_CASES)
+def test_lstm_bptt_chain(gpu, n_envs, t_max):
+    """The learner's trunk part on an LSTM net, T = 5, 37 envs and 1: the first cell
+    launch (dhn / dcn hold the sentinel: it must ignore them) and the T - 1 BPTT
+    launches against lstm_bptt_chain_ref over the whole dG, then the LSTM weight
+    gradients of the same run against lstm_wgrad_ref fed the reference dG."""
+    from asyncrl_amd import A3CLSTM
+    from asyncrl_amd._lib import LEARN_TRUNK
+    d = R.bptt_chain_data(n_envs, t_max)
+    fc = d["fc"]
+    N, T, S = n_envs, t_max, d["S"]
+    net = A3CLSTM(fc["A"], n_envs=N, t_max=T, init_seed=0, frames="pairs").net
+    net.reset()
+    for name in ("hfc", "hbuf", "gates", "cbuf", "dh"):
+        put(net, name, d[name])
+    put(net, "reset", d["reset"], torch.uint8)
+    put(net, "a2", fc["a2"])
+    words = R.pack_a2_mask(fc["a2"])
+    words[T] = 0xFFFFFFFF
+    put(net, "a2_mask", words)
+    put(net, "dlogits", fc["dlogits"])
+    put(net, "dv", fc["dv"])
+    for name, arr in (("1/upward/W", d["Wu"]), ("1/lateral/W", d["Wl"]), ("0/2/W", fc["W"])):
+        put_param(net, name, arr)
+    for name in ("dhn", "dcn"):
+        net.buffer(name, f32).fill_(float(R.SENTINEL))
+    for name in ("dG", "dfc"):
+        net.buffer(name, f32).fill_(R.PREFILL)
+    net.grads.fill_(R.PREFILL)
+    net.learn_parts([LEARN_TRUNK])
+    torch.cuda.synchronize()
+    dGr = R.lstm_bptt_chain_ref(d["Wl"], d["reset"], d["gates"], d["cbuf"], d["dh"])
+    dG = get(net, "dG", (T, N, R.GATES))
+    print(f"lstm_bptt chain N={N} T={T}: dG {close_normscaled(dG, dGr, RTOL)[1]:.3g} of the scale")
+    assert not (dG == R.PREFILL).any()
+    _close(dG, dGr, "dG")
+    hfc, hprev, reset = d["hfc"][:T].reshape(S, -1), d["hbuf"][:T].reshape(S, -1), d["reset"].reshape(-1)[:S]
+    ref, mag = R.lstm_wgrad_ref(dGr.reshape(S, R.GATES).astype(np.float32), hfc, hprev, reset, d["Wu"])
+    names = {"gWu": "1/upward/W", "gWl": "1/lateral/W", "gbu": "1/upward/b"}
+    got = {k: net.grad(name).cpu().numpy() for k, name in names.items()}
+    grads_match(got, {k: ref[k].reshape(got[k].shape) for k in names}, {k: mag[k].reshape(got[k].shape) for k in names},
+                rtol=RTOL, rtol_elem=RTOL)
+
+
+# ------------------------------------------------------------------ returns
+def _returns(t_max, n_actions, n_envs, lstm=False):
+    from asyncrl_amd import A3CFF, A3CLSTM
+    d = R.returns_data(t_max, n_actions, n_envs, lstm)
+    T, A, N = t_max, n_actions, n_envs
+    net = (A3CLSTM if lstm else A3CFF)(A, n_envs=N, t_max=T, init_seed=0, frames="pairs").net
+    net.reset()
+
+    def slot_T(arr, fill):   # the window's rows, then a slot T the stage must not read
+        return np.concatenate([arr, np.full((1,) + arr.shape[1:], fill, arr.dtype)])
+
+    put(net, "rewards", d["rewards"])
+    put(net, "dones", d["dones"], torch.uint8)
+    put(net, "v", d["v"])
+    put(net, "probs", slot_T(d["probs"], R.SENTINEL))
+    put(net, "logp", slot_T(d["logp"], R.SENTINEL))
+    put(net, "actions", slot_T(d["actions"], 10 ** 6), torch.int32)
+    put(net, "hfc", d["hfc"])
+    pi, vf = ("2/0/W", "3/0/W") if lstm else ("1/0/W", "2/0/W")
+    put_param(net, pi, d["Wpi"])
+    put_param(net, vf, d["Wv"])
+    out = "dh" if lstm else "dfc"
+    for name in ("dlogits", "dv", "loss", "dfc") + (("dh",) if lstm else ()):
+        net.buffer(name, f32).fill_(R.PREFILL)
+    net.run_stage("returns")
+    torch.cuda.synchronize()
+    ref = R.returns_heads_ref(d["rewards"], d["dones"], d["v"], d["probs"], d["logp"], d["actions"], d["Wpi"], d["Wv"],
+                              None if lstm else d["hfc"][:T])
+    got = (get(net, "dlogits", (T, N, A)), get(net, "dv", (T, N)), get(net, "loss", (N, 2)), get(net, out, (T, N, R.HID)))
+    errs = [close_normscaled(g, r, RTOL)[1] for g, r in zip(got, ref)]
+    print(f"returns T={T} A={A} N={N}{' lstm' if lstm else ''}: dlogits / dv / loss / {out} "
+          + " / ".join(f"{e:.3g}" for e in errs) + " of the scale")
+    for g, r, what in zip(got, ref, ("dlogits", "dv", "loss", out)):
+        assert not (g == R.PREFILL).any(), what
+        _close(g, r, what)
+    if lstm:   # unmasked, and nothing of the FF form written
+        assert bool((net.buffer("dfc", f32) == R.PREFILL).all())
+    else:
+        assert (got[3][d["hfc"][:T] <= 0] == 0).all()
+
+
+@pytest.mark.parametrize("t_max,n_actions,n_envs", R.RETURNS_CASES)
+def test_returns_stage(gpu, t_max, n_actions, n_envs):
+    """The learner's first launch on FF nets against returns_heads_ref, one case for
+    each returns_heads_kernel<AM, RB> the host picks and each row-pass count: t_max
+    <= 8 with A <= 4 / <= 8 / above (AM = 4, 8, 32; A = 4, 8 the largest of their
+    form), t_max = 9 (32 rows a pass, the returns' window loop from memory), 32 x 32
+    (every row and action register in use), 33 and 64 (a second pass over rows)."""
+    _returns(t_max, n_actions, n_envs)
+
+
+def test_returns_stage_lstm_arch(gpu):
+    """The same launch on an LSTM net: the output is dh, unmasked, and hfc (all
+    sentinel) is not read."""
+    _returns(*R.RETURNS_LSTM_CASE, lstm=True)
