@@ -211,8 +211,14 @@ class A3C:
                  process_idx: int = 0, clip_reward: bool = True, phi=None, pi_loss_coef: float = 1.0,
                  v_loss_coef: float = 0.5, keep_loss_scale_same: bool = False, resize_mode: int = RESIZE_SCALAR,
                  process_group=None, batch_loss: str = "sum", collectives: bool | None = None,
-                 gae_lambda: float = 1.0):
-        """gae_lambda: GAE(lambda) advantages in the policy term (an extension,
+                 gae_lambda: float = 1.0, ppo_epochs: int = 1, ppo_clip: float = 0.2):
+        """ppo_epochs: K >= 2 makes every window's update K clipped-surrogate
+        (PPO) epochs on the window's rollout (an extension; DeviceNet.set_ppo,
+        DESIGN.md "PPO epochs"): K gradient steps, the slots re-forwarded from
+        the frame ring before epochs 2..K; ppo_clip is the ratio's clip range.
+        FF models with the NIPS head, one rank.  The default 1 runs exactly
+        what ran without it and never touches set_ppo.
+        gae_lambda: GAE(lambda) advantages in the policy term (an extension,
         the reference has none; DeviceNet.set_gae).  The default 1 is the
         reference's n-step advantage and runs exactly what ran without it.
         collectives: all-reduce the window gradient over the process group
@@ -224,6 +230,12 @@ class A3C:
         collectives=False every rank is an independent learner."""
         if not 0.0 <= float(gae_lambda) <= 1.0:   # (nan fails both)
             raise ValueError("gae_lambda must be in [0, 1]")
+        if int(ppo_epochs) != ppo_epochs or ppo_epochs < 1:
+            raise ValueError("ppo_epochs must be an integer >= 1")
+        if ppo_epochs > 1 and not 0.0 < float(ppo_clip) < 1.0:   # (nan fails both)
+            raise ValueError("ppo_clip must be in (0, 1)")
+        if ppo_epochs > 1 and collectives:
+            raise ValueError("A3C: ppo_epochs > 1 runs on one rank (collectives=False)")
         if model.net.t_max != t_max:
             raise ValueError("model was built for a different t_max")
         if batch_loss not in ("sum", "mean"):
@@ -261,6 +273,11 @@ class A3C:
         self.net.set_loss(pi_loss_coef * scale, keep_loss_scale_same)
         self.gae_lambda = float(gae_lambda)
         self.net.set_gae(self.gae_lambda)
+        self.ppo_epochs, self.ppo_clip = int(ppo_epochs), float(ppo_clip)
+        if self.ppo_epochs > 1:
+            if self.collectives:
+                raise ValueError("A3C: ppo_epochs > 1 runs on one rank (collectives=False)")
+            self.net.set_ppo(self.ppo_clip)   # (refuses the LSTM and the Nature head)
         # no all-reduce between learn and update: the clip norm comes from the learner's conv reduce
         self.net.set_norm_fold(not self.collectives)
         self.t = 0          # env-steps taken (per env)
@@ -354,8 +371,43 @@ class A3C:
             self.optimizer.update(stream=main, advance_window=True)
 
     def _update(self, stream=None):
+        if self.ppo_epochs > 1:
+            return self._update_ppo(stream)
         self._learn(stream)
         self._reduce_and_step(stream)
+
+    def _update_ppo(self, stream=None):
+        """K epochs on the window's rollout: the snapshot, then per epoch [the
+        slots' forward again with the current parameters, over all envs on
+        one stream,] the PPO gradient and one update; the last ends the window."""
+        net, K = self.net, self.ppo_epochs
+        net.ppo_begin(self.gamma, self.clip_reward, stream=stream)
+        for j in range(1, K + 1):
+            if j > 1:
+                for t in range(self.t_max):
+                    net.act(t, mode=0, stream=stream)
+            net.ppo_learn(self.beta, self._vcoef, stream=stream)
+            self.optimizer.update(stream=stream, advance_window=(j == K))
+
+    def ppo_stats(self, stream=None) -> dict:
+        """Of the last epoch run, from the snapshot's planes (device ops and one
+        small copy): clip_fraction, the share of live samples whose policy
+        gradient the clip cut; approx_kl, the mean of logp_old - logp_new over
+        live samples; ratio_max.  A sample is live where its ratio is > 0."""
+        if self.ppo_epochs <= 1:
+            raise ValueError("ppo_stats: ppo_epochs is 1")
+        net = self.net
+        s = stream if stream is not None else torch.cuda.current_stream(net.device)
+        with torch.cuda.stream(s):
+            p = net.ppo_planes()
+            rho, adv = p["ratio"], p["adv"]
+            live = rho > 0
+            lo, hi = np.float32(1.0 - self.ppo_clip), np.float32(1.0 + self.ppo_clip)
+            cut = live & torch.where(adv >= 0, rho > float(hi), rho < float(lo))
+            n = live.sum().clamp(min=1).to(torch.float64)
+            kl = -(torch.log(rho.double().clamp(min=1e-45)) * live).sum() / n
+            out = torch.stack([cut.sum().to(torch.float64) / n, kl, rho.max().to(torch.float64)]).cpu()
+        return {"clip_fraction": float(out[0]), "approx_kl": float(out[1]), "ratio_max": float(out[2])}
 
     # ------------------------------------------------------------ reference-contract act
     def act(self, state, reward=None, is_state_terminal=None):
@@ -471,8 +523,11 @@ class A3C:
         chain is faster since those launches run two envs a conv workgroup and
         64-row FC tiles, C4 0.497 vs 0.509-0.518 ms; profiles/r03/r3l)."""
         net, T = self.net, self.t_max
+        ppo = self.ppo_epochs > 1
+        if ppo and split_update:
+            raise ValueError("run_window: split_update=True has no PPO epochs (ppo_epochs > 1)")
         groups = net.env_groups(net.default_env_groups() if env_groups is None else env_groups)
-        if (WINDOW_C and len(groups) == 1 and not split_update and not self.collectives
+        if (WINDOW_C and not ppo and len(groups) == 1 and not split_update and not self.collectives
                 and net.arch == net.base_arch and net.base_arch in (ARCH_FF, ARCH_LSTM)):
             # one C call: T x (observe, act), bootstrap, learn, clip + RMSProp, advance (arl_run_window)
             net.run_window(pair_pool, reward_pool, done_pool, pool_len, first, self.resize_mode, self.gamma, self.beta,
@@ -481,7 +536,7 @@ class A3C:
             return
         if len(groups) == 1:
             # FF: the learner's returns ride on the bootstrap policy launch (as arl_run_window does)
-            fuse = FUSE_RETURNS and net.base_arch == ARCH_FF and net.arch != ARCH_FF_NATURE
+            fuse = FUSE_RETURNS and not ppo and net.base_arch == ARCH_FF and net.arch != ARCH_FF_NATURE
             if fuse:
                 net.set_returns_fusion(True, self.gamma, self.beta, self._vcoef, self.clip_reward)
             try:
@@ -515,6 +570,10 @@ class A3C:
             for s in side:
                 main.wait_stream(s)
             stream = main
+        if ppo:
+            self._update_ppo(stream)
+            self.t += T
+            return
         self._learn(stream)
         if split_update:
             return

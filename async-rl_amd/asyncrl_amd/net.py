@@ -338,8 +338,42 @@ class DeviceNet:
         the lambda it was captured with."""
         check(lib.arl_net_set_gae(self._h, float(lambda_)), "arl_net_set_gae")
 
+    # ------------------------------------------------------------ PPO epochs
+    ppo_snap = None   # (4, t_max, n_envs) f32: logp_old, adv, ret, ratio; allocated by the first set_ppo
+    ppo_clip = None   # clip_eps while PPO is on, else None
+
+    def set_ppo(self, clip_eps: float | None = 0.2):
+        """Run the window's update as clipped-surrogate epochs (arl_net_set_ppo):
+        ppo_begin after the bootstrap forward, then per epoch [act(t, mode=0)
+        for t < t_max,] ppo_learn and optimize.  FF nets with the NIPS head
+        only.  None switches it off.  run_window (the one-call window) refuses
+        while it is on."""
+        if clip_eps is None:
+            check(lib.arl_net_set_ppo(self._h, None, 0.0), "arl_net_set_ppo")
+            self.ppo_clip = None
+            return
+        if self.ppo_snap is None:
+            self.ppo_snap = torch.zeros((4, self.t_max, self.n_envs), dtype=torch.float32, device=self.device)
+        check(lib.arl_net_set_ppo(self._h, ptr(self.ppo_snap), float(clip_eps)), "arl_net_set_ppo")
+        self.ppo_clip = float(clip_eps)
+
+    def ppo_begin(self, gamma=0.99, clip_reward=True, stream=None):
+        """The window's snapshot (logp_old, adv, ret) from the workspace, after
+        the bootstrap forward (arl_ppo_begin)."""
+        check(lib.arl_ppo_begin(self._h, gamma, int(clip_reward), stream_handle(stream)), "arl_ppo_begin")
+
+    def ppo_learn(self, beta=1e-2, v_loss_coef=0.5, stream=None):
+        """One epoch's gradient from the slots' current contents (arl_ppo_learn)."""
+        check(lib.arl_ppo_learn(self._h, beta, v_loss_coef, stream_handle(stream)), "arl_ppo_learn")
+
+    def ppo_planes(self) -> dict:
+        """Views of the snapshot's four (t_max, n_envs) planes."""
+        if self.ppo_snap is None:
+            raise RuntimeError("ppo_planes: PPO was never set (set_ppo)")
+        return dict(zip(("logp_old", "adv", "ret", "ratio"), self.ppo_snap))
+
     # ------------------------------------------------------------ Adam
-    adam_m = None     # Adam's first moment (flat f32, the params' layout), allocated by the first set_adam
+    adam_m = None    # Adam's first moment (flat f32, the params' layout), allocated by the first set_adam
     adam_betas = None   # (beta1, beta2) while Adam is the net's optimizer, else None
 
     def set_adam(self, beta1: float | None = 0.9, beta2: float = 0.999):

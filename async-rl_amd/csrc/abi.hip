@@ -192,6 +192,7 @@ int arl_net_reset(arl_net* h, void* s) {
   if (e == hipSuccess && n.w_fcb_tick)
     e = hipMemsetAsync(n.ws + n.w_fcb_tick, 0, (size_t)arl::fc_bwd_tickets() * 4, S(s));
   n.returns_done = false;
+  n.ppo_begun = false;
   if (e == hipSuccess && n.arch == arl::ARCH_LSTM) {
     e = hipMemsetAsync(n.ws + n.w_hbuf, 0, (size_t)(n.T + 2) * n.N * arl::HID * 4, S(s));
     if (e == hipSuccess) e = hipMemsetAsync(n.ws + n.w_cbuf, 0, (size_t)(n.T + 2) * n.N * arl::HID * 4, S(s));
@@ -455,6 +456,38 @@ int arl_net_set_gae(arl_net* h, double lambda) {
   if (!gae_lambda_ok(lambda)) return fail(ARL_EINVAL, "set_gae: lambda must be finite and in [0, 1]");
   h->net.gae_lambda = lambda;
   return ARL_OK;
+}
+
+int arl_net_set_ppo(arl_net* h, float* snap, double clip_eps) {
+  if (!h) return fail(ARL_EINVAL, "null net");
+  arl::Net& n = h->net;
+  if (!snap) {   // back to one gradient step per window
+    n.ppo_snap = nullptr;
+    n.ppo_begun = false;
+    return ARL_OK;
+  }
+  if (!(clip_eps > 0.0 && clip_eps < 1.0)) return fail(ARL_EINVAL, "set_ppo: clip_eps must be finite and in (0, 1)");
+  if (!aligned(snap, 16)) return fail(ARL_EINVAL, "set_ppo: snap must be 16-byte aligned");
+  if (n.arch != arl::ARCH_FF)
+    return fail(ARL_ESTATE, "set_ppo: FF nets with the NIPS head only (not the LSTM, not the Nature head)");
+  n.ppo_snap = snap;
+  n.ppo_lo = (float)(1.0 - clip_eps);
+  n.ppo_hi = (float)(1.0 + clip_eps);
+  n.ppo_begun = false;
+  return ARL_OK;
+}
+
+int arl_ppo_begin(arl_net* h, double gamma, int clip_reward, void* s) {
+  NEED_BOUND(h);
+  if (!h->net.ppo_snap) return fail(ARL_ESTATE, "ppo_begin: PPO is off (arl_net_set_ppo)");
+  return hip_status(arl::net_ppo_begin(h->net, gamma, clip_reward, S(s)), "ppo_begin");
+}
+
+int arl_ppo_learn(arl_net* h, double beta, double vcoef, void* s) {
+  NEED_BOUND(h);
+  if (!h->net.ppo_snap) return fail(ARL_ESTATE, "ppo_learn: PPO is off (arl_net_set_ppo)");
+  if (!h->net.ppo_begun) return fail(ARL_ESTATE, "ppo_learn: no arl_ppo_begin since the last window advance");
+  return hip_status(arl::net_ppo_learn(h->net, (float)beta, (float)vcoef, S(s)), "ppo_learn");
 }
 
 int arl_act(arl_net* h, int t, void* s) {
@@ -745,6 +778,7 @@ int arl_run_window(arl_net* h, const uint8_t* pair_pool, const float* reward_poo
                    double clip, void* s) {
   NEED_BOUND(h);
   arl::Net& n = h->net;
+  if (n.ppo_snap) return fail(ARL_ESTATE, "run_window: a single-call window has no epochs (arl_net_set_ppo is on)");
   if (n.rgb || n.stack || n.states || n.arch == arl::ARCH_FF_NATURE)
     return fail(ARL_ESTATE, "run_window: frame-pair nets with the NIPS head only (FF / LSTM)");
   if (resize_mode < 0 || resize_mode > (ARL_RESIZE_SIMD | ARL_RESIZE_CROP)) return fail(ARL_EINVAL, "bad resize_mode");
@@ -928,6 +962,33 @@ int arl_returns_lossgrad_gae(const float* rewards, const uint8_t* dones, const f
                                         (float)vcoef, clip_reward, dlogits, dv, loss, S(s), nullptr,
                                         (float)pi_loss_coef, keep_loss_scale_same ? 1 : 0, lambda),
                     "returns_gae");
+}
+
+int arl_ppo_snapshot(const float* rewards, const uint8_t* dones, const float* v, const float* logp, const int32_t* act,
+                     int T, int64_t n, int A, double gamma, double lambda, int clip_reward, float* logp_old,
+                     float* adv, float* ret, void* s) {
+  if (T < 1 || T > 256 || n < 0 || n > INT32_MAX / 256 || A < 1) return fail(ARL_EINVAL, "ppo_snapshot: bad T / n / A");
+  if (n > 0 && (!rewards || !dones || !v || !logp || !act || !logp_old || !adv || !ret))
+    return fail(ARL_EINVAL, "ppo_snapshot: null pointer");
+  if (!gae_lambda_ok(lambda)) return fail(ARL_EINVAL, "ppo_snapshot: lambda must be finite and in [0, 1]");
+  return hip_status(arl::launch_ppo_snapshot(rewards, dones, v, logp, act, T, (int)n, A, gamma, lambda, clip_reward,
+                                             logp_old, adv, ret, S(s)),
+                    "ppo_snapshot");
+}
+
+int arl_ppo_lossgrad(const uint8_t* dones, const float* v, const float* probs, const float* logp, const int32_t* act,
+                     const float* logp_old, const float* adv, const float* ret, int T, int64_t n, int A,
+                     double clip_eps, double beta, double pi_loss_coef, double vcoef, int keep_loss_scale_same,
+                     float* dlogits, float* dv, float* loss, float* ratio_out, void* s) {
+  if (T < 1 || T > 256 || n < 0 || n > INT32_MAX / 256 || A < 1 || A > arl::MAXA)
+    return fail(ARL_EINVAL, "ppo_lossgrad: bad T / n / A");
+  if (n > 0 && (!dones || !v || !probs || !logp || !act || !logp_old || !adv || !ret || !dlogits || !dv))
+    return fail(ARL_EINVAL, "ppo_lossgrad: null pointer");
+  if (!(clip_eps > 0.0 && clip_eps < 1.0)) return fail(ARL_EINVAL, "ppo_lossgrad: clip_eps must be finite and in (0, 1)");
+  const arl::PpoLossArgs p{dones, v, probs, logp, act, logp_old, adv, ret, T, (int)n, A, (float)(1.0 - clip_eps),
+                           (float)(1.0 + clip_eps), (float)beta, (float)vcoef, (float)pi_loss_coef,
+                           keep_loss_scale_same ? 1 : 0, dlogits, dv, loss, ratio_out};
+  return hip_status(arl::launch_ppo_lossgrad(p, S(s)), "ppo_lossgrad");
 }
 
 int arl_stream_copy(const void* src, void* dst, int64_t bytes, int blocks, int mode, void* s) {

@@ -269,7 +269,13 @@ struct Net {
   // GAE(lambda) advantages of the policy term (arl_net_set_gae; 1 = the n-step advantage, today's kernels):
   // read at every returns launch; win_lambda = that of the net's last returns launch, beside win_gamma
   double gae_lambda = 1.0, win_lambda = 1.0;
-  int hid;                 // width of the layer the heads read (256 NIPS / LSTM, 512 Nature)
+  // arl_net_set_ppo: non-null = the window's update runs as clipped-surrogate epochs (arl_ppo_begin, arl_ppo_learn)
+  // on this snapshot, 4 planes of T * N f32: logp_old, adv, ret, ratio; ppo_lo / ppo_hi = the clip range as f32;
+  // ppo_begun = arl_ppo_begin took the snapshot of the current window (cleared by the window advance)
+  float* ppo_snap = nullptr;
+  float ppo_lo = 0.8f, ppo_hi = 1.2f;
+  bool ppo_begun = false;
+  int hid;                // width of the layer the heads read (256 NIPS / LSTM, 512 Nature)
   int env_offset;          // global id of env 0 on this rank (RNG stream)
   uint64_t seed;
   std::vector<ParamInfo> params;
@@ -313,6 +319,10 @@ hipError_t ensure_fc_planes(Net& net, hipStream_t s);   // rebuild the FC weight
 enum { LEARN_RETURNS = 0, LEARN_TRUNK, LEARN_CONV, LEARN_PARTS };
 hipError_t net_learn_part(Net& net, int part, double gamma, float beta, float vcoef, int clip_reward, hipStream_t s);
 hipError_t net_learn(Net& net, double gamma, float beta, float vcoef, int clip_reward, hipStream_t s);
+// PPO epochs (net.ppo_snap set, FF): the window's snapshot after its bootstrap forward, and one epoch's gradient
+// from the slots' current contents (loss gradient + heads dh, LEARN_TRUNK, LEARN_CONV; no folded clip norm)
+hipError_t net_ppo_begin(Net& net, double gamma, int clip_reward, hipStream_t s);
+hipError_t net_ppo_learn(Net& net, float beta, float vcoef, hipStream_t s);
 // advance: also end the window, folded into the update kernel (arl_learn
 // snapshots the step counter, so the update's lr anneal does not race it).
 hipError_t net_optimize(Net& net, double lr0, int64_t total_steps, int64_t n_total, double alpha, double eps,
@@ -606,6 +616,28 @@ hipError_t launch_returns_heads(const float* rewards, const uint8_t* dones, cons
                                 float vcoef, int clip_reward, float* dlogits, float* dv, float* loss, hipStream_t s,
                                 int64_t* ctl_snap, float pcoef, int keep_scale, const float* Wpi, const float* Wv,
                                 const float* mask, float* dh, double lambda = 1.0);
+// Clipped-surrogate (PPO) epochs on a window's rollout (arl_net_set_ppo has the definition; policy.hip).
+// launch_ppo_snapshot: lpo / adv / ret (T, n) of the window, from return_step / gae_step (lambda != 1) as the
+// returns launch forms them.  launch_ppo_lossgrad: the loss gradient of one epoch from the slots' current probs /
+// logp / v and the snapshot (the PPO form of launch_returns); launch_ppo_heads: + the heads' dh and the step
+// snapshot (the PPO form of launch_returns_heads, T <= 64).
+hipError_t launch_ppo_snapshot(const float* rewards, const uint8_t* dones, const float* v, const float* logp,
+                               const int32_t* act, int T, int n, int A, double gamma, double lambda, int clip_reward,
+                               float* lpo, float* adv, float* ret, hipStream_t s);
+struct PpoLossArgs {
+  const uint8_t* dones;
+  const float *v, *probs, *logp;
+  const int32_t* act;
+  const float *lpo, *adv, *ret;   // the snapshot
+  int T, n, A;
+  float lo, hi;                   // (float)(1.0 - eps_clip), (float)(1.0 + eps_clip)
+  float beta, vcoef, pcoef;
+  int keep_scale;
+  float *dlogits, *dv, *loss, *ratio;   // loss, ratio: nullable
+};
+hipError_t launch_ppo_lossgrad(const PpoLossArgs& p, hipStream_t s);
+hipError_t launch_ppo_heads(const PpoLossArgs& p, int64_t* ctl_snap, const float* Wpi, const float* Wv,
+                            const float* mask, float* dh, hipStream_t s);
 // launch_policy_fc of the bootstrap slot (no draw) + launch_returns_heads for the same n envs, one launch
 // (policy.hip policy_fc_returns_kernel; v(s_T) handed over in LDS); bit-identical to the two launches
 hipError_t launch_policy_fc_returns(const float* slab, int n, const float* fc_bias, float* hfc, const PolicyArgs& pa,

@@ -388,7 +388,8 @@ hipError_t net_act(Net& net, int t, int mode, hipStream_t s, int e0, int ne) {
   if (net.arch != ARCH_LSTM) {   // FF: split-K partials, reduce + relu + heads in one policy_fc launch
     ARL_TRY(launch_fc_fwd(a2 + (int64_t)e0 * A2, ne, fc_planes(net), P + net.o_fcb, fc_slab, nullptr, nullptr, s));
     ARL_TRY(stamp(net, STAGE_FC_FWD, s));
-    if (t == net.T && net.fuse_returns && e0 == 0 && ne == n) {   // + the learner's returns (one env group)
+    // + the learner's returns (one env group); not while the update runs as PPO epochs (arl_ppo_begin / arl_ppo_learn)
+    if (t == net.T && net.fuse_returns && net.ppo_snap == nullptr && e0 == 0 && ne == n) {
       const Net::ReturnsCfg& r = net.ret;
       ARL_TRY(launch_policy_fc_returns(fc_slab, ne, P + net.o_fcb, hfc, pa, net.at<float>(net.w_rewards),
                                        net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v),
@@ -526,6 +527,39 @@ hipError_t net_learn(Net& net, double gamma, float beta, float vcoef, int clip_r
   ARL_TRY(conv_backward(net, s, norm_fold_args(net)));
   net.norm_ready = net.norm_fold;
   return hipSuccess;
+}
+
+// PPO epochs (arl_net_set_ppo; FF nets): the window's snapshot from the workspace, after its bootstrap forward
+hipError_t net_ppo_begin(Net& net, double gamma, int clip_reward, hipStream_t s) {
+  const int64_t S = (int64_t)net.T * net.N;
+  float* snap = net.ppo_snap;
+  net.returns_done = false;
+  net.win_gamma = gamma;   // as a returns launch: the window statistics repeat the snapshot's returns
+  net.win_clip_reward = clip_reward;
+  net.win_lambda = net.gae_lambda;
+  ARL_TRY(launch_ppo_snapshot(net.at<float>(net.w_rewards), net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v),
+                              net.at<float>(net.w_logp), net.at<int32_t>(net.w_act), net.T, net.N, net.A, gamma,
+                              net.gae_lambda, clip_reward, snap, snap + S, snap + 2 * S, s));
+  net.ppo_begun = true;
+  return stamp(net, STAGE_OTHER, s);
+}
+
+// One epoch's gradient: the PPO loss gradient + heads dh (it also snapshots the step counter, as the returns
+// launch it stands in for), then the trunk and conv parts unchanged
+hipError_t net_ppo_learn(Net& net, float beta, float vcoef, hipStream_t s) {
+  const int64_t S = (int64_t)net.T * net.N;
+  float* snap = net.ppo_snap;
+  const PpoLossArgs p{net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v), net.at<float>(net.w_probs),
+                      net.at<float>(net.w_logp), net.at<int32_t>(net.w_act), snap, snap + S, snap + 2 * S, net.T, net.N,
+                      net.A, net.ppo_lo, net.ppo_hi, beta, vcoef, net.pi_coef, net.keep_scale,
+                      net.at<float>(net.w_dlogits), net.at<float>(net.w_dv), net.at<float>(net.w_loss), snap + 3 * S};
+  net.norm_ready = false;   // a new gradient, no folded norm
+  net.returns_done = false;
+  ARL_TRY(launch_ppo_heads(p, net.at<int64_t>(net.w_ctl), net.p + net.o_piW, net.p + net.o_vW,
+                           net.at<float>(net.w_hfc), net.at<float>(net.w_dfc), s));
+  ARL_TRY(stamp(net, STAGE_RETURNS, s));
+  ARL_TRY(net_learn_part(net, LEARN_TRUNK, 0.0, beta, vcoef, 0, s));
+  return net_learn_part(net, LEARN_CONV, 0.0, beta, vcoef, 0, s);
 }
 
 // LSTM gate weight gradients ([x | h_prev] operand, reset rows' h dropped) straight into the gradient
@@ -753,12 +787,14 @@ hipError_t net_optimize(Net& net, double lr0, int64_t total_steps, int64_t n_tot
   else
     ARL_TRY(launch_rmsprop(net.p, net.ms, net.g, net.param_floats, lr0, alpha, eps, u, s));
   ARL_TRY(stamp(net, STAGE_RMSPROP, s));
+  if (advance) net.ppo_begun = false;   // the next window's epochs need their own snapshot
   return advance && !fused ? net_advance(net, s) : hipSuccess;
 }
 
 hipError_t net_advance(Net& net, hipStream_t s) {
   const bool L = net.arch == ARCH_LSTM;
   const int64_t cnt = L ? (int64_t)net.N * HID : net.N;
+  net.ppo_begun = false;
   hipLaunchKernelGGL(advance_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, net.at<int64_t>(net.w_ctl),
                      net.T, net.at<uint8_t>(net.w_reset), net.N, L ? net.at<float>(net.w_hbuf) : nullptr,
                      L ? net.at<float>(net.w_cbuf) : nullptr);

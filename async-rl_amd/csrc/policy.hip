@@ -152,12 +152,27 @@ struct ReturnsArgs {
   float* loss;
   int64_t* ctl;
 };
-// the GAE form's arguments (below): + gl = gamma * lambda.  ReturnsArgsT<false> is ReturnsArgs itself.
+// The launch's form G, compile time: the n-step advantage, the GAE one, or a clipped-surrogate (PPO) epoch on a
+// window's snapshot (arl_net_set_ppo).  false / true in a template argument list are RF_NSTEP / RF_GAE.
+// (ints, not an unnamed enum: the forms appear in the kernels' mangled names through ReturnsArgsT, and an unnamed
+// type there is numbered differently by the host and the device compilation)
+constexpr int RF_NSTEP = 0, RF_GAE = 1, RF_PPO = 2;
+// the GAE form's arguments (below): + gl = gamma * lambda.  ReturnsArgsT<RF_NSTEP> is ReturnsArgs itself.
 struct ReturnsArgsGae : ReturnsArgs {
   double gl;
 };
-template <bool G>
-using ReturnsArgsT = std::conditional_t<G, ReturnsArgsGae, ReturnsArgs>;
+// the PPO form's arguments (below): + the snapshot's planes, the ratio's output (or null) and the clip range
+// lo = (float)(1.0 - eps_clip), hi = (float)(1.0 + eps_clip); rewards and gamma are not read
+struct ReturnsArgsPpo : ReturnsArgs {
+  const float* lpo;
+  const float* adv;
+  const float* ret;
+  float* ratio;
+  float lo, hi;
+};
+template <int G>
+using ReturnsArgsT =
+    std::conditional_t<G == RF_PPO, ReturnsArgsPpo, std::conditional_t<G == RF_GAE, ReturnsArgsGae, ReturnsArgs>>;
 
 // dlogits / dv of (step t, env e); returns the two loss terms of the step
 // (pi term without the sign, v term) through lpi / lv
@@ -171,23 +186,30 @@ constexpr int RW = 8;
 // is the GAE(lambda) one (gae_step) instead of f32(Rf - v); the value target stays the n-step return.  It
 // carries gl = gamma * lambda and the register window of v: v[0 .. RW-1] at clamped offsets beside vboot, the
 // RW + 1 values v[k + 1] is taken from.  The G = false forms hold and do nothing more than they did.
-template <bool G>
+// PPO form (RF_PPO; the host picks it while arl_net_set_ppo is on): the return and the advantage are the
+// snapshot's (ppo_snapshot_kernel left there what the two forms above would form), the policy term is the clipped
+// surrogate's with the ratio exp(lp[ac] - lpo).  It scans only the dones, for the segment of keep_loss_scale_same.
+template <int G>
 struct GaeIn {};
 template <>
-struct GaeIn<true> {
+struct GaeIn<RF_GAE> {
   float vw[RW];
   double gl;
 };
+template <>
+struct GaeIn<RF_PPO> {
+  float lpo, adv, Rf;
+};
 // AM >= A: the action count the registers are sized for (4 / 8 / MAXA)
-template <int AM, bool G = false>
+template <int AM, int G = RF_NSTEP>
 struct RetIn : GaeIn<G> {   // everything returns_one reads of step (t, e)
   float pr[AM], lp[AM], rw[RW];
   int dn[RW];
   float vboot, vi;
   int ac, di;
 };
-template <int AM, bool G>
-__device__ inline void returns_load(const ReturnsArgs& a, int t, int e, RetIn<AM, G>& in) {
+template <int AM, int G>
+__device__ inline void returns_load(const ReturnsArgsT<G>& a, int t, int e, RetIn<AM, G>& in) {
   const int T = a.T, n = a.n, A = a.A;
   const int64_t i = (int64_t)t * n + e;
 #pragma unroll
@@ -199,17 +221,23 @@ __device__ inline void returns_load(const ReturnsArgs& a, int t, int e, RetIn<AM
 #pragma unroll
   for (int k = 0; k < RW; ++k) {
     const int64_t o = (int64_t)min(k, T - 1) * n + e;
-    in.rw[k] = a.rewards[o];
+    if constexpr (G != RF_PPO) in.rw[k] = a.rewards[o];
     in.dn[k] = a.dones[o];
-    if constexpr (G) in.vw[k] = a.v[o];
+    if constexpr (G == RF_GAE) in.vw[k] = a.v[o];
   }
-  in.vboot = a.v[(int64_t)T * n + e];
+  if constexpr (G == RF_PPO) {
+    in.lpo = a.lpo[i];
+    in.adv = a.adv[i];
+    in.Rf = a.ret[i];
+  } else {
+    in.vboot = a.v[(int64_t)T * n + e];
+  }
   in.vi = a.v[i];
   in.ac = a.act[i];
   in.di = a.dones[i];
 }
-template <int AM, bool G>
-__device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const RetIn<AM, G>& in, float& lpi,
+template <int AM, int G>
+__device__ inline void returns_compute(const ReturnsArgsT<G>& a, int t, int e, const RetIn<AM, G>& in, float& lpi,
                                        float& lv, float* sdl) {
   const int T = a.T, n = a.n, A = a.A;
   const int64_t i = (int64_t)t * n + e;
@@ -217,7 +245,9 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
   const float* lp = in.lp;
   const float* rw = in.rw;
   const int* dn = in.dn;
-  const float vboot = in.vboot, vi = in.vi;
+  float vboot = 0.f;
+  if constexpr (G != RF_PPO) vboot = in.vboot;
+  const float vi = in.vi;
   const int ac = in.ac, di = in.di;
   float* dl = a.dlogits + i * A;
   if (di & 2) {   // past the end of this window
@@ -225,6 +255,8 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
     a.dv[i] = 0.f;
     if (sdl)
       for (int k = 0; k <= A; ++k) sdl[k] = 0.f;
+    if constexpr (G == RF_PPO)
+      if (a.ratio != nullptr) a.ratio[i] = 0.f;
     lpi = 0.f;
     lv = 0.f;
     return;
@@ -238,8 +270,8 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
     for (int k = RW - 1; k >= 0; --k)
       if (k < T && k >= t) {
         if (dn[k] & 1) seg_end = k;
-        R = return_step(R, dn[k], rw[k], a.gamma, a.clip_reward);
-        if constexpr (G)   // v[k + 1]: the bootstrap value at the window's last step (k = RW - 1 is always that)
+        if constexpr (G != RF_PPO) R = return_step(R, dn[k], rw[k], a.gamma, a.clip_reward);
+        if constexpr (G == RF_GAE)   // v[k + 1]: the bootstrap value at the window's last step (k = RW - 1 is always that)
           Gl = gae_step(Gl, dn[k], rw[k], in.vw[k], k == T - 1 ? vboot : in.vw[k < RW - 1 ? k + 1 : k], a.gamma,
                         in.gl, a.clip_reward);
       }
@@ -250,8 +282,8 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
     for (int tt = T - 1; tt >= t; --tt) {
       const int64_t j = (int64_t)tt * n + e;
       if (a.dones[j] & 1) seg_end = tt;
-      R = return_step(R, a.dones[j], a.rewards[j], a.gamma, a.clip_reward);
-      if constexpr (G)
+      if constexpr (G != RF_PPO) R = return_step(R, a.dones[j], a.rewards[j], a.gamma, a.clip_reward);
+      if constexpr (G == RF_GAE)
         Gl = gae_step(Gl, a.dones[j], a.rewards[j], a.v[j], tt == T - 1 ? vboot : a.v[j + n], a.gamma, in.gl,
                       a.clip_reward);
     }
@@ -270,10 +302,15 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
       vf = __fmul_rn(vf, factor);
     }
   }
-  const float Rf = (float)R;
-  float adv;
-  if constexpr (G) adv = (float)Gl;
-  else adv = __fsub_rn(Rf, vi);
+  float Rf, adv;
+  if constexpr (G == RF_PPO) {
+    Rf = in.Rf;
+    adv = in.adv;
+  } else {
+    Rf = (float)R;
+    if constexpr (G == RF_GAE) adv = (float)Gl;
+    else adv = __fsub_rn(Rf, vi);
+  }
   float H = 0.f, lpa = 0.f;
 #pragma unroll
   for (int k = 0; k < AM; ++k)
@@ -282,11 +319,21 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
       if (k == ac) lpa = lp[k];
     }
   H = -H;
+  // the policy term's weight w (of the gradient) and its loss term: adv and lp[ac] * adv, or the clipped
+  // surrogate's (the header's "clipped-surrogate epochs"); rho == 1 leaves w == adv
+  float w = adv, surr = 0.f;
+  if constexpr (G == RF_PPO) {
+    const float rho = (float)exp((double)__fsub_rn(lpa, in.lpo));
+    const bool active = adv >= 0.f ? rho <= a.hi : rho >= a.lo;
+    w = active ? __fmul_rn(rho, adv) : 0.f;
+    surr = active ? w : __fmul_rn(adv >= 0.f ? a.hi : a.lo, adv);
+    if (a.ratio != nullptr) a.ratio[i] = rho;
+  }
 #pragma unroll
   for (int k = 0; k < AM; ++k)
     if (k < A) {
       const float oh = (k == ac) ? 1.f : 0.f;
-      const float t1 = __fmul_rn(-adv, __fsub_rn(oh, pr[k]));
+      const float t1 = __fmul_rn(-w, __fsub_rn(oh, pr[k]));
       const float t2 = __fmul_rn(__fmul_rn(a.beta, pr[k]), __fadd_rn(lp[k], H));
       const float d = __fmul_rn(pf, __fadd_rn(t1, t2));
       dl[k] = d;
@@ -296,15 +343,18 @@ __device__ inline void returns_compute(const ReturnsArgs& a, int t, int e, const
   const float dvo = __fmul_rn(vf, dvv);
   a.dv[i] = dvo;
   if (sdl) sdl[A] = dvo;
-  lpi = __fmul_rn(pf, __fadd_rn(__fmul_rn(lpa, adv), __fmul_rn(a.beta, H)));
+  float pterm;
+  if constexpr (G == RF_PPO) pterm = surr;
+  else pterm = __fmul_rn(lpa, adv);
+  lpi = __fmul_rn(pf, __fadd_rn(pterm, __fmul_rn(a.beta, H)));
   lv = __fmul_rn(vf, __fmul_rn(__fmul_rn(dvv, dvv), 0.5f));
 }
-template <bool G>
+template <int G>
 __device__ inline void returns_one(const ReturnsArgsT<G>& a, int t, int e, float& lpi, float& lv) {
   RetIn<MAXA, G> in;
-  if constexpr (G) in.gl = a.gl;
-  returns_load(a, t, e, in);
-  returns_compute(a, t, e, in, lpi, lv, nullptr);
+  if constexpr (G == RF_GAE) in.gl = a.gl;
+  returns_load<MAXA, G>(a, t, e, in);
+  returns_compute<MAXA, G>(a, t, e, in, lpi, lv, nullptr);
 }
 
 // per-env losses summed in the reference's order (t = T-1 .. 0)
@@ -318,7 +368,7 @@ __device__ inline void env_loss(const ReturnsArgs& a, const float* lpi, const fl
   a.loss[2 * e + 1] = v_loss;
 }
 
-template <bool G = false>
+template <int G = RF_NSTEP>
 __global__ void __launch_bounds__(256)
 returns_kernel(ReturnsArgsT<G> a) {
   __shared__ float lpi[256], lv[256];
@@ -333,6 +383,60 @@ returns_kernel(ReturnsArgsT<G> a) {
   if (t == 0 && on) env_loss(a, lpi, lv, EB, el, e);
 }
 
+// The snapshot a window's PPO epochs share (arl_net_set_ppo), one thread per (step t, env) as returns_kernel:
+// lpo = logp[t, e, act[t, e]], ret = Rf and adv as the G form of returns_compute forms them (the same loads, the
+// same device functions in the same order), or 0, 0, 0 past a truncated window's end.  G: RF_NSTEP or RF_GAE.
+struct SnapArgs : ReturnsArgsGae {   // probs: any readable (T, n, A) array (not used), dlogits / dv / loss: null
+  float* lpo_out;
+  float* adv_out;
+  float* ret_out;
+};
+template <int G>
+__global__ void __launch_bounds__(256)
+ppo_snapshot_kernel(SnapArgs a) {
+  const int EB = 256 / a.T;
+  const int tid = threadIdx.x, t = tid / EB, el = tid - t * EB;
+  const int e = blockIdx.x * EB + el;
+  if (t >= a.T || e >= a.n) return;
+  RetIn<1, G> in;
+  if constexpr (G == RF_GAE) in.gl = a.gl;
+  returns_load<1, G>(a, t, e, in);
+  const int64_t i = (int64_t)t * a.n + e;
+  const float lpa = a.logp[i * a.A + min(max(in.ac, 0), a.A - 1)];
+  float lpo = 0.f, adv = 0.f, Rf = 0.f;
+  if (!(in.di & 2)) {
+    // returns_compute's scan of R (and Gl) without the segment bookkeeping -- its own copy: with the scan in a
+    // function the two shared, the existing forms no longer compiled to the instructions they had
+    const float vboot = in.vboot;
+    double R = (double)vboot, Gl = 0.0;
+    if (a.T <= RW) {
+#pragma unroll
+      for (int k = RW - 1; k >= 0; --k)
+        if (k < a.T && k >= t) {
+          R = return_step(R, in.dn[k], in.rw[k], a.gamma, a.clip_reward);
+          if constexpr (G == RF_GAE)
+            Gl = gae_step(Gl, in.dn[k], in.rw[k], in.vw[k], k == a.T - 1 ? vboot : in.vw[k < RW - 1 ? k + 1 : k],
+                          a.gamma, in.gl, a.clip_reward);
+        }
+    } else {
+      for (int tt = a.T - 1; tt >= t; --tt) {
+        const int64_t j = (int64_t)tt * a.n + e;
+        R = return_step(R, a.dones[j], a.rewards[j], a.gamma, a.clip_reward);
+        if constexpr (G == RF_GAE)
+          Gl = gae_step(Gl, a.dones[j], a.rewards[j], a.v[j], tt == a.T - 1 ? vboot : a.v[j + a.n], a.gamma, in.gl,
+                        a.clip_reward);
+      }
+    }
+    Rf = (float)R;
+    if constexpr (G == RF_GAE) adv = (float)Gl;
+    else adv = __fsub_rn(Rf, in.vi);
+    lpo = lpa;
+  }
+  a.lpo_out[i] = lpo;
+  a.adv_out[i] = adv;
+  a.ret_out[i] = Rf;
+}
+
 // returns_kernel + the heads' backward (a3c.py:129-130 through policy.py /
 // v_function.py): dh[s][j] = sum_k dlogits[s][k] Wpi[k][j] + dv[s] Wv[j],
 // times (mask[s][j] > 0) when mask is given, for the T steps of one env per
@@ -345,7 +449,7 @@ returns_kernel(ReturnsArgsT<G> a) {
 // AM >= A actions, RB rows (steps) per pass: the register arrays (mask
 // entries, head-weight column, loaded probs / log-probs) are sized for the
 // window, e.g. 5 rows and 4 actions at C2 instead of 32 and 32
-template <int AM, int RB, bool G = false>
+template <int AM, int RB, int G = RF_NSTEP>
 struct RhState {
   float mv[RB];
   int64_t so[RB];
@@ -355,7 +459,7 @@ struct RhState {
 
 // mask entries of rows r0 .. r0 + RB - 1 (row r = step r of env e) for column j = threadIdx.x
 // (unconditional loads at clamped offsets: a load under a per-lane branch would wait for each one in turn)
-template <int AM, int RB, bool G>
+template <int AM, int RB, int G>
 __device__ inline void rh_rows(const ReturnsArgs& a, const float* __restrict__ mask, int e, int r0,
                                RhState<AM, RB, G>& st) {
   const int j = threadIdx.x;
@@ -368,19 +472,19 @@ __device__ inline void rh_rows(const ReturnsArgs& a, const float* __restrict__ m
   for (int u = 0; u < RB; ++u) st.mv[u] = mask != nullptr ? mask[st.so[u] < 0 ? j : st.so[u]] : 1.f;
 }
 
-template <int AM, int RB, bool G>
-__device__ inline void rh_load(const ReturnsArgs& a, const float* __restrict__ Wpi, const float* __restrict__ Wv,
+template <int AM, int RB, int G>
+__device__ inline void rh_load(const ReturnsArgsT<G>& a, const float* __restrict__ Wpi, const float* __restrict__ Wv,
                                const float* __restrict__ mask, int e, RhState<AM, RB, G>& st) {
   const int T = a.T, A = a.A, j = threadIdx.x;
   rh_rows(a, mask, e, 0, st);
 #pragma unroll
   for (int k = 0; k <= AM; ++k) st.wc[k] = k < A ? Wpi[min(k, A - 1) * HID + j] : Wv[j];
-  returns_load(a, min((int)threadIdx.x, T - 1), min(e, a.n - 1), st.in);   // off threads: a valid step, discarded
+  returns_load<AM, G>(a, min((int)threadIdx.x, T - 1), min(e, a.n - 1), st.in);   // off threads: a valid step, discarded
 }
 
 // lpi / lv: 64 floats, sdl: 64 (AM + 1), w: (AM + 1) HID of LDS
-template <int AM, int RB, bool G>
-__device__ inline void rh_finish(const ReturnsArgs& a, const float* __restrict__ mask, float* __restrict__ dh, int e,
+template <int AM, int RB, int G>
+__device__ inline void rh_finish(const ReturnsArgsT<G>& a, const float* __restrict__ mask, float* __restrict__ dh, int e,
                                  RhState<AM, RB, G>& st, float* lpi, float* lv, float* sdl, float* w) {
   const int T = a.T, A = a.A;
   const int tid = threadIdx.x, t = tid, j = tid;
@@ -388,7 +492,7 @@ __device__ inline void rh_finish(const ReturnsArgs& a, const float* __restrict__
 #pragma unroll
   for (int k = 0; k <= AM; ++k)
     if (k <= A) w[k * HID + j] = k < A ? st.wc[k] : st.wc[AM];   // thread j's own column
-  if (on) returns_compute(a, t, e, st.in, lpi[tid], lv[tid], sdl + tid * (A + 1));   // row tid = step t
+  if (on) returns_compute<AM, G>(a, t, e, st.in, lpi[tid], lv[tid], sdl + tid * (A + 1));   // row tid = step t
   __syncthreads();
   if (a.loss != nullptr && t == 0 && on) env_loss(a, lpi, lv, 1, 0, e);
   for (int r0 = 0; r0 < T; r0 += RB) {
@@ -405,7 +509,7 @@ __device__ inline void rh_finish(const ReturnsArgs& a, const float* __restrict__
   }
 }
 
-template <int AM, int RB, bool G = false>
+template <int AM, int RB, int G = RF_NSTEP>
 __global__ void __launch_bounds__(256)
 returns_heads_kernel(ReturnsArgsT<G> a, const float* __restrict__ Wpi, const float* __restrict__ Wv,
                      const float* __restrict__ mask, float* __restrict__ dh) {
@@ -414,9 +518,9 @@ returns_heads_kernel(ReturnsArgsT<G> a, const float* __restrict__ Wpi, const flo
   __shared__ float w[(AM + 1) * HID];
   if (a.ctl != nullptr && blockIdx.x == 0 && threadIdx.x == 0) a.ctl[CTL_STEP_SNAP] = a.ctl[CTL_STEP];
   RhState<AM, RB, G> st;
-  if constexpr (G) st.in.gl = a.gl;
-  rh_load(a, Wpi, Wv, mask, blockIdx.x, st);
-  rh_finish(a, mask, dh, blockIdx.x, st, lpi, lv, sdl, w);
+  if constexpr (G == RF_GAE) st.in.gl = a.gl;
+  rh_load<AM, RB, G>(a, Wpi, Wv, mask, blockIdx.x, st);
+  rh_finish<AM, RB, G>(a, mask, dh, blockIdx.x, st, lpi, lv, sdl, w);
 }
 
 // The FF window's bootstrap step (slot T, no draw) with the learner's first
@@ -427,7 +531,7 @@ returns_heads_kernel(ReturnsArgsT<G> a, const float* __restrict__ Wpi, const flo
 // before the FC partials' loads.  Results are bit-identical to the two
 // launches: the same per-element arithmetic in the same order.
 // GAE form: v(s_T) from LDS as here; the other v rows (slots 0 .. T - 1, earlier launches' stores) from memory.
-template <int AM, int RB, bool G = false>
+template <int AM, int RB, int G = RF_NSTEP>
 __global__ void __launch_bounds__(256)
 policy_fc_returns_kernel(const float* __restrict__ slab, int n, const float* __restrict__ fc_bias,
                          float* __restrict__ hfc, PolicyArgs pa, ReturnsArgsT<G> ra, const float* __restrict__ mask,
@@ -443,8 +547,8 @@ policy_fc_returns_kernel(const float* __restrict__ slab, int n, const float* __r
   const int e = blockIdx.x;
   if (ra.ctl != nullptr && e == 0 && tid == 0) ra.ctl[CTL_STEP_SNAP] = ra.ctl[CTL_STEP];
   RhState<AM, RB, G> st;
-  if constexpr (G) st.in.gl = ra.gl;
-  rh_load(ra, pa.Wpi, pa.Wv, mask, e, st);
+  if constexpr (G == RF_GAE) st.in.gl = ra.gl;
+  rh_load<AM, RB, G>(ra, pa.Wpi, pa.Wv, mask, e, st);
   const HeadsPrefetch<HID> pf = heads_prefetch<HID>(pa);
   // policy_fc_kernel's row (PF_ROWS = 1): threads 0..63 hold one float4 column of the 8 partials
   const int c = 4 * (tid & 63);
@@ -468,7 +572,7 @@ policy_fc_returns_kernel(const float* __restrict__ slab, int n, const float* __r
   __syncthreads();
   policy_rows16<HID, false, true, 1>(hl, e, n, pa, part, zs, &pf);   // ends with a barrier
   st.in.vboot = zs[0][pa.A];   // v(s_T) of env e (heads_row_out stored zs[0][A] to v)
-  rh_finish(ra, mask, dh, e, st, lpi, lv, sdl, w);
+  rh_finish<AM, RB, G>(ra, mask, dh, e, st, lpi, lv, sdl, w);
 }
 
 // gl = gamma * lambda: one f64 product, formed here on the host
@@ -520,6 +624,59 @@ hipError_t launch_returns_heads(const float* rewards, const uint8_t* dones, cons
   } else {
     hipLaunchKernelGGL((returns_heads_kernel<MAXA, 32>), grid, blk, 0, s, ra, Wpi, Wv, mask, dh);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_ppo_snapshot(const float* rewards, const uint8_t* dones, const float* v, const float* logp,
+                               const int32_t* act, int T, int n, int A, double gamma, double lambda, int clip_reward,
+                               float* lpo, float* adv, float* ret, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (T < 1 || T > 256) return hipErrorInvalidValue;
+  const int EB = 256 / T;
+  SnapArgs a;
+  static_cast<ReturnsArgs&>(a) = ReturnsArgs{rewards, dones, v, logp, logp, act, T, n, A, gamma, 0.f, 0.f, 0.f, clip_reward,
+                                             0, nullptr, nullptr, nullptr, nullptr};
+  a.gl = gamma * lambda;
+  a.lpo_out = lpo;
+  a.adv_out = adv;
+  a.ret_out = ret;
+  const dim3 grid((n + EB - 1) / EB), blk(256);
+  if (gae_on(lambda)) hipLaunchKernelGGL(ppo_snapshot_kernel<RF_GAE>, grid, blk, 0, s, a);
+  else hipLaunchKernelGGL(ppo_snapshot_kernel<RF_NSTEP>, grid, blk, 0, s, a);
+  return hipGetLastError();
+}
+
+static ReturnsArgsPpo ppo_args(const PpoLossArgs& p, int64_t* ctl_snap) {
+  ReturnsArgsPpo a;
+  static_cast<ReturnsArgs&>(a) = ReturnsArgs{nullptr, p.dones, p.v, p.probs, p.logp, p.act, p.T, p.n, p.A, 0.0, p.beta,
+                                             p.vcoef, p.pcoef, 0, p.keep_scale, p.dlogits, p.dv, p.loss, ctl_snap};
+  a.lpo = p.lpo;
+  a.adv = p.adv;
+  a.ret = p.ret;
+  a.ratio = p.ratio;
+  a.lo = p.lo;
+  a.hi = p.hi;
+  return a;
+}
+
+hipError_t launch_ppo_lossgrad(const PpoLossArgs& p, hipStream_t s) {
+  if (p.n <= 0) return hipSuccess;
+  if (p.T < 1 || p.T > 256) return hipErrorInvalidValue;
+  const int EB = 256 / p.T;
+  hipLaunchKernelGGL(returns_kernel<RF_PPO>, dim3((p.n + EB - 1) / EB), dim3(256), 0, s, ppo_args(p, nullptr));
+  return hipGetLastError();
+}
+
+hipError_t launch_ppo_heads(const PpoLossArgs& p, int64_t* ctl_snap, const float* Wpi, const float* Wv,
+                            const float* mask, float* dh, hipStream_t s) {
+  if (p.n <= 0) return hipSuccess;
+  if (p.T < 1 || p.T > 64 || p.A < 1 || p.A > MAXA) return hipErrorInvalidValue;
+  const ReturnsArgsPpo a = ppo_args(p, ctl_snap);
+  const dim3 grid(p.n), blk(256);
+  if (p.T > 8) hipLaunchKernelGGL((returns_heads_kernel<MAXA, 32, RF_PPO>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
+  else if (p.A <= 4) hipLaunchKernelGGL((returns_heads_kernel<4, 8, RF_PPO>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
+  else if (p.A <= 8) hipLaunchKernelGGL((returns_heads_kernel<8, 8, RF_PPO>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
+  else hipLaunchKernelGGL((returns_heads_kernel<MAXA, 8, RF_PPO>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
   return hipGetLastError();
 }
 

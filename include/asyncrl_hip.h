@@ -270,6 +270,82 @@ int arl_net_set_adam_t(arl_net* net, int64_t t, void* stream);
  * Addition to ABI 4. */
 int arl_net_set_gae(arl_net* net, double lambda);
 
+/* Clipped-surrogate epochs (PPO, Schulman et al. 2017): several gradient steps
+ * from one window's rollout.  An extension, off by default: the reference takes
+ * one step per window and discards the samples.  With it off every call makes
+ * exactly the launches it made before.  Additions to ABI 4.
+ *
+ * The rollout of a window runs as always: all t_max + 1 forwards with the
+ * pre-update parameters theta_old.  A snapshot (arl_ppo_begin) then fixes, per
+ * sample (t, e), t < t_max:
+ *   lpo = log_probs[t, e, actions[t, e]]      as theta_old left it
+ *   Rf  = (float)R_t                          the learner's n-step return
+ *   adv = f32(Rf - v[t, e])                   at lambda == 1
+ *       = the GAE adv_t                       at lambda != 1 (arl_net_set_gae)
+ * Rf and adv come from the returns launch's own device functions in its order,
+ * so they are bit for bit the values it forms.  A sample with dones bit 1 (past
+ * a truncated window's end) stores 0, 0, 0.
+ *
+ * Loss gradient of an epoch (arl_ppo_learn).  For a live sample take the slot's
+ * current pr[k], lp[k], vi -- the rollout's in epoch 1, those of the last
+ * re-forward (arl_act_mode(net, t, 0)) later -- and ac = actions[t, e], lpo, adv,
+ * Rf from the snapshot.  Every operation round-to-nearest f32 and unfused
+ * unless marked:
+ *   d      = f32(lp[ac] - lpo)
+ *   rho    = (float)exp((double)d)            one float64 exp, one rounding
+ *   lo, hi = (float)(1.0 - clip_eps), (float)(1.0 + clip_eps)     formed on the host
+ *   active = adv >= 0 ? rho <= hi : rho >= lo     (min(rho A, clip(rho) A) has a gradient)
+ *   w      = active ? f32(rho * adv) : 0.0f
+ *   surr   = active ? w : f32((adv >= 0 ? hi : lo) * adv)
+ *   H, t2_k as the returns launch forms them:  H = -sum_k f32(pr[k] * lp[k]) (k ascending),
+ *            t2_k = f32(f32(beta * pr[k]) * f32(lp[k] + H))
+ *   dlogits[k] = f32(pf * f32(f32(-w * f32(oh_k - pr[k])) + t2_k))       oh_k = (k == ac)
+ *   dv         = f32(vf * dvv),  dvv = f32(vi - Rf)
+ *   lpi = f32(pf * f32(surr + f32(beta * H)))
+ *   lv  = f32(vf * f32(f32(dvv * dvv) * 0.5f))
+ * pf, vf = pi_loss_coef, v_loss_coef, times the keep_loss_scale_same segment
+ * factor (arl_net_set_loss); the per-env losses loss[2e] = 0 - lpi_{T-1} - ... -
+ * lpi_0, loss[2e + 1] = 0 + lv_{T-1} + ... + lv_0 as arl_learn sums them.  At
+ * rho == 1 (epoch 1: d == 0 exactly) w == adv, so epoch 1's dlogits and dv are
+ * bit for bit those of arl_learn (n-step or GAE).  ratio[t, e] = rho (0 for a
+ * sample that is not live).  The device's exp and the C library's can differ
+ * in the last float64 bit, so rho is within 1 f32 ulp of a host replay.
+ *
+ * arl_net_set_ppo(net, snap, clip_eps): snap = 4 * t_max * n_envs f32,
+ * caller-owned, 16-byte aligned, planes (t_max, n_envs) in this order: logp_old,
+ * adv, ret, ratio.  NULL switches it off.  Host state of the handle, like
+ * arl_net_set_adam (works on an unbound handle).  clip_eps not finite or outside
+ * (0, 1), a misaligned snap: ARL_EINVAL.  Only FF nets with the NIPS head
+ * (whatever their observation flag); the LSTM and the Nature head: ARL_ESTATE.
+ * While set, the bootstrap arl_act does not fuse the returns
+ * (arl_net_set_returns_fusion is ignored) and arl_run_window returns ARL_ESTATE:
+ * a single-call window has no epochs.
+ *
+ * A window with K epochs:
+ *   observe / act slots 0 .. t_max as always (the bootstrap forward included)
+ *   arl_ppo_begin(net, gamma, clip_reward, stream)        the snapshot, with the net's lambda
+ *   for j = 1 .. K:
+ *     j > 1: arl_act_mode(net, t, 0, stream), t = 0 .. t_max - 1    re-forward from the frame ring;
+ *            mode 0 touches neither actions nor the Philox counters; the bootstrap slot is not
+ *            re-forwarded (ret and adv are fixed)
+ *     arl_ppo_learn(net, beta, v_loss_coef, stream)       loss gradient + heads dh, then
+ *                                                         ARL_LEARN_TRUNK and ARL_LEARN_CONV
+ *     arl_optimize (j < K) / arl_optimize_advance (j == K)
+ * arl_ppo_begin sets the gamma / clip_reward / lambda the window statistics use,
+ * as a returns launch does.  arl_ppo_learn's first launch writes the step
+ * snapshot the update's fused advance reads, as the returns launch it replaces;
+ * it never folds the clip norm (the update runs its own squared-norm launch).
+ * ARL_ESTATE from either on an unbound net or with PPO off, and from
+ * arl_ppo_learn without an arl_ppo_begin since the last window advance.
+ * Window statistics: one record per update, K per window; in epochs >= 2 fields
+ * 5-13 describe the slots' current contents (the re-forwarded v and entropy,
+ * that epoch's losses; returns and advantages recomputed from the current v).
+ * Not built: minibatches within an epoch, advantage normalisation, value
+ * clipping, several ranks. */
+int arl_net_set_ppo(arl_net* net, float* snap, double clip_eps);
+int arl_ppo_begin(arl_net* net, double gamma, int clip_reward, void* stream);
+int arl_ppo_learn(arl_net* net, double beta, double v_loss_coef, void* stream);
+
 /* GradientClipping's squared norm (a3c_ale.py:226) folded into arl_learn:
  * with on != 0, arl_learn's conv slab reduce also leaves the f64 partial
  * sums of squares of the whole gradient (the conv tensors it writes, and the
@@ -766,6 +842,26 @@ int arl_returns_lossgrad_gae(const float* rewards, const uint8_t* dones, const f
                              double gamma, double lambda, double beta, double pi_loss_coef, double v_loss_coef,
                              int keep_loss_scale_same, int clip_reward, float* dlogits, float* dv, float* loss,
                              void* stream);
+
+/* The snapshot of arl_ppo_begin on explicit arrays (arl_net_set_ppo has the
+ * definition): rewards, dones (t_max, n); v (t_max + 1, n), log_probs and
+ * actions (t_max + 1, n[, A]) with row t_max = bootstrap; logp_old, adv, ret
+ * (t_max, n) out.  lambda == 1: the n-step advantage.  t_max <= 256.
+ * Addition to ABI 4. */
+int arl_ppo_snapshot(const float* rewards, const uint8_t* dones, const float* v, const float* log_probs,
+                     const int32_t* actions, int t_max, int64_t n, int n_actions, double gamma, double lambda,
+                     int clip_reward, float* logp_old, float* adv, float* ret, void* stream);
+
+/* The loss gradient of one PPO epoch on explicit arrays (arl_net_set_ppo has
+ * the definition), the counterpart of arl_returns_lossgrad: v, probs,
+ * log_probs, actions as there (the current policy's), logp_old / adv / ret the
+ * snapshot.  loss: (n, 2) or NULL; ratio_out: (t_max, n) or NULL.  clip_eps
+ * not finite or outside (0, 1): ARL_EINVAL.  Addition to ABI 4. */
+int arl_ppo_lossgrad(const uint8_t* dones, const float* v, const float* probs, const float* log_probs,
+                     const int32_t* actions, const float* logp_old, const float* adv, const float* ret, int t_max,
+                     int64_t n, int n_actions, double clip_eps, double beta, double pi_loss_coef, double v_loss_coef,
+                     int keep_loss_scale_same, float* dlogits, float* dv, float* loss, float* ratio_out,
+                     void* stream);
 
 /* ------------------------------------------------------------------ measurement */
 

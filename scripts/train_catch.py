@@ -12,11 +12,12 @@ scores about 0.14 per life.
 
 Defaults are the reference's hyperparameters (RMSpropAsync lr 7e-4, alpha 0.99, eps 0.1, clip 40, beta 0.01,
 gamma 0.99) on the FF model with 256 envs; the batched learner sums the gradient of all envs, so --batch-loss
-mean, --opt adam and --gae-lambda are there to try.  One JSON line at the end (and --out FILE).
+mean, --opt adam, --gae-lambda and --ppo-epochs (clipped-surrogate epochs on each window's rollout, with
+--ppo-clip; each report row then carries A3C.ppo_stats of the last epoch) are there to try.  One JSON line at the end (and --out FILE).
 
     python scripts/train_catch.py [--env catch|breakout] [--windows 4000] [--report 200] [--envs 256] [--seed 0]
                                   [--lr 7e-4] [--opt rmsprop|adam] [--batch-loss sum|mean] [--gae-lambda 1.0]
-                                  [--arch ff|lstm]
+                                  [--arch ff|lstm] [--ppo-epochs 1] [--ppo-clip 0.2]
 """
 import argparse
 import json
@@ -33,7 +34,7 @@ import asyncrl_amd as pkg  # noqa: E402
 
 
 def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", batch_loss="sum", gae_lambda=1.0,
-          arch="ff", beta=1e-2, eps=None, device="cuda:0", log=print, env="catch"):
+          arch="ff", beta=1e-2, eps=None, device="cuda:0", log=print, env="catch", ppo_epochs=1, ppo_clip=0.2):
     """Returns the curve: one dict per report with the window count, the episodes completed since the last
     report and their mean return, and the newest window record's entropy / value / gradient norm."""
     dev = torch.device(device)
@@ -46,7 +47,7 @@ def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", ba
         optimizer = pkg.RMSpropAsync(lr=lr, eps=1e-1 if eps is None else eps, alpha=0.99).setup(model)
     optimizer.add_hook(pkg.GradientClipping(40))
     agent = pkg.A3C(model, optimizer, T, 0.99, beta=beta, batch_loss=batch_loss, gae_lambda=gae_lambda,
-                    collectives=False)
+                    collectives=False, ppo_epochs=ppo_epochs, ppo_clip=ppo_clip)
     net = model.net
     net.set_episode_stats(True)
     net.set_window_stats(True)
@@ -75,10 +76,14 @@ def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", ba
         row = {"windows": done, "episodes": ep["episodes"], "mean_return": ep["mean"], "entropy": ws["entropy"],
                "value_mean": ws["value_mean"], "grad_norm": ws["grad_norm"], "pi_loss": ws["pi_loss"],
                "v_loss": ws["v_loss"], "seconds": time.perf_counter() - t0}
+        if ppo_epochs > 1:
+            row.update(agent.ppo_stats(stream=stream))
         curve.append(row)
         log("windows %6d  episodes %6d  return %+.3f  entropy %.3f  v %+.3f  |g| %9.3f  pi_loss %+10.3f  "
             "v_loss %9.3f  %.1fs" % (done, row["episodes"], row["mean_return"], row["entropy"], row["value_mean"],
-                                     row["grad_norm"], row["pi_loss"], row["v_loss"], row["seconds"]))
+                                     row["grad_norm"], row["pi_loss"], row["v_loss"], row["seconds"])
+            + ("  clip %.3f  kl %+.4f  rho_max %.3f" % (row["clip_fraction"], row["approx_kl"], row["ratio_max"])
+               if ppo_epochs > 1 else ""))
     return curve
 
 
@@ -96,6 +101,8 @@ def main():
     ap.add_argument("--beta", type=float, default=1e-2)
     ap.add_argument("--eps", type=float, default=None)
     ap.add_argument("--arch", choices=("ff", "lstm"), default="ff")
+    ap.add_argument("--ppo-epochs", type=int, default=1)
+    ap.add_argument("--ppo-clip", type=float, default=0.2)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     cfg = {k: v for k, v in vars(a).items() if k != "out"}
