@@ -1,8 +1,8 @@
 """Plain float64 NumPy references of single learner / forward stages, the
 synthetic operands they are tested on, and the launch geometry of the HIP
 kernels that run them (tests/test_stage_ref.py pins all of it on the CPU,
-tests/test_gpu_stages.py compares arl_run_stage with it).  Nothing here
-touches a device.
+tests/test_gpu_stages.py and tests/test_gpu_gemm_stages.py compare
+arl_run_stage with it).  Nothing here touches a device.
 
 Every reduction over the window's S = t_max * n_envs samples is accumulated
 in float64 and rounded to float32 once, as oracle.gmm / oracle.gsum do, and
@@ -148,29 +148,35 @@ def conv_bwd_ref(x, a1, da2, W2, chunk=64):
 class RingX:
     """The conv input of every window sample s = t * n_envs + e, built from the
     frame ring a chunk at a time, as oracle.state_from_ring does with the
-    control block's step at 0 (R = t_max + 4 slots):
-      ring   frames (R, N, 84, 84): plane c = frames[(t - 3 + c) % R, e]
-      stack  frames (R, N, 4, 84, 84): plane c of frames[t % R, e]
-      rgb    frames (R, N, 3, 84, 84): the three planes of frames[t % R, e]
+    control block's step at `start` (R = t_max + 4 slots; k = start + t):
+      ring   frames (R, N, 84, 84): plane c = frames[(k - 3 + c) % R, e]
+      stack  frames (R, N, 4, 84, 84): plane c of frames[k % R, e]
+      rgb    frames (R, N, 3, 84, 84): the three planes of frames[k % R, e]
+      states frames (R, N, 4, 84, 84) float32: frames[k % R, e] as it is (no
+             lut, no nvalid: the ARCH_STATES ring of phi's output)
     through `lut` (O.PHI_LUT; PIXELS: the integer pixel values); ring / stack planes
-    c < 4 - nvalid[t % R, e] are zero.  steps: the window slots covered (t_max;
+    c < 4 - nvalid[k % R, e] are zero.  steps: the window slots covered (t_max;
     t_max + 1 takes in the bootstrap slot)."""
 
-    def __init__(self, frames, nvalid, n_envs, t_max, layout="ring", steps=None, lut=None):
+    def __init__(self, frames, nvalid, n_envs, t_max, layout="ring", steps=None, lut=None, start=0):
         self.frames, self.nvalid, self.N, self.R, self.layout = frames, nvalid, n_envs, t_max + 4, layout
         self.lut = O.PHI_LUT if lut is None else lut
+        self.start = int(start)
         self.shape = ((t_max if steps is None else steps) * n_envs, 3 if layout == "rgb" else 4, 84, 84)
 
     def __getitem__(self, sl):
         s = np.arange(self.shape[0])[sl]
         t, e = s // self.N, s % self.N
+        k = t + self.start % self.R + self.R   # the residue, as Python's % of the whole counter (k - 3 >= 0)
+        if self.layout == "states":
+            return self.frames[k % self.R, e]
         if self.layout == "rgb":
-            return self.lut[self.frames[t % self.R, e]]
+            return self.lut[self.frames[k % self.R, e]]
         if self.layout == "stack":
-            x = self.lut[self.frames[t % self.R, e]]
+            x = self.lut[self.frames[k % self.R, e]]
         else:
-            x = np.stack([self.lut[self.frames[(t - 3 + c) % self.R, e]] for c in range(4)], 1)
-        keep = np.arange(4)[None, :] >= 4 - self.nvalid[t % self.R, e].astype(np.int32)[:, None]
+            x = np.stack([self.lut[self.frames[(k - 3 + c) % self.R, e]] for c in range(4)], 1)
+        keep = np.arange(4)[None, :] >= 4 - self.nvalid[k % self.R, e].astype(np.int32)[:, None]
         return np.where(keep[:, :, None, None], x, F32(0.0))
 
 
@@ -291,14 +297,17 @@ def lstm_bptt_chain_ref(Wl, reset, gates, cbuf, dH):
 
 # ---------------------------------------------------------------- returns
 def returns_heads_ref(rewards, dones, v, probs, logp, actions, Wpi, Wv, hfc=None, gamma=0.99, beta=0.01, vcoef=0.5,
-                      clip_reward=True):
+                      clip_reward=True, lam=1.0):
     """The returns stage (returns_heads_kernel, policy.hip) in float64 from the f32
     buffers: oracle.returns_and_lossgrad's mathematics (R restarted at terminals,
     rewards clipped to +-1) on rewards / dones (T, N), v (T + 1, N) with slot T the
     bootstrap value, probs / logp (T, N, A), actions (T, N); the heads' backward
     dh = dlogits Wpi + dv Wv, and with hfc (T, N, 256) dfc = dh * (hfc > 0).
+    lam != 1: the policy term's advantage is GAE(lambda) (arl_net_set_gae: delta_k =
+    r_k + gamma v_{k+1} - v_k with v_{k+1} = 0 at a terminal, the scan cut there);
+    the value target stays the n-step return.
     Returns dlogits (T, N, A), dv (T, N), loss (N, 2) = per-env (pi, v) losses and
-    dh (or dfc) (T, N, 256)."""
+    dh (or dfc) (T, N, hidden width)."""
     T, N = rewards.shape
     r = np.asarray(rewards, F64)
     if clip_reward:
@@ -309,6 +318,12 @@ def returns_heads_ref(rewards, dones, v, probs, logp, actions, Wpi, Wv, hfc=None
         R = np.where(dones[t] != 0, 0.0, R) * gamma + r[t]
         Rs[t] = R
     adv = Rs - v[:T]
+    if lam != 1.0:
+        G, adv = np.zeros(N), np.empty((T, N))
+        for t in reversed(range(T)):
+            term = dones[t] != 0
+            G = (r[t] + gamma * np.where(term, 0.0, v[t + 1]) - v[t]) + gamma * lam * np.where(term, 0.0, G)
+            adv[t] = G
     H = -(p * lp).sum(-1)
     onehot = np.zeros_like(p)
     np.put_along_axis(onehot, np.asarray(actions, np.int64)[..., None], 1.0, axis=2)
@@ -510,3 +525,270 @@ BPTT_CHAIN_CASES = [(37, 5), (1, 5)]
 # returns (t_max, n_actions, n_envs): one case for each returns_heads_kernel<AM, RB> and row-pass count
 RETURNS_CASES = [(1, 1, 1), (8, 4, 3), (8, 5, 3), (8, 8, 2), (8, 9, 2), (9, 4, 3), (32, 32, 2), (33, 6, 2), (64, 32, 2)]
 RETURNS_LSTM_CASE = (5, 6, 3)
+
+
+# ================================================================ the generic implicit-GEMM paths
+# A3CFFNature (nature.hip) and the f32-state convs of an ARCH_STATES net (states.hip), both on gemm.hpp
+NHID, NC1, NC2, NC3, NP1, NP2, NP3 = 512, 32, 64, 64, 400, 81, 49
+NA1, NA2, NA3 = NC1 * NP1, NC2 * NP2, NC3 * NP3
+NFC_SPLIT = 8
+NATURE_NAMES = {"c1W": "0/0/W", "c1b": "0/0/b", "c2W": "0/1/W", "c2b": "0/1/b", "c3W": "0/2/W", "c3b": "0/2/b",
+                "fcW": "0/3/W", "fcb": "0/3/b", "piW": "1/0/W", "pib": "1/0/b", "vW": "2/0/W", "vb": "2/0/b"}
+
+
+# ---------------------------------------------------------------- launch geometry (gemm.hpp, layers.hpp)
+def ceil_div(a, b):
+    return -(-a // b)
+
+
+def plan_splits(tiles, K, bk=BK, target=1024):
+    """layers.hpp: aim at ~1024 workgroups, each slice >= 4 K chunks."""
+    return min(max(1, target // max(1, tiles)), max(1, ceil_div(K, bk * 4)))
+
+
+def slice_len(K, splits, bk=BK):
+    """launch_gemm's k_per_split: ceil(K / splits) rounded up to whole chunks."""
+    return ceil_div(ceil_div(K, max(1, splits)), bk) * bk
+
+
+def effective_splits(K, splits, bk=BK):
+    """gemm.hpp: the K slices launch_gemm really launches for a requested count."""
+    return ceil_div(K, slice_len(K, splits, bk))
+
+
+def slice_bounds(K, splits):
+    """[k0, k1) of every launched K slice (the last one may be shorter)."""
+    kps = slice_len(K, splits)
+    return [(z * kps, min(K, (z + 1) * kps)) for z in range(ceil_div(K, kps))]
+
+
+def nature_plans(S, A):
+    """nature.hip nature_plans: K slices of the five weight-gradient GEMMs."""
+    K3, K2, K1 = S * NP3, S * NP2, S * NP1
+    return {"heads": effective_splits(S, plan_splits(ceil_div(A + 1, 16) * ceil_div(NHID + 1, 64), S)),
+            "fc": effective_splits(S, plan_splits(ceil_div(NHID, 64) * ceil_div(NA3 + 1, 64), S)),
+            "c3": effective_splits(K3, plan_splits(ceil_div(NC2 * 9 + 1, 64), K3)),
+            "c2": effective_splits(K2, plan_splits(ceil_div(NC1 * 16 + 1, 64), K2)),
+            "c1": effective_splits(K1, plan_splits(ceil_div(4 * 64 + 1, 64), K1))}
+
+
+def states_plans(S):
+    """states.hip states_plans."""
+    K2, K1 = S * 81, S * 400
+    return {"c2": effective_splits(K2, plan_splits(ceil_div(16 * 16 + 1, 64), K2)),
+            "c1": effective_splits(K1, plan_splits(ceil_div(4 * 64 + 1, 64), K1))}
+
+
+def returns_blocks(T, N):
+    """policy.hip returns_kernel (the form launch_returns picks): 256 / T envs a workgroup."""
+    return ceil_div(N, 256 // T)
+
+
+# ---------------------------------------------------------------- references
+def _conv64(x, W, b, s):
+    """conv(x, W, stride s) + b in float64; x float64 or float32."""
+    oc, ic, k, _ = W.shape
+    cols, oh, ow = O._im2col(x, k, s)
+    z = np.asarray(cols.reshape(-1, ic * k * k), F64) @ np.asarray(W, F64).reshape(oc, -1).T + np.asarray(b, F64)
+    return z.reshape(x.shape[0], oh, ow, oc).transpose(0, 3, 1, 2)
+
+
+def nature_fwd_ref(x, p, chunk=64):
+    """The Nature head's forward in float64 from the f32 state x (an array, or RingX)
+    and the parameters p (Chainer names): z1 = conv(x, k8 s4), z2 = conv(a1, k4 s2),
+    z3 = conv(a2, k3 s1), zh = a3 W^T + b, every a = max(z, 0) and each layer from the
+    float64 one before it.  Returns {z1, a1, z2, a2, z3, a3, zh, h}, float64."""
+    S = x.shape[0]
+    z = {"z1": np.empty((S, NC1, 20, 20)), "z2": np.empty((S, NC2, 9, 9)), "z3": np.empty((S, NC3, 7, 7)),
+         "zh": np.empty((S, NHID))}
+    for c0 in range(0, S, chunk):
+        sl = slice(c0, min(S, c0 + chunk))
+        z["z1"][sl] = _conv64(np.ascontiguousarray(x[sl]), p["0/0/W"], p["0/0/b"], 4)
+        z["z2"][sl] = _conv64(np.maximum(z["z1"][sl], 0.0), p["0/1/W"], p["0/1/b"], 2)
+        z["z3"][sl] = _conv64(np.maximum(z["z2"][sl], 0.0), p["0/2/W"], p["0/2/b"], 1)
+        a3 = np.maximum(z["z3"][sl], 0.0).reshape(-1, NA3)
+        z["zh"][sl] = a3 @ np.asarray(p["0/3/W"], F64).T + np.asarray(p["0/3/b"], F64)
+    z.update({"a" + k[1:]: np.maximum(v, 0.0) for k, v in z.items() if k != "zh"})
+    z["h"] = np.maximum(z["zh"], 0.0)
+    return z
+
+
+def policy_ref(h, Wpi, bpi, Wv, bv):
+    """The heads and the softmax in float64: logits, v, probs, logp, entropy."""
+    h = np.asarray(h, F64)
+    logits = h @ np.asarray(Wpi, F64).T + np.asarray(bpi, F64)
+    v = (h @ np.asarray(Wv, F64).T)[:, 0] + F64(np.asarray(bv).reshape(-1)[0])
+    zc = logits - logits.max(-1, keepdims=True)
+    logp = zc - np.log(np.exp(zc).sum(-1, keepdims=True))
+    probs = np.exp(logp)
+    return {"logits": logits, "v": v, "probs": probs, "logp": logp, "entropy": -(probs * logp).sum(-1)}
+
+
+def conv_transpose_ref(dy, W, stride):
+    """The transposed convolution (a conv's backward to its input) in float64:
+    dx[s, ic, stride oy + ky, stride ox + kx] += dy[s, oc, oy, ox] W[oc, ic, ky, kx]."""
+    oc, ic, k, _ = W.shape
+    n, _, oh, ow = dy.shape
+    gcol = (np.asarray(dy, F64).transpose(0, 2, 3, 1).reshape(-1, oc) @ np.asarray(W, F64).reshape(oc, -1))
+    gcol = gcol.reshape(n, oh, ow, ic, k, k)
+    gx = np.zeros((n, ic, stride * (oh - 1) + k, stride * (ow - 1) + k))
+    for ky in range(k):
+        for kx in range(k):
+            gx[:, :, ky:ky + stride * oh:stride, kx:kx + stride * ow:stride] += gcol[..., ky, kx].transpose(0, 3, 1, 2)
+    return gx
+
+
+def nature_fc_bwd_ref(dfc, a3, W):
+    """The Nature fc_bwd stage: gW = dfc^T a3, gb = sum_s dfc, da3 = (dfc W) * (a3 > 0);
+    a3 (S, 3136).  Returns (g, mag), float32."""
+    g = {"fcW": mm64(dfc.T, a3), "fcb": dfc.sum(0, dtype=F64), "da3": mm64(dfc, W) * (a3 > 0)}
+    mag = {"fcW": O._mag_mm(dfc.T, a3), "fcb": O._mag_sum(dfc)}
+    return {k: v.astype(F32) for k, v in g.items()}, mag
+
+
+def nature_conv_bwd_ref(x, a1, a2, da3, W3, W2, chunk=64):
+    """The Nature conv_bwd stage: gW3, gb3 of conv3 (64 -> 64, k3 s1) from da3 and a2,
+    da2 = convT(da3, W3) * (a2 > 0); gW2, gb2 of conv2 (32 -> 64, k4 s2) from da2 and
+    a1, da1 = convT(da2, W2) * (a1 > 0); gW1, gb1 of conv1 (4 -> 32, k8 s4) from da1 and
+    x (an array, or RingX).  da2 and da1 are formed in float64 and rounded to float32
+    once, the values the next reduction is fed (as the device feeds its own); the six
+    sums are accumulated in float64 over chunks of <= chunk samples.  Returns (g,
+    mag) float32 and da2, da1 float64."""
+    S = x.shape[0]
+    shp = {"c3": (NC3, NC2, 3, 3), "c2": (NC2, NC1, 4, 4), "c1": (NC1, 4, 8, 8)}
+    gW = {k: np.zeros((s[0], s[1] * s[2] * s[3])) for k, s in shp.items()}
+    gb = {k: np.zeros(s[0]) for k, s in shp.items()}
+    m = {k: _Mag(*v.shape) for k, v in gW.items()}
+    da2, da1 = np.empty((S, NC2, 9, 9)), np.empty((S, NC1, 20, 20))
+
+    def wgrad(key, dy, xin, k, s):
+        oc = dy.shape[1]
+        cols = O._im2col(xin, k, s)[0].reshape(-1, gW[key].shape[1])
+        gy = dy.transpose(0, 2, 3, 1).reshape(-1, oc)
+        a64, b64 = np.asarray(gy.T, F64), np.asarray(cols, F64)
+        gW[key] += a64 @ b64
+        gb[key] += gy.sum(0, dtype=F64)
+        m[key].add(a64, b64)
+
+    for c0 in range(0, S, chunk):
+        sl = slice(c0, min(S, c0 + chunk))
+        d3, a2s, a1s = np.asarray(da3[sl], F32), np.asarray(a2[sl], F32), np.asarray(a1[sl], F32)
+        wgrad("c3", d3, a2s, 3, 1)
+        da2[sl] = conv_transpose_ref(d3, W3, 1) * (a2s > 0)
+        d2 = da2[sl].astype(F32)
+        wgrad("c2", d2, a1s, 4, 2)
+        da1[sl] = conv_transpose_ref(d2, W2, 2) * (a1s > 0)
+        wgrad("c1", da1[sl].astype(F32), np.ascontiguousarray(x[sl]), 8, 4)
+    g, mag = {}, {}
+    for k, s in shp.items():
+        P = {"c3": NP3, "c2": NP2, "c1": NP1}[k]
+        g[k + "W"], g[k + "b"] = gW[k].reshape(s).astype(F32), gb[k].astype(F32)
+        mag[k + "W"], mag[k + "b"] = m[k].mm().reshape(s), np.full(s[0], m[k].X * np.sqrt(S * float(P)))
+    return g, mag, da2, da1
+
+
+def nature_heads_ref(rewards, dones, v, probs, logp, actions, Wpi, Wv, hfc, **kw):
+    """returns_heads_ref at the heads' hidden width (512 on the Nature head) plus the
+    heads' weight gradients with their bias, as the heads GEMM of nature_learn forms
+    them from the f32 dlogits / dv: gpiW = dlogits^T h, gpib = sum_s dlogits, gvW =
+    dv^T h, gvb = sum_s dv; hfc (T, N, H).  Returns {dlogits, dv, loss, dfc} float64
+    and (g, mag) float32."""
+    dl, dv, loss, dfc = returns_heads_ref(rewards, dones, v, probs, logp, actions, Wpi, Wv, hfc, **kw)
+    S = dv.size
+    dl32, dvc, hh = dl.reshape(S, -1).astype(F32), dv.reshape(S, 1).astype(F32), np.asarray(hfc).reshape(S, -1)
+    g = {"piW": mm64(dl32.T, hh), "pib": dl32.sum(0, dtype=F64), "vW": mm64(dvc.T, hh), "vb": dvc.sum(0, dtype=F64)}
+    mag = {"piW": O._mag_mm(dl32.T, hh), "pib": O._mag_sum(dl32), "vW": O._mag_mm(dvc.T, hh), "vb": O._mag_sum(dvc)}
+    return {"dlogits": dl, "dv": dv, "loss": loss, "dfc": dfc}, {k: x.astype(F32) for k, x in g.items()}, mag
+
+
+def nature_learn_ref(d, lam=1.0):
+    """The whole of nature_learn on the operands of nature_data, chained: the heads
+    (nature_heads_ref), the FC (nature_fc_bwd_ref on the f32 dfc) and the convs
+    (nature_conv_bwd_ref on the f32 da3).  Returns (outs, g, mag): outs {dlogits, dv,
+    loss, dfc} float64, the 12 gradient tensors and their scales."""
+    T, S, p = d["T"], d["S"], d["p"]
+    outs, g, mag = nature_heads_ref(d["rewards"], d["dones"], d["v"], d["probs"], d["logp"], d["actions"], p["1/0/W"],
+                                    p["2/0/W"], d["hfc"][:T], lam=lam)
+    a3 = d["a3"][:T].reshape(S, NA3)
+    gf, mf = nature_fc_bwd_ref(outs["dfc"].reshape(S, NHID).astype(F32), a3, p["0/3/W"])
+    da3 = gf.pop("da3").reshape(S, NC3, 7, 7)
+    gc, mc, _, _ = nature_conv_bwd_ref(d["x"], d["a1"][:T].reshape(S, NC1, 20, 20), d["a2"][:T].reshape(S, NC2, 9, 9), da3,
+                                       p["0/2/W"], p["0/1/W"])
+    g.update(gf), g.update(gc), mag.update(mf), mag.update(mc)
+    return outs, g, mag
+
+
+# ---------------------------------------------------------------- data recipes
+def ring_nvalid(rng, R, N, T):
+    """nvalid as conv_data draws it: 1..4 per (slot, env), env 0 masked at slot 0 and at
+    the bootstrap slot."""
+    nvalid = rng.integers(1, 5, (R, N)).astype(np.uint8)
+    nvalid[0, 0], nvalid[T, 0] = 2, 3
+    return nvalid
+
+
+def rolled(ring, start, R):
+    """The ring array holding at slot (start + k) % R what `ring` holds at slot k: the
+    same window under a step counter of `start`."""
+    return np.roll(ring, start % R, axis=0)
+
+
+def ring_starts(T):
+    """The step counters of the ring-residue cases: R - 1, 2^32 - 3 and the first multiple of T above 2^40."""
+    return [T + 3, 2 ** 32 - 3, (2 ** 40 // T + 1) * T]
+
+
+def nature_data(n_envs, t_max, n_actions, seed=0):
+    """Operands of every Nature stage and of nature_learn, at a step counter of 0:
+    parameters as init_like_torch, frames / nvalid as conv_data (x: the window's T
+    steps, x_fwd: with the bootstrap slot), post-ReLU a1 / a2 / a3 / hfc with the
+    bootstrap slot a sentinel, da3, fresh_dfc(k), and the returns launch's inputs
+    (returns_data's rewards, dones, v, probs, logp, actions)."""
+    rng = np.random.default_rng([seed, n_envs, t_max, n_actions, 10])
+    N, T, A, S, R = n_envs, t_max, n_actions, n_envs * t_max, t_max + 4
+    d = {"N": N, "T": T, "A": A, "S": S, "R": R, "p": O.init_like_torch(O.ARCH_FF_NATURE, A, rng)}
+    d["frames"] = rng.integers(0, 256, (R, N, 84, 84), dtype=np.uint8)
+    d["nvalid"] = ring_nvalid(rng, R, N, T)
+    d["x"] = RingX(d["frames"], d["nvalid"], N, T)
+    d["x_fwd"] = RingX(d["frames"], d["nvalid"], N, T, steps=T + 1)
+    for name, shape in (("a1", (NC1, 20, 20)), ("a2", (NC2, 9, 9)), ("a3", (NA3,)), ("hfc", (NHID,))):
+        a = act_like(rng, (T + 1, N) + shape)
+        a[T] = SENTINEL
+        d[name] = a
+    d["da3"] = grad_like(rng, (S, NC3, 7, 7))
+    d["fresh_dfc"] = lambda k: grad_like(np.random.default_rng([seed, n_envs, t_max, n_actions, 11, k]), (S, NHID))
+    r = returns_data(T, A, N, seed=seed)
+    d.update({k: r[k] for k in ("rewards", "dones", "v", "probs", "logp", "actions")})
+    return d
+
+
+def states_data(n_envs, t_max, seed=0):
+    """Operands of the two conv stages of an ARCH_STATES net at a step counter of 0:
+    a (R, N, 4, 84, 84) ring of signed normal states (no image of uint8 frames) with
+    the three slots past the bootstrap slot sentinels, the convs' weights and biases,
+    a1 with the bootstrap slot a sentinel, da2; x: the window's T steps, x_fwd: with
+    the bootstrap slot."""
+    rng = np.random.default_rng([seed, n_envs, t_max, 12])
+    N, T, S, R = n_envs, t_max, n_envs * t_max, t_max + 4
+    frames = rng.standard_normal((R, N, 4, 84, 84), F32)
+    frames[T + 1:] = SENTINEL
+    a1 = act_like(rng, (T + 1, N, 16, 20, 20))
+    a1[T] = SENTINEL
+    d = {"N": N, "T": T, "S": S, "R": R, "frames": frames, "a1": a1, "da2": grad_like(rng, (S, 32, 9, 9)),
+         "W1": weight_like(rng, (16, 4, 8, 8)), "W2": weight_like(rng, (32, 16, 4, 4))}
+    d["b1"], d["b2"] = rng.uniform(-1 / 16, 1 / 16, 16).astype(F32), rng.uniform(-1 / 16, 1 / 16, 32).astype(F32)
+    d["x"] = RingX(frames, None, N, T, "states")
+    d["x_fwd"] = RingX(frames, None, N, T, "states", steps=T + 1)
+    return d
+
+
+# the cases of tests/test_gpu_gemm_stages.py; tests/test_stage_ref.py pins their launch geometry and runs the
+# sensitivity checks on the same data
+NATURE_CASES = [(1, 1, 4), (33, 5, 18), (67, 2, 6)]    # (n_envs, t_max, n_actions)
+NATURE_HEADS_CASE = (41, 9, 4)                         # the heads and fc_bwd only
+NATURE_LEARN_CASES = [(33, 5, 18), NATURE_HEADS_CASE]
+NATURE_RING_CASE = (33, 5, 18)
+STATES_CASES = [(1, 1), (33, 5)]                       # (n_envs, t_max)
+STATES_RING_CASE = (33, 5)
+GAE_LAMBDAS = (1.0, 0.95)
+TIE_SHARE_MAX = 1e-3                                   # of a tensor's elements the tie band may exempt

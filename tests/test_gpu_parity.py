@@ -388,6 +388,14 @@ def test_nature_head_windows_match_oracle(gpu):
     _run_ff(gpu, N=4, T=3, A=6, seed=41, kind="palette", arch=O.ARCH_FF_NATURE, p_done=0.2)
 
 
+def test_nature_head_ragged_window(gpu):
+    """The Nature head's forward -> learn -> clip -> RMSProp chain over two windows at
+    33 envs x 5 steps, 18 actions: S = 165 is odd and past 128, so the heads' and the
+    FC's weight gradients run in two K slices, the convs' in 64 / 105 / 188 with a
+    shorter last one, the heads GEMM has two M tiles and every M edge is ragged."""
+    _run_ff(gpu, N=33, T=5, A=18, seed=42, kind="palette", arch=O.ARCH_FF_NATURE, p_done=0.2, windows=2)
+
+
 @pytest.mark.parametrize("hw", [(120, 160), (240, 320)])
 def test_doom_ff_windows_match_oracle(gpu, hw):
     """train_a3c_doom.py:25-38 A3CFF on RGB screens (two doom_env.py

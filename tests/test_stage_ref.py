@@ -1,6 +1,8 @@
 """CPU tests of tests/stage_ref.py: the stage references against the oracle,
 the launch geometry restated from the .hip sources, and the sensitivity of
 the GPU stage tests' tolerance to the mistakes they exist to catch."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -411,3 +413,425 @@ def test_returns_tolerance_catches_mistakes(t_max, n_actions, n_envs, lstm):
         f = _worst(pert, ref)
         print(f"returns T={T} A={A} N={n_envs} {what}: {f:.3g} x the bound")
         assert f >= 10, (what, f)
+
+
+# ================================================================ the generic implicit-GEMM paths (Nature head, f32 states)
+NAT = R.NATURE_NAMES
+
+
+@functools.lru_cache(maxsize=None)
+def _nature_case(case):
+    return R.nature_data(*case)
+
+
+@functools.lru_cache(maxsize=None)
+def _nature_conv_bwd_case(case):
+    d = _nature_case(case)
+    T, S = d["T"], d["S"]
+    return R.nature_conv_bwd_ref(d["x"], d["a1"][:T].reshape(S, R.NC1, 20, 20), d["a2"][:T].reshape(S, R.NC2, 9, 9),
+                                 d["da3"], d["p"]["0/2/W"], d["p"]["0/1/W"])
+
+
+@functools.lru_cache(maxsize=None)
+def _states_case(case):
+    return R.states_data(*case)
+
+
+def test_nature_refs_equal_oracle_backward():
+    """S = 7: the Nature references, fed the oracle's own intermediates, against
+    oracle.ff_backward(arch=ARCH_FF_NATURE): the heads', the FC's and conv3's
+    gradients bit for bit (both round one float64 sum of the same f32 operands);
+    conv2's and conv1's within 1e-6 of the scale (the oracle forms da2 / da1 in
+    float32, the reference in float64), as da3 / da2 / da1 / dfc themselves."""
+    d = R.conv_data(7, 1, seed=3)
+    x = d["x"][:]
+    rng = np.random.default_rng(3)
+    A = 5
+    p = O.init_like_torch(O.ARCH_FF_NATURE, A, rng)
+    acts = O.nature_head(p, x)
+    a1, a2, a3, h = acts
+    r = R.returns_data(1, A, 7, seed=3)
+    outs, gh, mh = R.nature_heads_ref(r["rewards"], r["dones"], r["v"], r["probs"], r["logp"], r["actions"], p["1/0/W"],
+                                      p["2/0/W"], h[None])
+    dl, dv = outs["dlogits"].reshape(7, A).astype(np.float32), outs["dv"].reshape(7).astype(np.float32)
+    mag_o = {}
+    g_o = O.ff_backward(p, x, acts, dl, dv, arch=O.ARCH_FF_NATURE, mag=mag_o)
+    heads = {k: NAT[k] for k in ("piW", "pib", "vW", "vb")}
+    _equal(gh, g_o, heads)
+    for k, name in heads.items():
+        assert np.allclose(mh[k], mag_o[name], rtol=1e-12, atol=0), k
+    dfc_o = (dl @ p["1/0/W"] + dv[:, None] * p["2/0/W"]).astype(np.float32) * (h > 0)
+    ok, err = close_normscaled(outs["dfc"].reshape(7, -1), dfc_o, 1e-6)
+    assert ok, err
+    a3f = a3.reshape(7, -1)
+    gf, mf = R.nature_fc_bwd_ref(dfc_o, a3f, p["0/3/W"])
+    _equal(gf, g_o, {"fcW": NAT["fcW"], "fcb": NAT["fcb"]})
+    assert np.allclose(mf["fcW"], O._mag_mm(dfc_o.T, a3f), rtol=1e-12) and np.allclose(mf["fcb"], O._mag_sum(dfc_o))
+    da3_o = ((dfc_o @ p["0/3/W"]).reshape(a3.shape) * (a3 > 0)).astype(np.float32)   # oracle._nature_backward
+    ok, err = close_normscaled(gf["da3"], da3_o.reshape(7, -1), 1e-6)
+    assert ok, err
+    assert (gf["da3"][a3f <= 0] == 0).all()
+    gc, mc, da2, da1 = R.nature_conv_bwd_ref(x, a1, a2, da3_o, p["0/2/W"], p["0/1/W"])
+    _equal(gc, g_o, {"c3W": NAT["c3W"], "c3b": NAT["c3b"]})
+    _, _, da2_o = O.conv2d_backward(a2, p["0/2/W"], da3_o, 1)
+    da2_o = (da2_o * (a2 > 0)).astype(np.float32)
+    _, _, da1_o = O.conv2d_backward(a1, p["0/1/W"], da2_o, 2)
+    da1_o = (da1_o * (a1 > 0)).astype(np.float32)
+    for got, want, what in ((da2, da2_o, "da2"), (da1, da1_o, "da1")) + tuple(
+            (gc[k], g_o[NAT[k]], k) for k in ("c2W", "c2b", "c1W", "c1b")):
+        ok, err = close_normscaled(got, want, 1e-6)
+        print(f"nature_conv_bwd_ref {what}: {err:.3g} of the scale from the oracle")
+        assert ok and got.shape == want.shape, (what, err)
+    assert (da2[a2 <= 0] == 0).all() and (da1[a1 <= 0] == 0).all()
+    # the error scales: oracle._mag_mm / _mag_sum of the same operands
+    gy3 = da3_o.transpose(0, 2, 3, 1).reshape(-1, 64)
+    cols3 = O._im2col(a2, 3, 1)[0].reshape(-1, 576)
+    assert np.allclose(mc["c3W"].reshape(64, 576), O._mag_mm(gy3.T, cols3), rtol=1e-12)
+    assert np.allclose(mc["c3b"], O._mag_sum(gy3), rtol=1e-12)
+    # chunks of 3, 3, 1 samples: the same sums to float64 rounding
+    g3, m3, _, _ = R.nature_conv_bwd_ref(x, a1, a2, da3_o, p["0/2/W"], p["0/1/W"], chunk=3)
+    for k in gc:
+        assert np.allclose(g3[k], gc[k], rtol=1e-6, atol=1e-12) and np.allclose(m3[k], mc[k], rtol=1e-12), k
+
+
+def test_nature_fwd_ref_equals_oracle_head():
+    """N = 7 ring states with masked planes: nature_fwd_ref against oracle.nature_head's
+    f32 activations within 1e-6 of the scale; a = max(z, 0); policy_ref against the
+    oracle's heads and softmax."""
+    d = R.conv_data(7, 1, seed=2)
+    p = O.init_like_torch(O.ARCH_FF_NATURE, 6, np.random.default_rng(2))
+    want = dict(zip(("a1", "a2", "a3", "h"), O.nature_head(p, d["x"][:])))
+    got = R.nature_fwd_ref(d["x"], p, chunk=3)
+    for k, w in want.items():
+        ok, err = close_normscaled(got[k].reshape(w.shape), w, 1e-6)
+        print(f"nature_fwd_ref {k}: {err:.3g} of the scale from oracle.nature_head")
+        assert ok and got[k].dtype == np.float64, (k, err)
+        z = got["z" + k[1:]] if k != "h" else got["zh"]
+        assert np.array_equal(got[k], np.maximum(z, 0)) and (z < 0).any()
+    lo, vo, _ = O.pi_and_v_ff(p, d["x"][:], O.ARCH_FF_NATURE)
+    pol = R.policy_ref(want["h"], p["1/0/W"], p["1/0/b"], p["2/0/W"], p["2/0/b"])
+    lp = O.log_softmax(lo)
+    for k, w in (("logits", lo), ("v", vo), ("probs", O.softmax(lo)), ("logp", lp),
+                 ("entropy", O.entropy(O.softmax(lo), lp))):
+        ok, err = close_normscaled(pol[k], w, 1e-6)
+        assert ok, (k, err)
+
+
+def test_returns_heads_ref_gae_equals_the_replay():
+    """returns_heads_ref(lam=0.95) against tests/gae_replay.py (the device's own order of
+    operations) within 1e-6 of the scale; lam = 1 is the n-step form unchanged."""
+    from gae_replay import returns_and_lossgrad_gae
+    d = R.returns_data(9, 4, 5)
+    T = d["T"]
+    args = (d["rewards"], d["dones"], d["v"], d["probs"], d["logp"], d["actions"], d["Wpi"], d["Wv"], d["hfc"][:T])
+    dl, dv, loss, _ = R.returns_heads_ref(*args, lam=0.95)
+    _, _, dl_o, dv_o, pil, vl = returns_and_lossgrad_gae(d["rewards"], d["dones"], d["v"][:T], d["v"][T], d["probs"],
+                                                         d["logp"], d["actions"], lam=0.95, per_env=True)
+    for got, want in ((dl, dl_o), (dv, dv_o), (loss[:, 0], pil), (loss[:, 1], vl)):
+        ok, err = close_normscaled(got, want, 1e-6)
+        assert ok, err
+    assert not close_normscaled(dl, R.returns_heads_ref(*args)[0], 1e-3)[0]
+
+
+def test_ring_x_start_and_states_layout():
+    """RingX(start=k0) is oracle.state_from_ring at the slots (k0 + t - 3 + c) % R; rolled()
+    moves a window to where another counter finds it; the states layout returns the f32
+    ring slot (k0 + t) % R as it is."""
+    d = R.conv_data(3, 5, seed=1)
+    Rr, base = d["R"], d["x"][:]
+    for k0 in [4] + R.ring_starts(5):
+        fr, nv = R.rolled(d["frames"], k0, Rr), R.rolled(d["nvalid"], k0, Rr)
+        x = R.RingX(fr, nv, 3, 5, start=k0)
+        for t in range(5):
+            want = O.state_from_ring(fr, nv[(k0 + t) % Rr], [(k0 + t - 3 + c) % Rr for c in range(4)])
+            assert np.array_equal(x[3 * t:3 * t + 3], want), (k0, t)
+        assert np.array_equal(x[:], base)
+        assert k0 % Rr == 0 or not np.array_equal(R.RingX(fr, nv, 3, 5)[:], base)
+    s = _states_case((1, 1))
+    k0 = 2 ** 32 - 3
+    x = R.RingX(R.rolled(s["frames"], k0, 5), None, 1, 1, "states", steps=2, start=k0)
+    assert x.shape == (2, 4, 84, 84) and np.array_equal(x[:], s["frames"][:2, 0]) and (s["frames"][2:] == R.SENTINEL).all()
+    assert np.array_equal(R.RingX(s["frames"], None, 1, 1, "states", steps=2)[1:2], s["frames"][1])
+
+
+# ------------------------------------------------------------------ launch geometry of the GPU cases
+def test_gemm_launch_geometry():
+    """plan_splits / effective_splits / nature_plans / states_plans restated from
+    layers.hpp, gemm.hpp, nature.hip and states.hip: the slice and tile counts each case of
+    tests/test_gpu_gemm_stages.py exists for."""
+    plans = {c: R.nature_plans(c[0] * c[1], c[2]) for c in R.NATURE_CASES + [R.NATURE_HEADS_CASE]}
+    assert plans[(33, 5, 18)] == {"heads": 2, "fc": 2, "c3": 64, "c2": 105, "c1": 188}
+    assert plans[(1, 1, 4)] == {"heads": 1, "fc": 1, "c3": 1, "c2": 1, "c1": 4}
+    assert plans[(67, 2, 6)] == {"heads": 2, "fc": 2, "c3": 52, "c2": 85, "c1": 187}
+    assert plans[(41, 9, 4)]["heads"] == 3 and plans[(41, 9, 4)]["fc"] == 2
+    assert R.states_plans(165) == {"c2": 105, "c1": 188} and R.states_plans(1) == {"c2": 1, "c1": 4}
+    # the first S with two and three slices of the heads / FC weight gradients
+    assert [R.nature_plans(S, 6)["heads"] for S in (12, 128, 129, 256, 257)] == [1, 1, 2, 2, 3]
+    assert [R.nature_plans(S, 6)["fc"] for S in (12, 128, 129, 257)] == [1, 1, 2, 2]
+    # (33, 5, 18), S = 165: shorter last slices, none a whole number of chunks, conv3's and conv2's no multiple of 4
+    assert R.slice_bounds(165, 2) == [(0, 96), (96, 165)]
+    assert R.slice_bounds(165 * 49, 64)[-1] == (8064, 8085) and R.slice_bounds(165 * 81, 105)[-1] == (13312, 13365)
+    assert R.slice_bounds(165 * 400, 188)[-1] == (65824, 66000)
+    assert 165 % 4 and (165 * 49) % 4 and (165 * 81) % 4 and 21 % 4 and 53 % 4 and 69 % 32 and 176 % 32
+    # slice counts the reduce's 4 slice groups do not divide: 2 (heads, FC), 105 (conv2), 85 and 187 at (67, 2, 6)
+    assert 2 % 4 and 105 % 4 and 85 % 4 and 187 % 4 and 3 % 4
+    assert R.slice_bounds(369, 3) == [(0, 128), (128, 256), (256, 369)] and R.slice_bounds(369, 2)[-1] == (192, 369)
+    # tiles: the heads GEMM's M (A + 1 rows in tiles of 16), the FC forward's M (envs in tiles of 64), ragged edges
+    assert R.ceil_div(18 + 1, 16) == 2 and R.ceil_div(4 + 1, 16) == 1 and R.ceil_div(R.NHID + 1, 64) == 9
+    assert R.ceil_div(67, 64) == 2 and 67 % 64 == 3 and R.ceil_div(33, 64) == 1
+    assert 165 % 64 == 37 and (165 * 81) % 64 == 53 and (165 * 49) % 64 == 21 and (165 * 100) % 64 == 52
+    assert (R.NA3 + 1) % 4 == 1 and (R.NHID + 1) % 4 == 1 and 257 % 4 == 1 and 577 % 64 == 1 and 513 % 64 == 1
+    # the FC forward: K = 3136 in 8 slices of 416, the last 224
+    assert R.slice_bounds(R.NA3, R.NFC_SPLIT)[-1] == (2912, 3136) and R.effective_splits(R.NA3, R.NFC_SPLIT) == 8
+    # returns_kernel: 256 / T envs a workgroup; T <= 8 scans registers
+    assert R.returns_blocks(5, 33) == 1 and R.returns_blocks(9, 41) == 2 and 256 // 9 == 28
+    for T in (5,):
+        assert all(s % (T + 4) for s in R.ring_starts(T)) and R.ring_starts(T)[0] == T + 3
+        assert R.ring_starts(T)[2] > 2 ** 40 and R.ring_starts(T)[2] % T == 0
+
+
+# ------------------------------------------------------------------ tie-band shares of the conv_fwd cases
+@pytest.mark.parametrize("case", R.NATURE_CASES)
+def test_nature_conv_fwd_tie_share_and_sensitivity(case):
+    """On the data of every Nature conv_fwd case (slot 0 and the bootstrap slot): the tie
+    band exempts at most 0.1 % of a1, a2 and a3; mistakes (g) nvalid ignored and (h) the
+    ring slot taken from t % R under another step counter miss the 1e-5 bound by >= 10x."""
+    d = _nature_case(case)
+    N, T = d["N"], d["T"]
+    x = np.concatenate([d["x_fwd"][:N], d["x_fwd"][T * N:(T + 1) * N]])
+    ref = R.nature_fwd_ref(x, d["p"])
+    for k in ("1", "2", "3"):
+        share = max(R.tie_band(ref["z" + k][sl]).mean() for sl in (slice(0, N), slice(N, 2 * N)))
+        print(f"nature conv_fwd {case}: tie share of a{k} {share:.2g}")
+        assert share <= R.TIE_SHARE_MAX, (k, share)
+    want = [ref[k] for k in ("a1", "a2", "a3")]
+
+    def run(xs):
+        out = R.nature_fwd_ref(xs, d["p"])
+        return [out[k] for k in ("a1", "a2", "a3")]
+
+    all4 = R.RingX(d["frames"], np.full_like(d["nvalid"], 4), N, T, steps=T + 1)
+    mistakes = [("(g) nvalid ignored", run(np.concatenate([all4[:N], all4[T * N:(T + 1) * N]])))]
+    if case == R.NATURE_RING_CASE:
+        for start in R.ring_starts(T):
+            xw = R.RingX(R.rolled(d["frames"], start, d["R"]), R.rolled(d["nvalid"], start, d["R"]), N, T, steps=T + 1)
+            mistakes.append((f"(h) slot t % R at step {start}", run(np.concatenate([xw[:N], xw[T * N:(T + 1) * N]]))))
+    for what, pert in mistakes:
+        f = _worst(pert, want)
+        print(f"nature conv_fwd {case} {what}: {f:.3g} x the bound")
+        assert f >= 10, (what, f)
+
+
+@pytest.mark.parametrize("case", R.STATES_CASES)
+def test_states_conv_fwd_tie_share_and_sensitivity(case):
+    d = _states_case(case)
+    N, T = d["N"], d["T"]
+    W = (d["W1"], d["b1"], d["W2"], d["b2"])
+    x = np.concatenate([d["x_fwd"][:N], d["x_fwd"][T * N:(T + 1) * N]])
+    a1, a2, z1, z2 = R.conv_fwd_ref(x, *W)
+    for z, k in ((z1, "a1"), (z2, "a2")):
+        share = max(R.tie_band(z[sl]).mean() for sl in (slice(0, N), slice(N, 2 * N)))
+        print(f"states conv_fwd {case}: tie share of {k} {share:.2g}")
+        assert share <= R.TIE_SHARE_MAX, (k, share)
+    assert (x < 0).any() and not np.isin(x[0, 0, 0, :8], O.PHI_LUT).any()
+    if case == R.STATES_RING_CASE:
+        for start in R.ring_starts(T):
+            xw = R.RingX(R.rolled(d["frames"], start, d["R"]), None, N, T, "states", steps=T + 1)
+            f = _worst(R.conv_fwd_ref(np.concatenate([xw[:N], xw[T * N:(T + 1) * N]]), *W)[:2], (a1, a2))
+            print(f"states conv_fwd {case} (h) slot t % R at step {start}: {f:.3g} x the bound")
+            assert f >= 10, (start, f)
+
+
+# ------------------------------------------------------------------ sensitivity of the backward cases
+def _tail(dy, xin, k, s, k0=0):
+    """The contribution of the flattened (sample, position) rows [k0, K) to a conv's weight
+    and bias gradient (float64): dy (S, OC, OH, OH) f32, xin the conv's input."""
+    P = dy.shape[2] * dy.shape[3]
+    s0 = k0 // P
+    cols = O._im2col(np.ascontiguousarray(xin[s0:]), k, s)[0]
+    cols = cols.reshape(-1, cols.shape[-1])
+    gy = dy[s0:].transpose(0, 2, 3, 1).reshape(-1, dy.shape[1])
+    off = k0 - s0 * P
+    return R.mm64(gy[off:].T, cols[off:]), gy[off:].sum(0, dtype=np.float64)
+
+
+def _k_mistakes(K, Z, part, ref, keys):
+    """(a) the last of Z K slices dropped, (e) the last K % 4 elements of K dropped; part(k0)
+    -> (dW, db) of the rows [k0, K)."""
+    out = []
+    if Z > 1:
+        out.append(("(a) last K slice dropped", R.slice_bounds(K, Z)[-1][0]))
+    if K % 4:
+        out.append(("(e) last K % 4 elements dropped", K - K % 4))
+    for what, k0 in out:
+        dW, db = part(k0)
+        yield f"{what} ({keys[0]})", {keys[0]: ref[keys[0]] - dW.reshape(ref[keys[0]].shape), keys[1]: ref[keys[1]] - db}
+
+
+def _convt1_gather(dy, W, wrap=False):
+    """convT(dy, W) of conv3 (k3 s1, 7 x 7 -> 9 x 9) as ConvT1A gathers it: out[y, x] = sum
+    dy[y - ky, x - kx] W[ky, kx] with the taps outside the 7 x 7 grid zero.  wrap: mistake (d),
+    the tap at ox = -1 not zeroed -- it reads the flat neighbour, the last column of the row
+    above."""
+    S, OC = dy.shape[:2]
+    pad = np.zeros((S, OC, 11, 11))
+    pad[:, :, 2:9, 2:9] = dy
+    if wrap:
+        pad[:, :, 3:9, 1] = dy[:, :, 0:6, 6]
+    out = np.zeros((S, W.shape[1], 9, 9))
+    for ky in range(3):
+        for kx in range(3):
+            out += np.einsum("sohw,oi->sihw", pad[:, :, 2 - ky:11 - ky, 2 - kx:11 - kx],
+                             np.asarray(W[:, :, ky, kx], np.float64))
+    return out
+
+
+def _convt2_wrong_class(dy, W2):
+    """Mistake (c): the output parity class (1, 1) of the stride-2 transposed conv computed
+    with the taps of class (0, 0) (ky, kx in {0, 2} for {1, 3})."""
+    good = R.conv_transpose_ref(dy, W2, 2)
+    good[:, :, 1::2, 1::2] = R.conv_transpose_ref(dy, np.roll(W2, (1, 1), (2, 3)), 2)[:, :, 1::2, 1::2]
+    return good
+
+
+@pytest.mark.parametrize("case", R.NATURE_CASES)
+def test_nature_conv_bwd_tolerance_catches_gemm_mistakes(case):
+    d = _nature_case(case)
+    N, T, S, p = d["N"], d["T"], d["S"], d["p"]
+    ref, mag, da2, da1 = _nature_conv_bwd_case(case)
+    plans = R.nature_plans(S, d["A"])
+    a1, a2 = d["a1"][:T].reshape(S, R.NC1, 20, 20), d["a2"][:T].reshape(S, R.NC2, 9, 9)
+    da3, d2, d1 = d["da3"], da2.astype(np.float32), da1.astype(np.float32)
+    ops = {"c3": (da3, a2, 3, 1, R.NP3), "c2": (d2, a1, 4, 2, R.NP2), "c1": (d1, d["x"], 8, 4, R.NP1)}
+    mistakes = []
+    for key, (dy, xin, k, s, P) in ops.items():
+        mistakes += list(_k_mistakes(S * P, plans[key], lambda k0: _tail(dy, xin, k, s, k0), ref, (key + "W", key + "b")))
+    if S > 1:   # (b) the ones column of conv3's OnesCol<Im2col> reads k = 576: channel 0 of the next sample
+        nxt = d["a2"].reshape(-1, R.NC2, 9, 9)[1:S + 1, 0, :7, :7]
+        mistakes.append(("(b) ones column reads the operand (c3b)",
+                         {"c3b": np.einsum("sohw,shw->o", da3.astype(np.float64), nxt)}))
+    all4 = R.RingX(d["frames"], np.full_like(d["nvalid"], 4), N, T)
+    gW, gb = _tail(d1, all4, 8, 4)
+    mistakes.append(("(g) nvalid ignored", {"c1W": gW.reshape(ref["c1W"].shape), "c1b": gb}))
+    if case == R.NATURE_RING_CASE:
+        for start in R.ring_starts(T):
+            xw = R.RingX(R.rolled(d["frames"], start, d["R"]), R.rolled(d["nvalid"], start, d["R"]), N, T)
+            mistakes.append((f"(h) slot t % R at step {start}", {"c1W": _tail(d1, xw, 8, 4)[0].reshape(ref["c1W"].shape)}))
+    for what, pert in mistakes:
+        f = _excess(pert, ref, mag)
+        print(f"nature conv_bwd {case} {what}: {f:.3g} x the bound")
+        assert f >= 10, (what, f)
+    # the non-reduced outputs
+    m2, m1 = a2 > 0, a1 > 0
+    good = _convt1_gather(da3, p["0/2/W"]) * m2
+    assert close_normscaled(good, da2, 1e-12)[0]
+    plain = [("(c) class (1, 1) with class (0, 0)'s taps", _convt2_wrong_class(d2, p["0/1/W"]) * m1, da1),
+             ("(d) boundary tap not zeroed", _convt1_gather(da3, p["0/2/W"], wrap=True) * m2, da2)]
+    if (S * R.NP2) % 64:   # (f): da2 is (s, ic, p), the GEMM's rows are (s, p)
+        t = da2.transpose(0, 2, 3, 1).reshape(S * R.NP2, R.NC2).copy()
+        t[(S * R.NP2) // 64 * 64:] = 0
+        plain.append(("(f) last partial M tile dropped (da2)", t.reshape(S, 9, 9, R.NC2).transpose(0, 3, 1, 2), da2))
+    for what, pert, want in plain:
+        f = _worst([pert], [want])
+        print(f"nature conv_bwd {case} {what}: {f:.3g} x the bound")
+        assert f >= 10, (what, f)
+
+
+@pytest.mark.parametrize("case", R.NATURE_CASES + [R.NATURE_HEADS_CASE])
+def test_nature_fc_bwd_tolerance_catches_gemm_mistakes(case):
+    d = _nature_case(case)
+    T, S = d["T"], d["S"]
+    dfc, a3 = d["fresh_dfc"](0), d["a3"][:T].reshape(S, R.NA3)
+    ref, mag = R.nature_fc_bwd_ref(dfc, a3, d["p"]["0/3/W"])
+    mistakes = list(_k_mistakes(S, R.nature_plans(S, d["A"])["fc"],
+                                lambda k0: (R.mm64(dfc[k0:].T, a3[k0:]), dfc[k0:].sum(0, dtype=np.float64)), ref,
+                                ("fcW", "fcb")))
+    nxt = d["a3"].reshape(-1, R.NA3)[1:S + 1, 0]   # OnesColB at j = K: the next sample's first element
+    mistakes.append(("(b) ones column reads the operand", {"fcb": R.mm64(dfc.T, nxt)}))
+    mistakes.append(("(e) the last N % 4 columns (the bias column) dropped", {"fcb": np.zeros(R.NHID)}))
+    for what, pert in mistakes:
+        f = _excess(pert, ref, mag)
+        print(f"nature fc_bwd {case} {what}: {f:.3g} x the bound")
+        assert f >= 10, (what, f)
+    if S % 64:
+        pert = ref["da3"].copy()
+        pert[S // 64 * 64:] = 0
+        f = _worst([pert], [ref["da3"]])
+        print(f"nature fc_bwd {case} (f) last partial M tile dropped (da3): {f:.3g} x the bound")
+        assert f >= 10, f
+
+
+@pytest.mark.parametrize("lam", R.GAE_LAMBDAS)
+@pytest.mark.parametrize("case", R.NATURE_LEARN_CASES)
+def test_nature_heads_tolerance_catches_gemm_mistakes(case, lam):
+    d = _nature_case(case)
+    T, S, A, p = d["T"], d["S"], d["A"], d["p"]
+    args = (d["rewards"], d["dones"], d["v"], d["probs"], d["logp"], d["actions"], p["1/0/W"], p["2/0/W"], d["hfc"][:T])
+    outs, ref, mag = R.nature_heads_ref(*args, lam=lam)
+    dl, dv = outs["dlogits"].reshape(S, A).astype(np.float32), outs["dv"].reshape(S, 1).astype(np.float32)
+    hh = d["hfc"][:T].reshape(S, R.NHID)
+
+    def part(k0):
+        return {"piW": R.mm64(dl[k0:].T, hh[k0:]), "pib": dl[k0:].sum(0, dtype=np.float64),
+                "vW": R.mm64(dv[k0:].T, hh[k0:]), "vb": dv[k0:].sum(0, dtype=np.float64)}
+
+    mistakes = []
+    Z = R.nature_plans(S, A)["heads"]
+    assert Z > 1 and S % 4
+    for what, k0 in (("(a) last K slice dropped", R.slice_bounds(S, Z)[-1][0]),
+                     ("(e) last K % 4 samples dropped", S - S % 4)):
+        mistakes.append((what, {k: ref[k] - v for k, v in part(k0).items()}))
+    nxt = d["hfc"].reshape(-1, R.NHID)[1:S + 1, 0]
+    mistakes.append(("(b) ones column reads the operand", {"pib": R.mm64(dl.T, nxt), "vb": R.mm64(dv.T, nxt)}))
+    if (A + 1) % 16 and A + 1 > 16:   # rows 16 .. A of the (A + 1)-row GEMM: the last policy rows and the value row
+        w = ref["piW"].copy()
+        w[16:] = 0
+        mistakes.append(("(f) last partial M tile dropped", {"piW": w, "vW": np.zeros_like(ref["vW"])}))
+    w, b = ref["piW"].copy(), ref["pib"].copy()
+    w[A - 1], b[A - 1] = ref["vW"][0], ref["vb"][0]
+    mistakes.append(("(i) the value row written into the policy rows", {"piW": w, "pib": b}))
+    for what, pert in mistakes:
+        f = _excess(pert, ref, mag)
+        print(f"nature heads {case} lambda={lam} {what}: {f:.3g} x the bound")
+        assert f >= 10, (what, f)
+    other = R.returns_heads_ref(*args, lam=1.0 if lam != 1.0 else 0.95)
+    f = _worst([other[0], other[3]], [outs["dlogits"], outs["dfc"]])
+    print(f"nature heads {case} lambda={lam} the other lambda's advantage: {f:.3g} x the bound")
+    assert f >= 10, f
+
+
+@pytest.mark.parametrize("case", R.STATES_CASES)
+def test_states_conv_bwd_tolerance_catches_gemm_mistakes(case):
+    d = _states_case(case)
+    N, T, S = d["N"], d["T"], d["S"]
+    a1, da2, W2 = d["a1"][:T].reshape(S, 16, 20, 20), d["da2"], d["W2"]
+    ref, mag = R.conv_bwd_ref(d["x"], a1, da2, W2)
+    da1 = R.conv_transpose_ref(da2, W2, 2) * (a1 > 0)
+    d1 = da1.astype(np.float32)
+    plans = R.states_plans(S)
+    mistakes = list(_k_mistakes(S * 81, plans["c2"], lambda k0: _tail(da2, a1, 4, 2, k0), ref, ("c2W", "c2b")))
+    mistakes += list(_k_mistakes(S * 400, plans["c1"], lambda k0: _tail(d1, d["x"], 8, 4, k0), ref, ("c1W", "c1b")))
+    if case == R.STATES_RING_CASE:
+        fr = d["frames"].copy()
+        fr[T] = R.SENTINEL
+        for start in R.ring_starts(T):
+            xw = R.RingX(R.rolled(fr, start, d["R"]), None, N, T, "states")
+            mistakes.append((f"(h) slot t % R at step {start}", {"c1W": _tail(d1, xw, 8, 4)[0].reshape(ref["c1W"].shape)}))
+    for what, pert in mistakes:
+        f = _excess(pert, ref, mag)
+        print(f"states conv_bwd {case} {what}: {f:.3g} x the bound")
+        assert f >= 10, (what, f)
+    f = _worst([_convt2_wrong_class(da2, W2) * (a1 > 0)], [da1])
+    print(f"states conv_bwd {case} (c) class (1, 1) with class (0, 0)'s taps: {f:.3g} x the bound")
+    assert f >= 10, f
+
+
+def test_fc_fwd_second_m_tile_sensitivity():
+    """(f) on the FC forward at 67 envs: the 3 rows of the second 64-row tile dropped."""
+    N = 67
+    p = _nature_case((67, 2, 6))["p"]
+    a3 = R.act_like(np.random.default_rng([7, N, 0]), (N, R.NA3))
+    h = np.maximum(R.mm64(a3, p["0/3/W"].T) + p["0/3/b"], 0.0)
+    pert = h.copy()
+    pert[64:] = 0
+    assert (h[64:] > 0).any() and _worst([pert], [h]) >= 10
