@@ -6,7 +6,7 @@ from .a3c import A3C, A3CFF, A3CFFNature, A3CLSTM, A3CModel, DoomA3CFF, DoomA3CL
 from .envs import DeviceBreakout, DeviceCatch  # noqa: F401
 from .evaluation import eval_performance, run_episodes  # noqa: F401
 from .dqn_phi import current_screen, dqn_phi, max_luminance, phi_stack, rgb_phi  # noqa: F401
-from .net import DeviceNet, init_like_torch, param_shapes, window_stats_dict  # noqa: F401
+from .net import DeviceNet, init_like_torch, param_shapes, ppo_epoch_stats_dict, window_stats_dict  # noqa: F401
 from .policy_output import SoftmaxPolicyOutput, fc_softmax_policy_and_v  # noqa: F401
 from .rmsprop_async import GradientClipping, NonbiasWeightDecay, RMSpropAsync  # noqa: F401
 from .adam import Adam  # noqa: F401

@@ -72,6 +72,14 @@ SIGNATURES = {
     "arl_ppo_lossgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_int, c_i64, c_int, c_double, c_double, c_double, c_double, c_int, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "arl_net_set_ppo_options": (c_int, [c_void_p, c_int, c_double, c_void_p, c_void_p]),
+    "arl_ppo_lossgrad_vclip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_int, c_i64, c_int, c_double, c_double, c_double, c_double,
+                                       c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "arl_ppo_normalize_adv": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_void_p, c_void_p]),
+    "arl_ppo_epoch_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_int, c_i64, c_int, c_double, c_double, c_double, c_double, c_void_p,
+                                    c_void_p]),
     "arl_net_set_adam": (c_int, [c_void_p, c_void_p, c_double, c_double]),
     "arl_net_set_adam_t": (c_int, [c_void_p, c_i64, c_void_p]),
     "arl_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_double, c_double, c_double, c_double, c_i64,
@@ -167,6 +175,12 @@ WINDOW_STAT_FIELDS = 17   # ARL_WINDOW_STAT_FIELDS: doubles per record, named in
 WINDOW_STAT_NAMES = ("window", "step", "samples", "terminals", "reward_sum", "pi_loss", "v_loss", "entropy_sum",
                      "value_sum", "value_sumsq", "return_sum", "return_sumsq", "adv_sum", "adv_sumsq", "grad_sqnorm",
                      "clip_scale", "lr")
+PPO_LOG = 16              # ARL_PPO_LOG: epoch records the aux block of arl_net_set_ppo_options keeps
+PPO_STAT_FIELDS = 10      # ARL_PPO_STAT_FIELDS: doubles per epoch record, named in order:
+PPO_STAT_NAMES = ("window", "epoch", "samples", "clipped", "kl_sum", "ratio_max", "ratio_min", "vclipped", "adv_sum",
+                  "adv_sumsq")
+PPO_AUX_HEAD = 8          # doubles before the records: the int64 count, n_live, mean, std, 4 reserved
+PPO_AUX_DOUBLES = PPO_AUX_HEAD + PPO_LOG * PPO_STAT_FIELDS   # ARL_PPO_AUX_DOUBLES
 # window timeline stages (arl_stamps_*): arl_run_stage's 1..11, then the stamp-only ones
 STAGE_NAMES = {1: "conv_fwd", 2: "fc_fwd", 3: "policy", 4: "fc_bwd", 5: "conv_bwd", 6: "returns", 7: "conv_reduce",
                8: "grad_sqnorm", 9: "lstm_gates", 10: "lstm_bptt", 11: "lstm_wgrad", 12: "phi", 13: "rmsprop",

@@ -49,7 +49,7 @@ from ._lib import (ACT_AFTER_CONV, ACT_CONV_ONLY, ARCH_FF, ARCH_FF_NATURE, ARCH_
 from .dqn_phi import dqn_phi as _device_dqn_phi
 from .distributed import (allreduce_grads, dist_initialized, gather_episode_stats, gather_window_stats,
                           merge_episode_stats, merge_window_stats, world_info)
-from .net import DeviceNet, episode_stats_dict, init_like_torch, window_stats_dict
+from .net import DeviceNet, episode_stats_dict, init_like_torch, ppo_epoch_stats_dict, window_stats_dict
 from . import serializers
 from .policy_output import SoftmaxPolicyOutput
 
@@ -211,8 +211,14 @@ class A3C:
                  process_idx: int = 0, clip_reward: bool = True, phi=None, pi_loss_coef: float = 1.0,
                  v_loss_coef: float = 0.5, keep_loss_scale_same: bool = False, resize_mode: int = RESIZE_SCALAR,
                  process_group=None, batch_loss: str = "sum", collectives: bool | None = None,
-                 gae_lambda: float = 1.0, ppo_epochs: int = 1, ppo_clip: float = 0.2):
-        """ppo_epochs: K >= 2 makes every window's update K clipped-surrogate
+                 gae_lambda: float = 1.0, ppo_epochs: int = 1, ppo_clip: float = 0.2, ppo_norm_adv: bool = False,
+                 ppo_vclip: float | None = None):
+        """ppo_norm_adv / ppo_vclip: options of the PPO epochs, off by default
+        (DeviceNet.set_ppo_options): normalise each window's advantages over
+        its live samples; clip the value loss within ppo_vclip of the rollout's
+        values.  Either also keeps a device-side record per epoch
+        (ppo_epoch_stats).  They need ppo_epochs >= 2.
+        ppo_epochs: K >= 2 makes every window's update K clipped-surrogate
         (PPO) epochs on the window's rollout (an extension; DeviceNet.set_ppo,
         DESIGN.md "PPO epochs"): K gradient steps, the slots re-forwarded from
         the frame ring before epochs 2..K; ppo_clip is the ratio's clip range.
@@ -236,6 +242,10 @@ class A3C:
             raise ValueError("ppo_clip must be in (0, 1)")
         if ppo_epochs > 1 and collectives:
             raise ValueError("A3C: ppo_epochs > 1 runs on one rank (collectives=False)")
+        if ppo_vclip is not None and not 0.0 < float(ppo_vclip) < float("inf"):   # (nan fails both)
+            raise ValueError("ppo_vclip must be finite and > 0 (None: off)")
+        if ppo_epochs == 1 and (ppo_norm_adv or ppo_vclip is not None):
+            raise ValueError("ppo_norm_adv / ppo_vclip need ppo_epochs >= 2")
         if model.net.t_max != t_max:
             raise ValueError("model was built for a different t_max")
         if batch_loss not in ("sum", "mean"):
@@ -278,6 +288,10 @@ class A3C:
             if self.collectives:
                 raise ValueError("A3C: ppo_epochs > 1 runs on one rank (collectives=False)")
             self.net.set_ppo(self.ppo_clip)   # (refuses the LSTM and the Nature head)
+        self.ppo_norm_adv = bool(ppo_norm_adv)
+        self.ppo_vclip = None if ppo_vclip is None else float(ppo_vclip)
+        if self.ppo_norm_adv or self.ppo_vclip is not None:   # (the default never touches set_ppo_options)
+            self.net.set_ppo_options(self.ppo_norm_adv, self.ppo_vclip)
         # no all-reduce between learn and update: the clip norm comes from the learner's conv reduce
         self.net.set_norm_fold(not self.collectives)
         self.t = 0          # env-steps taken (per env)
@@ -408,6 +422,15 @@ class A3C:
             kl = -(torch.log(rho.double().clamp(min=1e-45)) * live).sum() / n
             out = torch.stack([cut.sum().to(torch.float64) / n, kl, rho.max().to(torch.float64)]).cpu()
         return {"clip_fraction": float(out[0]), "approx_kl": float(out[1]), "ratio_max": float(out[2])}
+
+    def ppo_epoch_stats(self, last: int = 1, stream=None) -> list:
+        """The newest `last` per-epoch records of the device-side log
+        (ppo_norm_adv or ppo_vclip on; at most PPO_LOG), oldest first, as
+        dicts (ppo_epoch_stats_dict): one copy to the host, no host work per
+        epoch, and a replayed window writes them like an eager one."""
+        if not (self.ppo_norm_adv or self.ppo_vclip is not None):
+            raise ValueError("ppo_epoch_stats: neither ppo_norm_adv nor ppo_vclip is on")
+        return [ppo_epoch_stats_dict(r) for r in self.net.ppo_epoch_log(last, stream)]
 
     # ------------------------------------------------------------ reference-contract act
     def act(self, state, reward=None, is_state_terminal=None):

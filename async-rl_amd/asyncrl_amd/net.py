@@ -18,8 +18,8 @@ import torch
 
 from ._lib import (ARCH_FF, ARCH_FF_NATURE, ARCH_LSTM, ARCH_RGB, ARCH_STACK, ARCH_STATES, CTL_ADAM_T, ENV_CATCH,
                    ENV_GROUP_ALIGN, EPISODE_LOG, EPISODE_STAT_FIELDS, FWD_KEEP_STATE, POOL_DONES, POOL_FRAMES, POOL_REWARDS,
-                   RESIZE_SCALAR, STAGE_HOST, STAGE_NAMES, WINDOW_LOG, WINDOW_STAT_FIELDS, WINDOW_STAT_NAMES, check,
-                   lib, ptr, stream_handle)
+                   PPO_AUX_DOUBLES, PPO_AUX_HEAD, PPO_LOG, PPO_STAT_FIELDS, PPO_STAT_NAMES, RESIZE_SCALAR, STAGE_HOST, STAGE_NAMES,
+                   WINDOW_LOG, WINDOW_STAT_FIELDS, WINDOW_STAT_NAMES, check, lib, ptr, stream_handle)
 
 
 def param_shapes(arch: int, n_actions: int):
@@ -127,6 +127,25 @@ def window_stats_dict(row) -> dict:
     d["clipped"] = d["clip_scale"] < 1
     d["total_loss"] = d["pi_loss"] + d["v_loss"]
     return d
+
+
+def ppo_epoch_stats_dict(row) -> dict:
+    """One per-epoch record of the PPO options' log (PPO_STAT_NAMES order) as
+    the dict A3C.ppo_epoch_stats returns: window, epoch, samples as int,
+    ratio_max / ratio_min as stored, and from the sums clip_fraction,
+    approx_kl = kl_sum / samples, vclip_fraction, adv_mean and adv_std (the
+    population form; nan without a sample)."""
+    if len(row) != PPO_STAT_FIELDS:
+        raise ValueError(f"ppo_epoch_stats_dict: need {PPO_STAT_FIELDS} values")
+    r = {k: float(x) for k, x in zip(PPO_STAT_NAMES, row)}
+    n = int(r["samples"])
+    nan = float("nan")
+    mean = r["adv_sum"] / n if n else nan
+    return {"window": int(r["window"]), "epoch": int(r["epoch"]), "samples": n,
+            "clip_fraction": r["clipped"] / n if n else nan, "approx_kl": r["kl_sum"] / n if n else nan,
+            "ratio_max": r["ratio_max"], "ratio_min": r["ratio_min"],
+            "vclip_fraction": r["vclipped"] / n if n else nan, "adv_mean": mean,
+            "adv_std": math.sqrt(max(r["adv_sumsq"] / n - mean * mean, 0.0)) if n else nan}
 
 
 class DeviceNet:
@@ -371,6 +390,52 @@ class DeviceNet:
         if self.ppo_snap is None:
             raise RuntimeError("ppo_planes: PPO was never set (set_ppo)")
         return dict(zip(("logp_old", "adv", "ret", "ratio"), self.ppo_snap))
+
+    ppo_v_old = None   # (t_max, n_envs) f32: the rollout's values, allocated by the first set_ppo_options(vclip=)
+    ppo_aux = None     # PPO_AUX_DOUBLES f64: count, moments, epoch records; allocated by the first option set
+    ppo_options = (False, None)   # (norm_adv, vclip) as last set
+
+    def set_ppo_options(self, norm_adv: bool = False, vclip: float | None = None):
+        """Options of the PPO epochs (arl_net_set_ppo_options): norm_adv
+        normalises the snapshot's advantages over the window's live samples,
+        vclip = eps clips the value loss around the rollout's values; either
+        also switches the device-side per-epoch record on (ppo_epoch_log).
+        The defaults switch all of it off: the launches of a net that never
+        called this.  A captured window keeps what it was captured with."""
+        if vclip is not None and not (0.0 < float(vclip) < float("inf")):   # (nan fails)
+            raise ValueError("set_ppo_options: vclip must be finite and > 0 (None: off)")
+        if not norm_adv and vclip is None:
+            check(lib.arl_net_set_ppo_options(self._h, 0, 0.0, None, None), "arl_net_set_ppo_options")
+            self.ppo_options = (False, None)
+            return
+        if vclip is not None and self.ppo_v_old is None:
+            self.ppo_v_old = torch.zeros((self.t_max, self.n_envs), dtype=torch.float32, device=self.device)
+        if self.ppo_aux is None:
+            self.ppo_aux = torch.zeros(PPO_AUX_DOUBLES, dtype=torch.float64, device=self.device)
+        check(lib.arl_net_set_ppo_options(self._h, int(bool(norm_adv)), 0.0 if vclip is None else float(vclip),
+                                          ptr(self.ppo_v_old) if vclip is not None else None, ptr(self.ppo_aux)),
+              "arl_net_set_ppo_options")
+        self.ppo_options = (bool(norm_adv), None if vclip is None else float(vclip))
+
+    def ppo_aux_raw(self, stream=None):
+        """The aux block as the kernels left it: one copy to the host ->
+        (count of epoch records ever written, (n_live, mean, std) of the last
+        normalisation, the (PPO_LOG, PPO_STAT_FIELDS) f64 ring of records)."""
+        if self.ppo_aux is None:
+            raise RuntimeError("ppo_aux_raw: no PPO option was ever set (set_ppo_options)")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(s):
+            a = self.ppo_aux.cpu()
+        count = int(a[:1].view(torch.int64)[0])
+        return count, a[1:4].tolist(), a[PPO_AUX_HEAD:].reshape(PPO_LOG, PPO_STAT_FIELDS).numpy()
+
+    def ppo_epoch_log(self, last: int = 1, stream=None) -> list:
+        """The newest `last` epoch records (at most PPO_LOG, and no more than
+        were written), oldest first, each PPO_STAT_FIELDS floats
+        (PPO_STAT_NAMES)."""
+        count, _, ring = self.ppo_aux_raw(stream)
+        k = max(0, min(int(last), count, PPO_LOG))
+        return [ring[r % PPO_LOG].tolist() for r in range(count - k, count)]
 
     # ------------------------------------------------------------ Adam
     adam_m = None    # Adam's first moment (flat f32, the params' layout), allocated by the first set_adam

@@ -477,6 +477,26 @@ int arl_net_set_ppo(arl_net* h, float* snap, double clip_eps) {
   return ARL_OK;
 }
 
+static bool vclip_ok(double e) { return e >= 0.0 && e <= 1.7976931348623157e308; }   // finite, >= 0 (nan fails both)
+
+int arl_net_set_ppo_options(arl_net* h, int norm_adv, double vclip_eps, float* v_old, double* aux) {
+  if (!h) return fail(ARL_EINVAL, "null net");
+  arl::Net& n = h->net;
+  if (!vclip_ok(vclip_eps)) return fail(ARL_EINVAL, "set_ppo_options: vclip_eps must be finite and >= 0");
+  if (vclip_eps > 0.0 && !v_old) return fail(ARL_EINVAL, "set_ppo_options: value clipping needs v_old");
+  if (norm_adv && !aux) return fail(ARL_EINVAL, "set_ppo_options: advantage normalisation needs aux");
+  if (!aligned(v_old, 16) || !aligned(aux, 8))
+    return fail(ARL_EINVAL, "set_ppo_options: v_old must be 16-byte and aux 8-byte aligned");
+  const bool on = norm_adv || vclip_eps > 0.0 || aux;
+  if (on && n.arch != arl::ARCH_FF)
+    return fail(ARL_ESTATE, "set_ppo_options: FF nets with the NIPS head only (not the LSTM, not the Nature head)");
+  n.ppo_norm_adv = norm_adv != 0;
+  n.ppo_vold = vclip_eps > 0.0 ? v_old : nullptr;
+  n.ppo_ev = (float)vclip_eps;
+  n.ppo_aux = aux;
+  return ARL_OK;
+}
+
 int arl_ppo_begin(arl_net* h, double gamma, int clip_reward, void* s) {
   NEED_BOUND(h);
   if (!h->net.ppo_snap) return fail(ARL_ESTATE, "ppo_begin: PPO is off (arl_net_set_ppo)");
@@ -989,6 +1009,55 @@ int arl_ppo_lossgrad(const uint8_t* dones, const float* v, const float* probs, c
                            (float)(1.0 + clip_eps), (float)beta, (float)vcoef, (float)pi_loss_coef,
                            keep_loss_scale_same ? 1 : 0, dlogits, dv, loss, ratio_out};
   return hip_status(arl::launch_ppo_lossgrad(p, S(s)), "ppo_lossgrad");
+}
+
+int arl_ppo_lossgrad_vclip(const uint8_t* dones, const float* v, const float* probs, const float* logp,
+                           const int32_t* act, const float* logp_old, const float* adv, const float* ret,
+                           const float* v_old, int T, int64_t n, int A, double clip_eps, double vclip_eps, double beta,
+                           double pi_loss_coef, double vcoef, int keep_loss_scale_same, float* dlogits, float* dv,
+                           float* loss, float* ratio_out, void* s) {
+  if (T < 1 || T > 256 || n < 0 || n > INT32_MAX / 256 || A < 1 || A > arl::MAXA)
+    return fail(ARL_EINVAL, "ppo_lossgrad_vclip: bad T / n / A");
+  if (n > 0 && (!dones || !v || !probs || !logp || !act || !logp_old || !adv || !ret || !v_old || !dlogits || !dv))
+    return fail(ARL_EINVAL, "ppo_lossgrad_vclip: null pointer");
+  if (!(clip_eps > 0.0 && clip_eps < 1.0))
+    return fail(ARL_EINVAL, "ppo_lossgrad_vclip: clip_eps must be finite and in (0, 1)");
+  if (!(vclip_ok(vclip_eps) && vclip_eps > 0.0))
+    return fail(ARL_EINVAL, "ppo_lossgrad_vclip: vclip_eps must be finite and > 0");
+  arl::PpoLossArgs p{dones, v, probs, logp, act, logp_old, adv, ret, T, (int)n, A, (float)(1.0 - clip_eps),
+                     (float)(1.0 + clip_eps), (float)beta, (float)vcoef, (float)pi_loss_coef,
+                     keep_loss_scale_same ? 1 : 0, dlogits, dv, loss, ratio_out};
+  p.vold = v_old;
+  p.ev = (float)vclip_eps;
+  return hip_status(arl::launch_ppo_lossgrad(p, S(s)), "ppo_lossgrad_vclip");
+}
+
+int arl_ppo_normalize_adv(const uint8_t* dones, float* adv, int T, int64_t n, double* moments3_device, void* s) {
+  if (T < 1 || T > 256 || n < 0 || n > INT32_MAX / 256) return fail(ARL_EINVAL, "ppo_normalize_adv: bad T / n");
+  if (n > 0 && (!dones || !adv || !moments3_device)) return fail(ARL_EINVAL, "ppo_normalize_adv: null pointer");
+  if (!aligned(moments3_device, 8)) return fail(ARL_EINVAL, "ppo_normalize_adv: moments must be 8-byte aligned");
+  return hip_status(arl::launch_ppo_normalize_adv(dones, adv, T, (int)n, moments3_device, S(s)), "ppo_normalize_adv");
+}
+
+int arl_ppo_epoch_stats(const uint8_t* dones, const float* v, const float* logp, const int32_t* act,
+                        const float* logp_old, const float* adv, const float* ret, const float* ratio,
+                        const float* v_old, int T, int64_t n, int A, double clip_eps, double vclip_eps, double window,
+                        double epoch, double* record10_device, void* s) {
+  if (T < 1 || T > 256 || n < 0 || n > INT32_MAX / 256 || A < 1 || A > arl::MAXA)
+    return fail(ARL_EINVAL, "ppo_epoch_stats: bad T / n / A");
+  if (n > 0 && (!dones || !v || !logp || !act || !logp_old || !adv || !ret || !ratio || !record10_device))
+    return fail(ARL_EINVAL, "ppo_epoch_stats: null pointer");
+  if (!(clip_eps > 0.0 && clip_eps < 1.0))
+    return fail(ARL_EINVAL, "ppo_epoch_stats: clip_eps must be finite and in (0, 1)");
+  if (!vclip_ok(vclip_eps) || (v_old && !(vclip_eps > 0.0)))
+    return fail(ARL_EINVAL, "ppo_epoch_stats: vclip_eps must be finite and >= 0, > 0 with v_old");
+  if (!aligned(record10_device, 8)) return fail(ARL_EINVAL, "ppo_epoch_stats: the record must be 8-byte aligned");
+  arl::PpoLossArgs p{dones, v, nullptr, logp, act, logp_old, adv, ret, T, (int)n, A, (float)(1.0 - clip_eps),
+                     (float)(1.0 + clip_eps), 0.f, 0.f, 0.f, 0, nullptr, nullptr, nullptr, const_cast<float*>(ratio)};
+  p.vold = v_old;
+  p.ev = (float)vclip_eps;
+  return hip_status(arl::launch_ppo_epoch_stats(p, nullptr, window, epoch, nullptr, record10_device, S(s)),
+                    "ppo_epoch_stats");
 }
 
 int arl_stream_copy(const void* src, void* dst, int64_t bytes, int blocks, int mode, void* s) {

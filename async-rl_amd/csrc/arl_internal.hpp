@@ -275,7 +275,16 @@ struct Net {
   float* ppo_snap = nullptr;
   float ppo_lo = 0.8f, ppo_hi = 1.2f;
   bool ppo_begun = false;
-  int hid;                // width of the layer the heads read (256 NIPS / LSTM, 512 Nature)
+  // arl_net_set_ppo_options, read when arl_ppo_begin / arl_ppo_learn launch: ppo_norm_adv = normalise the
+  // snapshot's advantages; ppo_vold non-null = value clipping within ppo_ev = (float)vclip_eps of it (T * N f32);
+  // ppo_aux non-null = the moments and the per-epoch records (ARL_PPO_AUX_DOUBLES f64); ppo_epoch = epochs
+  // launched since the last arl_ppo_begin (the record's 1-based epoch)
+  bool ppo_norm_adv = false;
+  float* ppo_vold = nullptr;
+  float ppo_ev = 0.f;
+  double* ppo_aux = nullptr;
+  int ppo_epoch = 0;
+  int hid;               // width of the layer the heads read (256 NIPS / LSTM, 512 Nature)
   int env_offset;          // global id of env 0 on this rank (RNG stream)
   uint64_t seed;
   std::vector<ParamInfo> params;
@@ -634,10 +643,26 @@ struct PpoLossArgs {
   float beta, vcoef, pcoef;
   int keep_scale;
   float *dlogits, *dv, *loss, *ratio;   // loss, ratio: nullable
+  // value clipping (arl_net_set_ppo_options): vold non-null picks the value-clipped form of the two launchers
+  // below, ev = (float)vclip_eps
+  const float* vold = nullptr;
+  float ev = 0.f;
 };
 hipError_t launch_ppo_lossgrad(const PpoLossArgs& p, hipStream_t s);
 hipError_t launch_ppo_heads(const PpoLossArgs& p, int64_t* ctl_snap, const float* Wpi, const float* Wv,
                             const float* mask, float* dh, hipStream_t s);
+// The PPO options' own launches (arl_net_set_ppo_options has the definitions; policy.hip).
+// launch_ppo_vold: vold[t, e] = v[t, e] of a live sample, else 0.  launch_ppo_normalize_adv: the adv plane in
+// place, moments = (n_live, mean, std); one workgroup.  launch_ppo_epoch_stats: one epoch's record from the
+// arrays of p (dlogits / dv / loss and the coefficients are not read, ratio is); ctl non-null: the window
+// counter is read there instead of `window`; count non-null: rec is the aux block, the record goes to its ring
+// and the count is advanced, else rec is the record; one workgroup.
+constexpr int PPO_LOG = ARL_PPO_LOG, PPO_STAT_FIELDS = ARL_PPO_STAT_FIELDS, PPO_AUX_HEAD = 8;
+static_assert(PPO_AUX_HEAD + PPO_LOG * PPO_STAT_FIELDS == ARL_PPO_AUX_DOUBLES, "aux layout");
+hipError_t launch_ppo_vold(const uint8_t* dones, const float* v, float* vold, int T, int n, hipStream_t s);
+hipError_t launch_ppo_normalize_adv(const uint8_t* dones, float* adv, int T, int n, double* moments, hipStream_t s);
+hipError_t launch_ppo_epoch_stats(const PpoLossArgs& p, const int64_t* ctl, double window, double epoch, int64_t* count,
+                                  double* rec, hipStream_t s);
 // launch_policy_fc of the bootstrap slot (no draw) + launch_returns_heads for the same n envs, one launch
 // (policy.hip policy_fc_returns_kernel; v(s_T) handed over in LDS); bit-identical to the two launches
 hipError_t launch_policy_fc_returns(const float* slab, int n, const float* fc_bias, float* hfc, const PolicyArgs& pa,

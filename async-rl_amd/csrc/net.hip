@@ -541,7 +541,19 @@ hipError_t net_ppo_begin(Net& net, double gamma, int clip_reward, hipStream_t s)
                               net.at<float>(net.w_logp), net.at<int32_t>(net.w_act), net.T, net.N, net.A, gamma,
                               net.gae_lambda, clip_reward, snap, snap + S, snap + 2 * S, s));
   net.ppo_begun = true;
-  return stamp(net, STAGE_OTHER, s);
+  net.ppo_epoch = 0;
+  ARL_TRY(stamp(net, STAGE_OTHER, s));
+  // arl_net_set_ppo_options: v_old of the window, then the adv plane normalised in place (each with a stamp
+  // of its own; with the options off nothing more is launched)
+  if (net.ppo_vold != nullptr) {
+    ARL_TRY(launch_ppo_vold(net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v), net.ppo_vold, net.T, net.N, s));
+    ARL_TRY(stamp(net, STAGE_OTHER, s));
+  }
+  if (net.ppo_norm_adv) {
+    ARL_TRY(launch_ppo_normalize_adv(net.at<uint8_t>(net.w_dones), snap + S, net.T, net.N, net.ppo_aux + 1, s));
+    ARL_TRY(stamp(net, STAGE_OTHER, s));
+  }
+  return hipSuccess;
 }
 
 // One epoch's gradient: the PPO loss gradient + heads dh (it also snapshots the step counter, as the returns
@@ -549,15 +561,23 @@ hipError_t net_ppo_begin(Net& net, double gamma, int clip_reward, hipStream_t s)
 hipError_t net_ppo_learn(Net& net, float beta, float vcoef, hipStream_t s) {
   const int64_t S = (int64_t)net.T * net.N;
   float* snap = net.ppo_snap;
-  const PpoLossArgs p{net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v), net.at<float>(net.w_probs),
-                      net.at<float>(net.w_logp), net.at<int32_t>(net.w_act), snap, snap + S, snap + 2 * S, net.T, net.N,
-                      net.A, net.ppo_lo, net.ppo_hi, beta, vcoef, net.pi_coef, net.keep_scale,
-                      net.at<float>(net.w_dlogits), net.at<float>(net.w_dv), net.at<float>(net.w_loss), snap + 3 * S};
+  PpoLossArgs p{net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v), net.at<float>(net.w_probs),
+                net.at<float>(net.w_logp), net.at<int32_t>(net.w_act), snap, snap + S, snap + 2 * S, net.T, net.N,
+                net.A, net.ppo_lo, net.ppo_hi, beta, vcoef, net.pi_coef, net.keep_scale,
+                net.at<float>(net.w_dlogits), net.at<float>(net.w_dv), net.at<float>(net.w_loss), snap + 3 * S};
+  p.vold = net.ppo_vold;   // (null: the form without value clipping, the launch it always was)
+  p.ev = net.ppo_ev;
   net.norm_ready = false;   // a new gradient, no folded norm
   net.returns_done = false;
   ARL_TRY(launch_ppo_heads(p, net.at<int64_t>(net.w_ctl), net.p + net.o_piW, net.p + net.o_vW,
                            net.at<float>(net.w_hfc), net.at<float>(net.w_dfc), s));
   ARL_TRY(stamp(net, STAGE_RETURNS, s));
+  net.ppo_epoch += 1;
+  if (net.ppo_aux != nullptr) {   // the epoch's record, while its ratio plane and the slots' log_probs / v stand
+    ARL_TRY(launch_ppo_epoch_stats(p, net.at<int64_t>(net.w_ctl), 0.0, (double)net.ppo_epoch,
+                                   reinterpret_cast<int64_t*>(net.ppo_aux), net.ppo_aux, s));
+    ARL_TRY(stamp(net, STAGE_OTHER, s));
+  }
   ARL_TRY(net_learn_part(net, LEARN_TRUNK, 0.0, beta, vcoef, 0, s));
   return net_learn_part(net, LEARN_CONV, 0.0, beta, vcoef, 0, s);
 }

@@ -156,7 +156,9 @@ struct ReturnsArgs {
 // window's snapshot (arl_net_set_ppo).  false / true in a template argument list are RF_NSTEP / RF_GAE.
 // (ints, not an unnamed enum: the forms appear in the kernels' mangled names through ReturnsArgsT, and an unnamed
 // type there is numbered differently by the host and the device compilation)
-constexpr int RF_NSTEP = 0, RF_GAE = 1, RF_PPO = 2;
+constexpr int RF_NSTEP = 0, RF_GAE = 1, RF_PPO = 2, RF_PPO_VC = 3;
+// RF_PPO_VC: the PPO form with the clipped value loss (arl_net_set_ppo_options); rf_ppo: either PPO form
+constexpr bool rf_ppo(int G) { return G == RF_PPO || G == RF_PPO_VC; }
 // the GAE form's arguments (below): + gl = gamma * lambda.  ReturnsArgsT<RF_NSTEP> is ReturnsArgs itself.
 struct ReturnsArgsGae : ReturnsArgs {
   double gl;
@@ -170,9 +172,16 @@ struct ReturnsArgsPpo : ReturnsArgs {
   float* ratio;
   float lo, hi;
 };
+// the value-clipped PPO form's arguments: + the values the rollout's policy gave (0 where a sample is not live)
+// and ev = (float)vclip_eps, formed on the host
+struct ReturnsArgsPpoVc : ReturnsArgsPpo {
+  const float* vold;
+  float ev;
+};
 template <int G>
-using ReturnsArgsT =
-    std::conditional_t<G == RF_PPO, ReturnsArgsPpo, std::conditional_t<G == RF_GAE, ReturnsArgsGae, ReturnsArgs>>;
+using ReturnsArgsT = std::conditional_t<
+    G == RF_PPO_VC, ReturnsArgsPpoVc,
+    std::conditional_t<G == RF_PPO, ReturnsArgsPpo, std::conditional_t<G == RF_GAE, ReturnsArgsGae, ReturnsArgs>>>;
 
 // dlogits / dv of (step t, env e); returns the two loss terms of the step
 // (pi term without the sign, v term) through lpi / lv
@@ -189,6 +198,9 @@ constexpr int RW = 8;
 // PPO form (RF_PPO; the host picks it while arl_net_set_ppo is on): the return and the advantage are the
 // snapshot's (ppo_snapshot_kernel left there what the two forms above would form), the policy term is the clipped
 // surrogate's with the ratio exp(lp[ac] - lpo).  It scans only the dones, for the segment of keep_loss_scale_same.
+// Value-clipped PPO form (RF_PPO_VC; the host picks it while arl_net_set_ppo_options has vclip_eps > 0): the
+// PPO form with one more load, vold, and a value tail of its own in returns_compute (vclip_step).  New
+// instantiations only: the other three forms compile to the instructions they had (DESIGN.md "PPO options").
 template <int G>
 struct GaeIn {};
 template <>
@@ -200,6 +212,27 @@ template <>
 struct GaeIn<RF_PPO> {
   float lpo, adv, Rf;
 };
+template <>
+struct GaeIn<RF_PPO_VC> : GaeIn<RF_PPO> {
+  float vold;
+};
+// The clipped value loss 0.5 * max((v - R)^2, (v_clip - R)^2), v_clip = vold + clamp(v - vold, -ev, ev), for
+// one sample (the header's "value clipping"; every operation f32 round-to-nearest, unfused): lsq = the square
+// the loss takes; returns taken = the clipped square is the larger, so the value gets no gradient.  Within
+// ev of vold (every sample in epoch 1) this is today's lsq = f32(dvv * dvv), not taken.  Shared by the loss
+// gradient (returns_compute) and the per-epoch record (ppo_epoch_stats_kernel), as return_step / gae_step are.
+__device__ inline bool vclip_step(float vi, float vold, float Rf, float ev, float dvv, float& lsq) {
+  const float dvo = __fsub_rn(vi, vold);
+  const float lu = __fmul_rn(dvv, dvv);
+  lsq = lu;
+  if (fabsf(dvo) <= ev) return false;
+  const float vc = __fadd_rn(vold, dvo > 0.f ? ev : -ev);
+  const float dvc = __fsub_rn(vc, Rf);
+  const float lc = __fmul_rn(dvc, dvc);
+  const bool taken = lc > lu;
+  if (taken) lsq = lc;
+  return taken;
+}
 // AM >= A: the action count the registers are sized for (4 / 8 / MAXA)
 template <int AM, int G = RF_NSTEP>
 struct RetIn : GaeIn<G> {   // everything returns_one reads of step (t, e)
@@ -221,14 +254,15 @@ __device__ inline void returns_load(const ReturnsArgsT<G>& a, int t, int e, RetI
 #pragma unroll
   for (int k = 0; k < RW; ++k) {
     const int64_t o = (int64_t)min(k, T - 1) * n + e;
-    if constexpr (G != RF_PPO) in.rw[k] = a.rewards[o];
+    if constexpr (!rf_ppo(G)) in.rw[k] = a.rewards[o];
     in.dn[k] = a.dones[o];
     if constexpr (G == RF_GAE) in.vw[k] = a.v[o];
   }
-  if constexpr (G == RF_PPO) {
+  if constexpr (rf_ppo(G)) {
     in.lpo = a.lpo[i];
     in.adv = a.adv[i];
     in.Rf = a.ret[i];
+    if constexpr (G == RF_PPO_VC) in.vold = a.vold[i];
   } else {
     in.vboot = a.v[(int64_t)T * n + e];
   }
@@ -246,7 +280,7 @@ __device__ inline void returns_compute(const ReturnsArgsT<G>& a, int t, int e, c
   const float* rw = in.rw;
   const int* dn = in.dn;
   float vboot = 0.f;
-  if constexpr (G != RF_PPO) vboot = in.vboot;
+  if constexpr (!rf_ppo(G)) vboot = in.vboot;
   const float vi = in.vi;
   const int ac = in.ac, di = in.di;
   float* dl = a.dlogits + i * A;
@@ -255,7 +289,7 @@ __device__ inline void returns_compute(const ReturnsArgsT<G>& a, int t, int e, c
     a.dv[i] = 0.f;
     if (sdl)
       for (int k = 0; k <= A; ++k) sdl[k] = 0.f;
-    if constexpr (G == RF_PPO)
+    if constexpr (rf_ppo(G))
       if (a.ratio != nullptr) a.ratio[i] = 0.f;
     lpi = 0.f;
     lv = 0.f;
@@ -270,7 +304,7 @@ __device__ inline void returns_compute(const ReturnsArgsT<G>& a, int t, int e, c
     for (int k = RW - 1; k >= 0; --k)
       if (k < T && k >= t) {
         if (dn[k] & 1) seg_end = k;
-        if constexpr (G != RF_PPO) R = return_step(R, dn[k], rw[k], a.gamma, a.clip_reward);
+        if constexpr (!rf_ppo(G)) R = return_step(R, dn[k], rw[k], a.gamma, a.clip_reward);
         if constexpr (G == RF_GAE)   // v[k + 1]: the bootstrap value at the window's last step (k = RW - 1 is always that)
           Gl = gae_step(Gl, dn[k], rw[k], in.vw[k], k == T - 1 ? vboot : in.vw[k < RW - 1 ? k + 1 : k], a.gamma,
                         in.gl, a.clip_reward);
@@ -282,7 +316,7 @@ __device__ inline void returns_compute(const ReturnsArgsT<G>& a, int t, int e, c
     for (int tt = T - 1; tt >= t; --tt) {
       const int64_t j = (int64_t)tt * n + e;
       if (a.dones[j] & 1) seg_end = tt;
-      if constexpr (G != RF_PPO) R = return_step(R, a.dones[j], a.rewards[j], a.gamma, a.clip_reward);
+      if constexpr (!rf_ppo(G)) R = return_step(R, a.dones[j], a.rewards[j], a.gamma, a.clip_reward);
       if constexpr (G == RF_GAE)
         Gl = gae_step(Gl, a.dones[j], a.rewards[j], a.v[j], tt == T - 1 ? vboot : a.v[j + n], a.gamma, in.gl,
                       a.clip_reward);
@@ -303,7 +337,7 @@ __device__ inline void returns_compute(const ReturnsArgsT<G>& a, int t, int e, c
     }
   }
   float Rf, adv;
-  if constexpr (G == RF_PPO) {
+  if constexpr (rf_ppo(G)) {
     Rf = in.Rf;
     adv = in.adv;
   } else {
@@ -322,7 +356,7 @@ __device__ inline void returns_compute(const ReturnsArgsT<G>& a, int t, int e, c
   // the policy term's weight w (of the gradient) and its loss term: adv and lp[ac] * adv, or the clipped
   // surrogate's (the header's "clipped-surrogate epochs"); rho == 1 leaves w == adv
   float w = adv, surr = 0.f;
-  if constexpr (G == RF_PPO) {
+  if constexpr (rf_ppo(G)) {
     const float rho = (float)exp((double)__fsub_rn(lpa, in.lpo));
     const bool active = adv >= 0.f ? rho <= a.hi : rho >= a.lo;
     w = active ? __fmul_rn(rho, adv) : 0.f;
@@ -340,6 +374,16 @@ __device__ inline void returns_compute(const ReturnsArgsT<G>& a, int t, int e, c
       if (sdl) sdl[k] = d;
     }
   const float dvv = __fsub_rn(vi, Rf);
+  if constexpr (G == RF_PPO_VC) {   // the clipped value loss: its own tail, the other forms' below stays as it was
+    float lsq;
+    const bool taken = vclip_step(vi, in.vold, Rf, a.ev, dvv, lsq);
+    const float dvc = taken ? 0.f : __fmul_rn(vf, dvv);
+    a.dv[i] = dvc;
+    if (sdl) sdl[A] = dvc;
+    lpi = __fmul_rn(pf, __fadd_rn(surr, __fmul_rn(a.beta, H)));
+    lv = __fmul_rn(vf, __fmul_rn(lsq, 0.5f));
+    return;
+  }
   const float dvo = __fmul_rn(vf, dvv);
   a.dv[i] = dvo;
   if (sdl) sdl[A] = dvo;
@@ -659,11 +703,22 @@ static ReturnsArgsPpo ppo_args(const PpoLossArgs& p, int64_t* ctl_snap) {
   return a;
 }
 
+// p.vold set: the value-clipped form's arguments
+static ReturnsArgsPpoVc ppo_vc_args(const PpoLossArgs& p, int64_t* ctl_snap) {
+  ReturnsArgsPpoVc a;
+  static_cast<ReturnsArgsPpo&>(a) = ppo_args(p, ctl_snap);
+  a.vold = p.vold;
+  a.ev = p.ev;
+  return a;
+}
+
 hipError_t launch_ppo_lossgrad(const PpoLossArgs& p, hipStream_t s) {
   if (p.n <= 0) return hipSuccess;
   if (p.T < 1 || p.T > 256) return hipErrorInvalidValue;
   const int EB = 256 / p.T;
-  hipLaunchKernelGGL(returns_kernel<RF_PPO>, dim3((p.n + EB - 1) / EB), dim3(256), 0, s, ppo_args(p, nullptr));
+  const dim3 grid((p.n + EB - 1) / EB), blk(256);
+  if (p.vold != nullptr) hipLaunchKernelGGL(returns_kernel<RF_PPO_VC>, grid, blk, 0, s, ppo_vc_args(p, nullptr));
+  else hipLaunchKernelGGL(returns_kernel<RF_PPO>, grid, blk, 0, s, ppo_args(p, nullptr));
   return hipGetLastError();
 }
 
@@ -671,12 +726,256 @@ hipError_t launch_ppo_heads(const PpoLossArgs& p, int64_t* ctl_snap, const float
                             const float* mask, float* dh, hipStream_t s) {
   if (p.n <= 0) return hipSuccess;
   if (p.T < 1 || p.T > 64 || p.A < 1 || p.A > MAXA) return hipErrorInvalidValue;
-  const ReturnsArgsPpo a = ppo_args(p, ctl_snap);
   const dim3 grid(p.n), blk(256);
+  if (p.vold != nullptr) {
+    const ReturnsArgsPpoVc a = ppo_vc_args(p, ctl_snap);
+    if (p.T > 8) hipLaunchKernelGGL((returns_heads_kernel<MAXA, 32, RF_PPO_VC>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
+    else if (p.A <= 4) hipLaunchKernelGGL((returns_heads_kernel<4, 8, RF_PPO_VC>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
+    else if (p.A <= 8) hipLaunchKernelGGL((returns_heads_kernel<8, 8, RF_PPO_VC>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
+    else hipLaunchKernelGGL((returns_heads_kernel<MAXA, 8, RF_PPO_VC>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
+    return hipGetLastError();
+  }
+  const ReturnsArgsPpo a = ppo_args(p, ctl_snap);
   if (p.T > 8) hipLaunchKernelGGL((returns_heads_kernel<MAXA, 32, RF_PPO>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
   else if (p.A <= 4) hipLaunchKernelGGL((returns_heads_kernel<4, 8, RF_PPO>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
   else if (p.A <= 8) hipLaunchKernelGGL((returns_heads_kernel<8, 8, RF_PPO>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
   else hipLaunchKernelGGL((returns_heads_kernel<MAXA, 8, RF_PPO>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- PPO options (arl_net_set_ppo_options)
+// The two one-workgroup kernels below follow window_stats_kernel's ordering rule (optim.hip): thread j of 256
+// owns envs j, j + 256, ... ascending, and per env the steps t = 0 .. T - 1 ascending; its f64 partial sums
+// start at +0.0 and a sample that is not live (dones bit 1) adds +0.0; partial 0, then partials 1 .. 255 are
+// added in order.  Every f64 operation is an unfused round-to-nearest one, so a NumPy restatement in this
+// order gives the same bits.
+
+// partial 0 + partial 1 + ... + partial 255 of column f (stride S doubles a thread), the adds in that order;
+// op 1 / 2: the column's max / min instead (one instruction stream for the lanes of a wave, whatever their op).
+// The LDS reads of 32 partials at a time are in flight ahead of the chain that waits for them.
+template <int S>
+__device__ inline double ordered_total(const double* part, int f, int op = 0) {
+  double sum = part[f];
+  for (int q0 = 1; q0 < 256; q0 += 32) {
+    double x[32];
+#pragma unroll
+    for (int u = 0; u < 32; ++u) x[u] = part[min(q0 + u, 255) * S + f];
+#pragma unroll
+    for (int u = 0; u < 32; ++u)
+      if (q0 + u < 256) {
+        const double add = __dadd_rn(sum, x[u]), mx = fmax(sum, x[u]), mn = fmin(sum, x[u]);
+        sum = op == 0 ? add : op == 1 ? mx : mn;
+      }
+  }
+  return sum;
+}
+
+// v_old of a window (arl_ppo_begin with value clipping on): v[t, e] of a live sample, else 0
+__global__ void __launch_bounds__(256)
+ppo_vold_kernel(const uint8_t* __restrict__ dones, const float* __restrict__ v, float* __restrict__ vold, int64_t S) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < S) vold[i] = (dones[i] & 2) ? 0.f : v[i];
+}
+
+// A thread's samples in the one-workgroup kernels' order, f(i, dones[i], adv[i]) for each: envs j, j + 256, ...,
+// per env t ascending.  Windows up to PO_RW steps load an env's adv / dones into registers first (static
+// indices, clamped offsets, as returns_load), so the loads of an env are in flight together and ahead of f's
+// stores; longer windows loop over memory.
+constexpr int PO_RW = 8;
+template <class F>
+__device__ inline void ppo_for_samples(const uint8_t* __restrict__ dones, const float* adv, int T, int n, F&& f) {
+  for (int e = threadIdx.x; e < n; e += 256) {
+    if (T <= PO_RW) {
+      float a[PO_RW];
+      int d[PO_RW];
+#pragma unroll
+      for (int k = 0; k < PO_RW; ++k) {
+        const int64_t o = (int64_t)min(k, T - 1) * n + e;
+        a[k] = adv[o];
+        d[k] = dones[o];
+      }
+#pragma unroll
+      for (int k = 0; k < PO_RW; ++k)
+        if (k < T) f((int64_t)k * n + e, d[k], a[k]);
+    } else {
+      for (int t = 0; t < T; ++t) {
+        const int64_t i = (int64_t)t * n + e;
+        f(i, (int)dones[i], adv[i]);
+      }
+    }
+  }
+}
+
+// Advantage normalisation (the header's definition): the snapshot's adv plane in place, over the live samples,
+//   mean = S1 / n_live,  std = sqrt(S2 / n_live) (population),  adv' = (float)((adv - mean) / (std + 1e-8))
+// in three passes; each thread reads and writes only its own envs' samples, and the two barriers order the
+// partials.  Every thread forms the totals itself from the 256 partials in LDS (the same adds in the same
+// order, so the same bits).  moments: n_live, mean, std.
+__global__ void __launch_bounds__(256)
+ppo_normalize_adv_kernel(const uint8_t* __restrict__ dones, float* adv, int T, int n, double* __restrict__ moments) {
+  __shared__ double p1[256], p2[256];
+  __shared__ int pc[256];
+  const int j = threadIdx.x;
+  double s1 = 0.0;
+  int cnt = 0;
+  ppo_for_samples(dones, adv, T, n, [&](int64_t, int d, float a) {
+    const bool live = (d & 2) == 0;
+    s1 = __dadd_rn(s1, live ? (double)a : 0.0);
+    cnt += live ? 1 : 0;
+  });
+  p1[j] = s1;
+  pc[j] = cnt;
+  __syncthreads();
+  int64_t n_live = 0;
+  for (int q = 0; q < 256; ++q) n_live += pc[q];
+  if (n_live == 0) {   // nothing to rewrite (the same branch in every thread)
+    if (j == 0) moments[0] = moments[1] = moments[2] = 0.0;
+    return;
+  }
+  const double nl = (double)n_live;
+  const double mean = ordered_total<1>(p1, 0) / nl;
+  double s2 = 0.0;
+  ppo_for_samples(dones, adv, T, n, [&](int64_t, int d, float a) {
+    const double dd = __dsub_rn((double)a, mean);
+    s2 = __dadd_rn(s2, (d & 2) == 0 ? __dmul_rn(dd, dd) : 0.0);
+  });
+  p2[j] = s2;
+  __syncthreads();
+  const double sd = sqrt(ordered_total<1>(p2, 0) / nl);
+  const double den = __dadd_rn(sd, 1e-8);
+  ppo_for_samples(dones, adv, T, n, [&](int64_t i, int d, float a) {
+    if ((d & 2) == 0) adv[i] = (float)(__dsub_rn((double)a, mean) / den);
+  });
+  if (j == 0) {
+    moments[0] = nl;
+    moments[1] = mean;
+    moments[2] = sd;
+  }
+}
+
+// The per-epoch record (the header's table): fields 2 .. 9 from one pass over the samples, combined by the
+// first eight lanes (one field each); thread 0 writes the record.  count non-null: the record goes to slot
+// *count % PPO_LOG of the ring at rec and the count is advanced; null: rec is the record itself.
+struct EpochStatsArgs {
+  const uint8_t* dones;
+  const float *v, *logp;
+  const int32_t* act;
+  const float *lpo, *adv, *ret, *ratio, *vold;   // vold: null = no value clipping (vclipped = 0)
+  int T, n, A;
+  float lo, hi, ev;
+  const int64_t* ctl;   // non-null: window = ctl[CTL_WINDOW]
+  double window, epoch;
+  int64_t* count;
+  double* rec;
+};
+constexpr int ES_SUMS = 8;   // samples, clipped, kl_sum, ratio_max, ratio_min, vclipped, adv_sum, adv_sumsq
+static_assert(2 + ES_SUMS == PPO_STAT_FIELDS, "epoch record layout");
+__global__ void __launch_bounds__(256)
+ppo_epoch_stats_kernel(EpochStatsArgs a) {
+  __shared__ double part[256 * ES_SUMS];
+  __shared__ double tot[ES_SUMS];
+  const int j = threadIdx.x, T = a.T, n = a.n, A = a.A;
+  double acc[ES_SUMS];
+#pragma unroll
+  for (int f = 0; f < ES_SUMS; ++f) acc[f] = 0.0;
+  double rmax = -HUGE_VAL, rmin = HUGE_VAL;
+  const bool vc = a.vold != nullptr;
+  // one sample into the sums (values loaded by the caller)
+  auto sample = [&](int dn, float lpa, float lpo, float rho, float adv, float vi, float Rf, float vo) {
+    const bool live = (dn & 2) == 0;
+    const float d = __fsub_rn(lpa, lpo);
+    const bool cut = !(adv >= 0.f ? rho <= a.hi : rho >= a.lo);
+    float lsq;
+    const bool taken = vc && vclip_step(vi, vo, Rf, a.ev, __fsub_rn(vi, Rf), lsq);
+    const double ad = (double)adv;
+    acc[0] = __dadd_rn(acc[0], live ? 1.0 : 0.0);
+    acc[1] = __dadd_rn(acc[1], live && cut ? 1.0 : 0.0);
+    acc[2] = __dadd_rn(acc[2], live ? -(double)d : 0.0);
+    acc[5] = __dadd_rn(acc[5], live && taken ? 1.0 : 0.0);
+    acc[6] = __dadd_rn(acc[6], live ? ad : 0.0);
+    acc[7] = __dadd_rn(acc[7], live ? __dmul_rn(ad, ad) : 0.0);
+    rmax = live ? fmax(rmax, (double)rho) : rmax;
+    rmin = live ? fmin(rmin, (double)rho) : rmin;
+  };
+  for (int e = j; e < n; e += 256) {
+    if (T <= PO_RW) {   // the env's window in registers: two rounds of loads (the log-prob gather needs the action)
+      int dn[PO_RW], ac[PO_RW];
+      float lpa[PO_RW], lpo[PO_RW], rho[PO_RW], adv[PO_RW], vi[PO_RW], Rf[PO_RW], vo[PO_RW];
+#pragma unroll
+      for (int k = 0; k < PO_RW; ++k) {
+        const int64_t o = (int64_t)min(k, T - 1) * n + e;
+        dn[k] = a.dones[o];
+        ac[k] = a.act[o];
+        lpo[k] = a.lpo[o];
+        rho[k] = a.ratio[o];
+        adv[k] = a.adv[o];
+        vi[k] = a.v[o];
+        Rf[k] = a.ret[o];
+        vo[k] = vc ? a.vold[o] : 0.f;
+      }
+#pragma unroll
+      for (int k = 0; k < PO_RW; ++k)
+        lpa[k] = a.logp[((int64_t)min(k, T - 1) * n + e) * A + min(max(ac[k], 0), A - 1)];
+#pragma unroll
+      for (int k = 0; k < PO_RW; ++k)
+        if (k < T) sample(dn[k], lpa[k], lpo[k], rho[k], adv[k], vi[k], Rf[k], vo[k]);
+    } else {
+      for (int t = 0; t < T; ++t) {
+        const int64_t i = (int64_t)t * n + e;
+        sample(a.dones[i], a.logp[i * A + min(max(a.act[i], 0), A - 1)], a.lpo[i], a.ratio[i], a.adv[i], a.v[i],
+               a.ret[i], vc ? a.vold[i] : 0.f);
+      }
+    }
+  }
+  acc[3] = rmax;
+  acc[4] = rmin;
+#pragma unroll
+  for (int f = 0; f < ES_SUMS; ++f) part[j * ES_SUMS + f] = acc[f];
+  __syncthreads();
+  if (j < ES_SUMS) tot[j] = ordered_total<ES_SUMS>(part, j, j == 3 ? 1 : j == 4 ? 2 : 0);
+  __syncthreads();
+  if (j != 0) return;
+  double* rec = a.rec;
+  int64_t cnt = 0;
+  if (a.count != nullptr) {
+    cnt = *a.count;
+    rec += PPO_AUX_HEAD + (int64_t)((uint64_t)cnt % PPO_LOG) * PPO_STAT_FIELDS;
+  }
+  const bool any = tot[0] > 0.0;
+  rec[0] = a.ctl != nullptr ? (double)a.ctl[CTL_WINDOW] : a.window;
+  rec[1] = a.epoch;
+  rec[2] = tot[0];
+  rec[3] = tot[1];
+  rec[4] = tot[2];
+  rec[5] = any ? tot[3] : 0.0;
+  rec[6] = any ? tot[4] : 0.0;
+  rec[7] = tot[5];
+  rec[8] = tot[6];
+  rec[9] = tot[7];
+  if (a.count != nullptr) *a.count = cnt + 1;
+}
+
+hipError_t launch_ppo_vold(const uint8_t* dones, const float* v, float* vold, int T, int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int64_t S = (int64_t)T * n;
+  hipLaunchKernelGGL(ppo_vold_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, dones, v, vold, S);
+  return hipGetLastError();
+}
+
+hipError_t launch_ppo_normalize_adv(const uint8_t* dones, float* adv, int T, int n, double* moments, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (T < 1 || T > 256) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ppo_normalize_adv_kernel, dim3(1), dim3(256), 0, s, dones, adv, T, n, moments);
+  return hipGetLastError();
+}
+
+hipError_t launch_ppo_epoch_stats(const PpoLossArgs& p, const int64_t* ctl, double window, double epoch, int64_t* count,
+                                  double* rec, hipStream_t s) {
+  if (p.n <= 0) return hipSuccess;
+  if (p.T < 1 || p.T > 256 || p.A < 1 || p.A > MAXA || p.ratio == nullptr) return hipErrorInvalidValue;
+  const EpochStatsArgs a{p.dones, p.v, p.logp, p.act, p.lpo, p.adv, p.ret, p.ratio, p.vold, p.T, p.n, p.A,
+                         p.lo, p.hi, p.ev, ctl, window, epoch, count, rec};
+  hipLaunchKernelGGL(ppo_epoch_stats_kernel, dim3(1), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -340,11 +340,79 @@ int arl_net_set_gae(arl_net* net, double lambda);
  * Window statistics: one record per update, K per window; in epochs >= 2 fields
  * 5-13 describe the slots' current contents (the re-forwarded v and entropy,
  * that epoch's losses; returns and advantages recomputed from the current v).
- * Not built: minibatches within an epoch, advantage normalisation, value
- * clipping, several ranks. */
+ * Fields 12 / 13 (adv_sum, adv_sumsq) stay the un-normalised advantage whatever
+ * arl_net_set_ppo_options sets.
+ * Not built: minibatches within an epoch, several ranks. */
 int arl_net_set_ppo(arl_net* net, float* snap, double clip_eps);
 int arl_ppo_begin(arl_net* net, double gamma, int clip_reward, void* stream);
 int arl_ppo_learn(arl_net* net, double beta, double v_loss_coef, void* stream);
+
+/* Options of the PPO epochs: advantage normalisation, the clipped value loss and
+ * a device-side record per epoch.  All off by default, (0, 0.0, NULL, NULL):
+ * every call then makes exactly the launches it made before.  Host state of the
+ * handle, like arl_net_set_ppo (works on an unbound handle); read when
+ * arl_ppo_begin / arl_ppo_learn launch, inert while PPO is off; a captured window
+ * keeps what it was captured with.  Additions to ABI 4.
+ *
+ * A thread order shared by the two one-workgroup kernels below ("ordered sum"):
+ * thread j of 256 owns envs j, j + 256, ... ascending and, per env, the steps
+ * t = 0 .. t_max - 1 ascending; its float64 partial starts at +0.0, a sample that
+ * is not live (dones bit 1) adds +0.0; the total is partial 0 + partial 1 + ... +
+ * partial 255 in that order.  Every float64 operation is unfused round-to-nearest.
+ *
+ * norm_adv != 0 -- advantage normalisation.  arl_ppo_begin, right after the
+ * snapshot, rewrites the snapshot's adv plane in place (logp_old and ret stay, so
+ * the value target does not change):
+ *   n_live = the count of live samples,  S1 = ordered sum of (double)adv
+ *   mean = S1 / (double)n_live
+ *   S2 = ordered sum of dd * dd,  dd = (double)adv - mean
+ *   std = sqrt(S2 / (double)n_live)               the population form
+ *   adv' = (float)(((double)adv - mean) / (std + 1e-8))   live samples, one rounding
+ * A sample that is not live stays 0.  n_live == 0: nothing is rewritten and the
+ * moments are 0, 0, 0.  (n_live, mean, std) go to aux[1..3].  Needs aux.
+ *
+ * vclip_eps > 0 -- the clipped value loss 0.5 * max((v - R)^2, (v_clip - R)^2),
+ * v_clip = v_old + clamp(v - v_old, -eps, eps).  v_old: t_max * n_envs f32,
+ * caller-owned, 16-byte aligned; arl_ppo_begin writes v_old[t, e] = v[t, e] of a
+ * live sample, 0 otherwise (one small launch).  In arl_ppo_learn only the value
+ * tail changes; with ev = (float)vclip_eps formed on the host, f32 unfused:
+ *   dvv = f32(vi - Rf)                     as without it
+ *   do  = f32(vi - vold);  inside = fabsf(do) <= ev
+ *   inside:  dv = f32(vf * dvv);  lv = f32(vf * f32(f32(dvv * dvv) * 0.5f))
+ *   outside: vc = f32(vold + (do > 0 ? ev : -ev));  dvc = f32(vc - Rf)
+ *            lu = f32(dvv * dvv);  lc = f32(dvc * dvc);  taken = lc > lu
+ *            dv = taken ? 0.0f : f32(vf * dvv)
+ *            lv = f32(vf * f32((taken ? lc : lu) * 0.5f))
+ * In epoch 1 vi == vold, so every sample is inside and dv, dlogits are bit for
+ * bit those without value clipping.  vclip_eps == 0 switches it off (v_old is
+ * then ignored).
+ *
+ * aux != NULL -- ARL_PPO_AUX_DOUBLES doubles, caller-owned, 8-byte aligned, zeroed
+ * by the caller (arl_net_reset does not own it).  Word 0 is an int64: the count of
+ * epoch records ever written.  Words 1..3: n_live, mean, std of the last
+ * normalisation.  Words 4..7 reserved.  Record r sits at
+ * 8 + (r % ARL_PPO_LOG) * ARL_PPO_STAT_FIELDS.  arl_ppo_learn launches the record's
+ * kernel right after its loss-gradient launch (stream order: it sees that epoch's
+ * ratio plane and the slots' log_probs / v).  Fields, sums ordered as above:
+ *   0 window     the control block's window counter, read on the device
+ *   1 epoch      1-based, counted on the host from arl_ppo_begin
+ *   2 samples    live samples
+ *   3 clipped    live samples with !(adv >= 0 ? rho <= hi : rho >= lo), rho from
+ *                the ratio plane: the learner's decision
+ *   4 kl_sum     sum of -(double)d, d = f32(lp[ac] - lpo)
+ *   5 ratio_max  over live samples, 0 when there are none
+ *   6 ratio_min  over live samples, 0 when there are none
+ *   7 vclipped   live samples with `taken` above; 0 with value clipping off
+ *   8 adv_sum    sum of (double)adv as the epoch used it (after normalisation)
+ *   9 adv_sumsq  sum of its float64 square
+ *
+ * ARL_EINVAL: vclip_eps negative or not finite; vclip_eps > 0 with a NULL v_old;
+ * norm_adv with a NULL aux; a misaligned pointer.  ARL_ESTATE: any option on for a
+ * net arl_net_set_ppo refuses. */
+#define ARL_PPO_LOG 16            /* epoch records kept */
+#define ARL_PPO_STAT_FIELDS 10
+#define ARL_PPO_AUX_DOUBLES (8 + ARL_PPO_LOG * ARL_PPO_STAT_FIELDS)
+int arl_net_set_ppo_options(arl_net* net, int norm_adv, double vclip_eps, float* v_old, double* aux);
 
 /* GradientClipping's squared norm (a3c_ale.py:226) folded into arl_learn:
  * with on != 0, arl_learn's conv slab reduce also leaves the f64 partial
@@ -862,6 +930,36 @@ int arl_ppo_lossgrad(const uint8_t* dones, const float* v, const float* probs, c
                      int64_t n, int n_actions, double clip_eps, double beta, double pi_loss_coef, double v_loss_coef,
                      int keep_loss_scale_same, float* dlogits, float* dv, float* loss, float* ratio_out,
                      void* stream);
+
+/* arl_ppo_lossgrad with the clipped value loss (arl_net_set_ppo_options has the
+ * definition).  The two added arguments stand beside their kin: v_old (t_max, n)
+ * closes the snapshot's planes, after ret; vclip_eps follows clip_eps.  vclip_eps
+ * not finite or <= 0, a NULL v_old: ARL_EINVAL.  Addition to ABI 4. */
+int arl_ppo_lossgrad_vclip(const uint8_t* dones, const float* v, const float* probs, const float* log_probs,
+                           const int32_t* actions, const float* logp_old, const float* adv, const float* ret,
+                           const float* v_old, int t_max, int64_t n, int n_actions, double clip_eps,
+                           double vclip_eps, double beta, double pi_loss_coef, double v_loss_coef,
+                           int keep_loss_scale_same, float* dlogits, float* dv, float* loss, float* ratio_out,
+                           void* stream);
+
+/* The advantage normalisation of arl_ppo_begin on explicit arrays
+ * (arl_net_set_ppo_options has the definition): adv (t_max, n) in place,
+ * moments3_device = (n_live, mean, std), 3 doubles on the device.  One workgroup.
+ * t_max <= 256; n == 0 returns ARL_OK without a launch.  Addition to ABI 4. */
+int arl_ppo_normalize_adv(const uint8_t* dones, float* adv, int t_max, int64_t n, double* moments3_device,
+                          void* stream);
+
+/* One epoch's record on explicit arrays (arl_net_set_ppo_options has the fields):
+ * v, log_probs, actions the current policy's (rows 0 .. t_max - 1 are read),
+ * logp_old / adv / ret / ratio the snapshot's planes after arl_ppo_lossgrad,
+ * v_old or NULL (then vclip_eps is not read and vclipped = 0); window and epoch
+ * are stored as given; record10_device: ARL_PPO_STAT_FIELDS doubles on the device.
+ * One workgroup.  t_max <= 256, n_actions <= 32; n == 0 returns ARL_OK without a
+ * launch.  Addition to ABI 4. */
+int arl_ppo_epoch_stats(const uint8_t* dones, const float* v, const float* log_probs, const int32_t* actions,
+                        const float* logp_old, const float* adv, const float* ret, const float* ratio,
+                        const float* v_old, int t_max, int64_t n, int n_actions, double clip_eps, double vclip_eps,
+                        double window, double epoch, double* record10_device, void* stream);
 
 /* ------------------------------------------------------------------ measurement */
 

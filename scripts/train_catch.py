@@ -13,11 +13,13 @@ scores about 0.14 per life.
 Defaults are the reference's hyperparameters (RMSpropAsync lr 7e-4, alpha 0.99, eps 0.1, clip 40, beta 0.01,
 gamma 0.99) on the FF model with 256 envs; the batched learner sums the gradient of all envs, so --batch-loss
 mean, --opt adam, --gae-lambda and --ppo-epochs (clipped-surrogate epochs on each window's rollout, with
---ppo-clip; each report row then carries A3C.ppo_stats of the last epoch) are there to try.  One JSON line at the end (and --out FILE).
+--ppo-clip; each report row then carries A3C.ppo_stats of the last epoch; --ppo-norm-adv and --ppo-vclip X switch
+the epochs' advantage normalisation and clipped value loss on, and each row then also carries the last epoch's
+device-side record, A3C.ppo_epoch_stats) are there to try.  One JSON line at the end (and --out FILE).
 
     python scripts/train_catch.py [--env catch|breakout] [--windows 4000] [--report 200] [--envs 256] [--seed 0]
                                   [--lr 7e-4] [--opt rmsprop|adam] [--batch-loss sum|mean] [--gae-lambda 1.0]
-                                  [--arch ff|lstm] [--ppo-epochs 1] [--ppo-clip 0.2]
+                                  [--arch ff|lstm] [--ppo-epochs 1] [--ppo-clip 0.2] [--ppo-norm-adv] [--ppo-vclip X]
 """
 import argparse
 import json
@@ -34,7 +36,8 @@ import asyncrl_amd as pkg  # noqa: E402
 
 
 def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", batch_loss="sum", gae_lambda=1.0,
-          arch="ff", beta=1e-2, eps=None, device="cuda:0", log=print, env="catch", ppo_epochs=1, ppo_clip=0.2):
+          arch="ff", beta=1e-2, eps=None, device="cuda:0", log=print, env="catch", ppo_epochs=1, ppo_clip=0.2, ppo_norm_adv=False,
+          ppo_vclip=None):
     """Returns the curve: one dict per report with the window count, the episodes completed since the last
     report and their mean return, and the newest window record's entropy / value / gradient norm."""
     dev = torch.device(device)
@@ -47,7 +50,8 @@ def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", ba
         optimizer = pkg.RMSpropAsync(lr=lr, eps=1e-1 if eps is None else eps, alpha=0.99).setup(model)
     optimizer.add_hook(pkg.GradientClipping(40))
     agent = pkg.A3C(model, optimizer, T, 0.99, beta=beta, batch_loss=batch_loss, gae_lambda=gae_lambda,
-                    collectives=False, ppo_epochs=ppo_epochs, ppo_clip=ppo_clip)
+                    collectives=False, ppo_epochs=ppo_epochs, ppo_clip=ppo_clip, ppo_norm_adv=ppo_norm_adv,
+                    ppo_vclip=ppo_vclip)
     net = model.net
     net.set_episode_stats(True)
     net.set_window_stats(True)
@@ -78,12 +82,17 @@ def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", ba
                "v_loss": ws["v_loss"], "seconds": time.perf_counter() - t0}
         if ppo_epochs > 1:
             row.update(agent.ppo_stats(stream=stream))
+        if ppo_norm_adv or ppo_vclip is not None:
+            row["ppo_epoch"] = agent.ppo_epoch_stats(1, stream=stream)[0]
         curve.append(row)
         log("windows %6d  episodes %6d  return %+.3f  entropy %.3f  v %+.3f  |g| %9.3f  pi_loss %+10.3f  "
             "v_loss %9.3f  %.1fs" % (done, row["episodes"], row["mean_return"], row["entropy"], row["value_mean"],
                                      row["grad_norm"], row["pi_loss"], row["v_loss"], row["seconds"])
             + ("  clip %.3f  kl %+.4f  rho_max %.3f" % (row["clip_fraction"], row["approx_kl"], row["ratio_max"])
-               if ppo_epochs > 1 else ""))
+               if ppo_epochs > 1 else "")
+            + ("  vclip %.3f  adv %+.3f +- %.3f" % tuple(row["ppo_epoch"][k] for k in ("vclip_fraction", "adv_mean",
+                                                                                          "adv_std"))
+               if "ppo_epoch" in row else ""))
     return curve
 
 
@@ -103,6 +112,8 @@ def main():
     ap.add_argument("--arch", choices=("ff", "lstm"), default="ff")
     ap.add_argument("--ppo-epochs", type=int, default=1)
     ap.add_argument("--ppo-clip", type=float, default=0.2)
+    ap.add_argument("--ppo-norm-adv", action="store_true")
+    ap.add_argument("--ppo-vclip", type=float, default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     cfg = {k: v for k, v in vars(a).items() if k != "out"}
