@@ -957,31 +957,42 @@ int arl_policy(const float* hh, int64_t n, const float* Wpi, const float* bpi, c
                     "policy");
 }
 
+// arl_returns_lossgrad is arl_returns_lossgrad_gae at lambda = 1 (gae_on(1.0) is false: the n-step kernel it always
+// launched); who: their error texts' prefix
+static int returns_lossgrad(const char* who_, const float* rewards, const uint8_t* dones, const float* v,
+                            const float* probs, const float* logp, const int32_t* act, int T, int64_t n, int A,
+                            double gamma, double lambda, double beta, double pi_loss_coef, double vcoef,
+                            int keep_loss_scale_same, int clip_reward, float* dlogits, float* dv, float* loss,
+                            void* s) {
+  const std::string who = who_;
+  if (T < 1 || n < 0 || A < 1) return fail(ARL_EINVAL, who + ": bad T / n / A");
+  if (n > 0 && (!rewards || !dones || !v || !probs || !logp || !act || !dlogits || !dv))
+    return fail(ARL_EINVAL, who + ": null pointer");
+  if (!gae_lambda_ok(lambda)) return fail(ARL_EINVAL, who + ": lambda must be finite and in [0, 1]");
+  arl::ReturnsArgs ra{};   // (no step snapshot: ctl stays null)
+  ra.rewards = rewards; ra.dones = dones; ra.v = v; ra.probs = probs; ra.logp = logp; ra.act = act;
+  ra.T = T; ra.n = (int)n; ra.A = A;
+  ra.gamma = gamma; ra.clip_reward = clip_reward;
+  ra.beta = (float)beta; ra.vcoef = (float)vcoef; ra.pcoef = (float)pi_loss_coef;
+  ra.keep_scale = keep_loss_scale_same ? 1 : 0;
+  ra.dlogits = dlogits; ra.dv = dv; ra.loss = loss;
+  return hip_status(arl::launch_returns(ra, lambda, S(s)), who_);
+}
+
 int arl_returns_lossgrad(const float* rewards, const uint8_t* dones, const float* v, const float* probs,
                          const float* logp, const int32_t* act, int T, int64_t n, int A, double gamma, double beta,
                          double pi_loss_coef, double vcoef, int keep_loss_scale_same, int clip_reward, float* dlogits,
                          float* dv, float* loss, void* s) {
-  if (T < 1 || n < 0 || A < 1) return fail(ARL_EINVAL, "returns: bad T / n / A");
-  if (n > 0 && (!rewards || !dones || !v || !probs || !logp || !act || !dlogits || !dv))
-    return fail(ARL_EINVAL, "returns: null pointer");
-  return hip_status(arl::launch_returns(rewards, dones, v, probs, logp, act, T, (int)n, A, gamma, (float)beta,
-                                        (float)vcoef, clip_reward, dlogits, dv, loss, S(s), nullptr,
-                                        (float)pi_loss_coef, keep_loss_scale_same ? 1 : 0),
-                    "returns");
+  return returns_lossgrad("returns", rewards, dones, v, probs, logp, act, T, n, A, gamma, 1.0, beta, pi_loss_coef,
+                          vcoef, keep_loss_scale_same, clip_reward, dlogits, dv, loss, s);
 }
 
 int arl_returns_lossgrad_gae(const float* rewards, const uint8_t* dones, const float* v, const float* probs,
                              const float* logp, const int32_t* act, int T, int64_t n, int A, double gamma,
                              double lambda, double beta, double pi_loss_coef, double vcoef, int keep_loss_scale_same,
                              int clip_reward, float* dlogits, float* dv, float* loss, void* s) {
-  if (T < 1 || n < 0 || A < 1) return fail(ARL_EINVAL, "returns_gae: bad T / n / A");
-  if (n > 0 && (!rewards || !dones || !v || !probs || !logp || !act || !dlogits || !dv))
-    return fail(ARL_EINVAL, "returns_gae: null pointer");
-  if (!gae_lambda_ok(lambda)) return fail(ARL_EINVAL, "returns_gae: lambda must be finite and in [0, 1]");
-  return hip_status(arl::launch_returns(rewards, dones, v, probs, logp, act, T, (int)n, A, gamma, (float)beta,
-                                        (float)vcoef, clip_reward, dlogits, dv, loss, S(s), nullptr,
-                                        (float)pi_loss_coef, keep_loss_scale_same ? 1 : 0, lambda),
-                    "returns_gae");
+  return returns_lossgrad("returns_gae", rewards, dones, v, probs, logp, act, T, n, A, gamma, lambda, beta,
+                          pi_loss_coef, vcoef, keep_loss_scale_same, clip_reward, dlogits, dv, loss, s);
 }
 
 int arl_ppo_snapshot(const float* rewards, const uint8_t* dones, const float* v, const float* logp, const int32_t* act,
@@ -991,24 +1002,64 @@ int arl_ppo_snapshot(const float* rewards, const uint8_t* dones, const float* v,
   if (n > 0 && (!rewards || !dones || !v || !logp || !act || !logp_old || !adv || !ret))
     return fail(ARL_EINVAL, "ppo_snapshot: null pointer");
   if (!gae_lambda_ok(lambda)) return fail(ARL_EINVAL, "ppo_snapshot: lambda must be finite and in [0, 1]");
-  return hip_status(arl::launch_ppo_snapshot(rewards, dones, v, logp, act, T, (int)n, A, gamma, lambda, clip_reward,
-                                             logp_old, adv, ret, S(s)),
-                    "ppo_snapshot");
+  arl::ReturnsArgs ra{};   // what the snapshot reads of it
+  ra.rewards = rewards; ra.dones = dones; ra.v = v; ra.logp = logp; ra.act = act;
+  ra.T = T; ra.n = (int)n; ra.A = A;
+  ra.gamma = gamma; ra.clip_reward = clip_reward;
+  return hip_status(arl::launch_ppo_snapshot(ra, lambda, logp_old, adv, ret, S(s)), "ppo_snapshot");
+}
+
+// The three granular PPO entries (arl_ppo_lossgrad, arl_ppo_lossgrad_vclip, arl_ppo_epoch_stats) share their
+// shape and clip-range checks and the arguments all of them give; who: their error texts' prefix
+static int ppo_dims_ok(const std::string& who, int T, int64_t n, int A) {
+  if (T < 1 || T > 256 || n < 0 || n > INT32_MAX / 256 || A < 1 || A > arl::MAXA)
+    return fail(ARL_EINVAL, who + ": bad T / n / A");
+  return ARL_OK;
+}
+static int clip_eps_ok(const std::string& who, double clip_eps) {
+  if (!(clip_eps > 0.0 && clip_eps < 1.0)) return fail(ARL_EINVAL, who + ": clip_eps must be finite and in (0, 1)");
+  return ARL_OK;
+}
+static arl::PpoLossArgs ppo_entry_args(const uint8_t* dones, const float* v, const float* logp, const int32_t* act,
+                                       const float* logp_old, const float* adv, const float* ret, int T, int64_t n,
+                                       int A, double clip_eps) {
+  arl::PpoLossArgs p{};   // the rest stays 0 / null until the entry names it
+  p.r.dones = dones; p.r.v = v; p.r.logp = logp; p.r.act = act;
+  p.r.T = T; p.r.n = (int)n; p.r.A = A;
+  p.lpo = logp_old; p.adv = adv; p.ret = ret;
+  p.lo = (float)(1.0 - clip_eps); p.hi = (float)(1.0 + clip_eps);
+  return p;
+}
+
+// arl_ppo_lossgrad is arl_ppo_lossgrad_vclip without v_old (vclip false: v_old / vclip_eps are not looked at)
+static int ppo_lossgrad(const char* who_, bool vclip, const uint8_t* dones, const float* v, const float* probs,
+                        const float* logp, const int32_t* act, const float* logp_old, const float* adv,
+                        const float* ret, const float* v_old, int T, int64_t n, int A, double clip_eps,
+                        double vclip_eps, double beta, double pi_loss_coef, double vcoef, int keep_loss_scale_same,
+                        float* dlogits, float* dv, float* loss, float* ratio_out, void* s) {
+  const std::string who = who_;
+  if (const int rc = ppo_dims_ok(who, T, n, A)) return rc;
+  if (n > 0 && (!dones || !v || !probs || !logp || !act || !logp_old || !adv || !ret || (vclip && !v_old) ||
+                !dlogits || !dv))
+    return fail(ARL_EINVAL, who + ": null pointer");
+  if (const int rc = clip_eps_ok(who, clip_eps)) return rc;
+  if (vclip && !(vclip_ok(vclip_eps) && vclip_eps > 0.0))
+    return fail(ARL_EINVAL, who + ": vclip_eps must be finite and > 0");
+  arl::PpoLossArgs p = ppo_entry_args(dones, v, logp, act, logp_old, adv, ret, T, n, A, clip_eps);
+  p.r.probs = probs;
+  p.r.beta = (float)beta; p.r.vcoef = (float)vcoef; p.r.pcoef = (float)pi_loss_coef;
+  p.r.keep_scale = keep_loss_scale_same ? 1 : 0;
+  p.r.dlogits = dlogits; p.r.dv = dv; p.r.loss = loss; p.ratio = ratio_out;
+  if (vclip) { p.vold = v_old; p.ev = (float)vclip_eps; }
+  return hip_status(arl::launch_ppo_lossgrad(p, S(s)), who_);
 }
 
 int arl_ppo_lossgrad(const uint8_t* dones, const float* v, const float* probs, const float* logp, const int32_t* act,
                      const float* logp_old, const float* adv, const float* ret, int T, int64_t n, int A,
                      double clip_eps, double beta, double pi_loss_coef, double vcoef, int keep_loss_scale_same,
                      float* dlogits, float* dv, float* loss, float* ratio_out, void* s) {
-  if (T < 1 || T > 256 || n < 0 || n > INT32_MAX / 256 || A < 1 || A > arl::MAXA)
-    return fail(ARL_EINVAL, "ppo_lossgrad: bad T / n / A");
-  if (n > 0 && (!dones || !v || !probs || !logp || !act || !logp_old || !adv || !ret || !dlogits || !dv))
-    return fail(ARL_EINVAL, "ppo_lossgrad: null pointer");
-  if (!(clip_eps > 0.0 && clip_eps < 1.0)) return fail(ARL_EINVAL, "ppo_lossgrad: clip_eps must be finite and in (0, 1)");
-  const arl::PpoLossArgs p{dones, v, probs, logp, act, logp_old, adv, ret, T, (int)n, A, (float)(1.0 - clip_eps),
-                           (float)(1.0 + clip_eps), (float)beta, (float)vcoef, (float)pi_loss_coef,
-                           keep_loss_scale_same ? 1 : 0, dlogits, dv, loss, ratio_out};
-  return hip_status(arl::launch_ppo_lossgrad(p, S(s)), "ppo_lossgrad");
+  return ppo_lossgrad("ppo_lossgrad", false, dones, v, probs, logp, act, logp_old, adv, ret, nullptr, T, n, A, clip_eps,
+                      0.0, beta, pi_loss_coef, vcoef, keep_loss_scale_same, dlogits, dv, loss, ratio_out, s);
 }
 
 int arl_ppo_lossgrad_vclip(const uint8_t* dones, const float* v, const float* probs, const float* logp,
@@ -1016,20 +1067,9 @@ int arl_ppo_lossgrad_vclip(const uint8_t* dones, const float* v, const float* pr
                            const float* v_old, int T, int64_t n, int A, double clip_eps, double vclip_eps, double beta,
                            double pi_loss_coef, double vcoef, int keep_loss_scale_same, float* dlogits, float* dv,
                            float* loss, float* ratio_out, void* s) {
-  if (T < 1 || T > 256 || n < 0 || n > INT32_MAX / 256 || A < 1 || A > arl::MAXA)
-    return fail(ARL_EINVAL, "ppo_lossgrad_vclip: bad T / n / A");
-  if (n > 0 && (!dones || !v || !probs || !logp || !act || !logp_old || !adv || !ret || !v_old || !dlogits || !dv))
-    return fail(ARL_EINVAL, "ppo_lossgrad_vclip: null pointer");
-  if (!(clip_eps > 0.0 && clip_eps < 1.0))
-    return fail(ARL_EINVAL, "ppo_lossgrad_vclip: clip_eps must be finite and in (0, 1)");
-  if (!(vclip_ok(vclip_eps) && vclip_eps > 0.0))
-    return fail(ARL_EINVAL, "ppo_lossgrad_vclip: vclip_eps must be finite and > 0");
-  arl::PpoLossArgs p{dones, v, probs, logp, act, logp_old, adv, ret, T, (int)n, A, (float)(1.0 - clip_eps),
-                     (float)(1.0 + clip_eps), (float)beta, (float)vcoef, (float)pi_loss_coef,
-                     keep_loss_scale_same ? 1 : 0, dlogits, dv, loss, ratio_out};
-  p.vold = v_old;
-  p.ev = (float)vclip_eps;
-  return hip_status(arl::launch_ppo_lossgrad(p, S(s)), "ppo_lossgrad_vclip");
+  return ppo_lossgrad("ppo_lossgrad_vclip", true, dones, v, probs, logp, act, logp_old, adv, ret, v_old, T, n, A,
+                      clip_eps, vclip_eps, beta, pi_loss_coef, vcoef, keep_loss_scale_same, dlogits, dv, loss,
+                      ratio_out, s);
 }
 
 int arl_ppo_normalize_adv(const uint8_t* dones, float* adv, int T, int64_t n, double* moments3_device, void* s) {
@@ -1043,17 +1083,15 @@ int arl_ppo_epoch_stats(const uint8_t* dones, const float* v, const float* logp,
                         const float* logp_old, const float* adv, const float* ret, const float* ratio,
                         const float* v_old, int T, int64_t n, int A, double clip_eps, double vclip_eps, double window,
                         double epoch, double* record10_device, void* s) {
-  if (T < 1 || T > 256 || n < 0 || n > INT32_MAX / 256 || A < 1 || A > arl::MAXA)
-    return fail(ARL_EINVAL, "ppo_epoch_stats: bad T / n / A");
+  if (const int rc = ppo_dims_ok("ppo_epoch_stats", T, n, A)) return rc;
   if (n > 0 && (!dones || !v || !logp || !act || !logp_old || !adv || !ret || !ratio || !record10_device))
     return fail(ARL_EINVAL, "ppo_epoch_stats: null pointer");
-  if (!(clip_eps > 0.0 && clip_eps < 1.0))
-    return fail(ARL_EINVAL, "ppo_epoch_stats: clip_eps must be finite and in (0, 1)");
+  if (const int rc = clip_eps_ok("ppo_epoch_stats", clip_eps)) return rc;
   if (!vclip_ok(vclip_eps) || (v_old && !(vclip_eps > 0.0)))
     return fail(ARL_EINVAL, "ppo_epoch_stats: vclip_eps must be finite and >= 0, > 0 with v_old");
   if (!aligned(record10_device, 8)) return fail(ARL_EINVAL, "ppo_epoch_stats: the record must be 8-byte aligned");
-  arl::PpoLossArgs p{dones, v, nullptr, logp, act, logp_old, adv, ret, T, (int)n, A, (float)(1.0 - clip_eps),
-                     (float)(1.0 + clip_eps), 0.f, 0.f, 0.f, 0, nullptr, nullptr, nullptr, const_cast<float*>(ratio)};
+  arl::PpoLossArgs p = ppo_entry_args(dones, v, logp, act, logp_old, adv, ret, T, n, A, clip_eps);
+  p.ratio = const_cast<float*>(ratio);   // (read only)
   p.vold = v_old;
   p.ev = (float)vclip_eps;
   return hip_status(arl::launch_ppo_epoch_stats(p, nullptr, window, epoch, nullptr, record10_device, S(s)),

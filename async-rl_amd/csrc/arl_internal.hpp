@@ -9,6 +9,9 @@
 #include "../../include/asyncrl_hip.h"
 #include "fastdiv.hpp"
 
+// propagate a failed launch / runtime call out of a function that returns hipError_t
+#define ARL_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return _e; } while (0)
+
 namespace arl {
 
 // control block (device int64[16]), read by kernels so that a captured window
@@ -328,6 +331,12 @@ hipError_t ensure_fc_planes(Net& net, hipStream_t s);   // rebuild the FC weight
 enum { LEARN_RETURNS = 0, LEARN_TRUNK, LEARN_CONV, LEARN_PARTS };
 hipError_t net_learn_part(Net& net, int part, double gamma, float beta, float vcoef, int clip_reward, hipStream_t s);
 hipError_t net_learn(Net& net, double gamma, float beta, float vcoef, int clip_reward, hipStream_t s);
+// what every returns launch of a net (or the PPO snapshot standing in for one) leaves for the window statistics
+inline void note_returns_launch(Net& net, double gamma, int clip_reward) {
+  net.win_gamma = gamma;
+  net.win_clip_reward = clip_reward;
+  net.win_lambda = net.gae_lambda;
+}
 // PPO epochs (net.ppo_snap set, FF): the window's snapshot after its bootstrap forward, and one epoch's gradient
 // from the slots' current contents (loss gradient + heads dh, LEARN_TRUNK, LEARN_CONV; no folded clip norm)
 hipError_t net_ppo_begin(Net& net, double gamma, int clip_reward, hipStream_t s);
@@ -611,50 +620,64 @@ __device__ inline double gae_step(double G, int done, float r, float vk, float v
 }
 // lambda == 1 is not GAE: the launchers below then run the n-step kernels with the arguments they always had
 inline bool gae_on(double lambda) { return lambda != 1.0; }
-// dones: bit 0 = the transition t -> t+1 ended the episode; bit 1 = step t lies
-// past the end of this window (arl_truncate_window: no loss, no gradient).
-// pcoef = pi_loss_coef; keep_scale: keep_loss_scale_same (a3c.py:110-121)
-hipError_t launch_returns(const float* rewards, const uint8_t* dones, const float* v, const float* probs,
-                          const float* logp, const int32_t* act, int T, int n, int A, double gamma, float beta,
-                          float vcoef, int clip_reward, float* dlogits, float* dv, float* loss, hipStream_t s,
-                          int64_t* ctl_snap = nullptr, float pcoef = 1.f, int keep_scale = 0, double lambda = 1.0);
-// launch_returns + the heads' backward dh = dlogits Wpi + dv Wv (times
-// mask > 0 when mask is given) for hidden width HID, one launch (T <= 64)
-hipError_t launch_returns_heads(const float* rewards, const uint8_t* dones, const float* v, const float* probs,
-                                const float* logp, const int32_t* act, int T, int n, int A, double gamma, float beta,
-                                float vcoef, int clip_reward, float* dlogits, float* dv, float* loss, hipStream_t s,
-                                int64_t* ctl_snap, float pcoef, int keep_scale, const float* Wpi, const float* Wv,
-                                const float* mask, float* dh, double lambda = 1.0);
+// Arguments of the loss-gradient launches (policy.hip describes the kernels above its device-side forms of this
+// struct).  rewards / dones (T, n); v / probs / logp / act indexed (T + 1, n[, A]), row T = the bootstrap value.
+// dones: bit 0 = the transition t -> t+1 ended the episode; bit 1 = step t lies past the end of this window
+// (arl_truncate_window: no loss, no gradient).  pcoef = pi_loss_coef; keep_scale: keep_loss_scale_same
+// (a3c.py:110-121).  loss: nullable; ctl non-null: also snapshot the step counter (CTL_STEP_SNAP).
+// Callers name the fields they set (a net's window: window_returns_args below); no launcher has a default.
+struct ReturnsArgs {
+  const float* rewards;
+  const uint8_t* dones;
+  const float* v;
+  const float* probs;
+  const float* logp;
+  const int32_t* act;
+  int T, n, A;
+  double gamma;
+  float beta, vcoef, pcoef;
+  int clip_reward, keep_scale;
+  float* dlogits;
+  float* dv;
+  float* loss;
+  int64_t* ctl;
+};
+// the heads' backward that rides on a loss-gradient launch: dh = dlogits Wpi + dv Wv (times mask > 0 when mask is
+// given) for hidden width HID
+struct HeadsBwd {
+  const float *Wpi, *Wv, *mask;
+  float* dh;
+};
+// the two from a net's workspace, parameters and loss options (net.hip); FF: mask hfc, dh = dfc; LSTM: no mask, dh
+ReturnsArgs window_returns_args(const Net& net, double gamma, float beta, float vcoef, int clip_reward);
+HeadsBwd window_heads_bwd(const Net& net);
+// lambda: 1 = the n-step advantage, else GAE(lambda) (gae_on above)
+hipError_t launch_returns(const ReturnsArgs& ra, double lambda, hipStream_t s);
+// launch_returns + the heads' backward, one launch (T <= 64)
+hipError_t launch_returns_heads(const ReturnsArgs& ra, double lambda, const HeadsBwd& hb, hipStream_t s);
 // Clipped-surrogate (PPO) epochs on a window's rollout (arl_net_set_ppo has the definition; policy.hip).
 // launch_ppo_snapshot: lpo / adv / ret (T, n) of the window, from return_step / gae_step (lambda != 1) as the
-// returns launch forms them.  launch_ppo_lossgrad: the loss gradient of one epoch from the slots' current probs /
-// logp / v and the snapshot (the PPO form of launch_returns); launch_ppo_heads: + the heads' dh and the step
-// snapshot (the PPO form of launch_returns_heads, T <= 64).
-hipError_t launch_ppo_snapshot(const float* rewards, const uint8_t* dones, const float* v, const float* logp,
-                               const int32_t* act, int T, int n, int A, double gamma, double lambda, int clip_reward,
-                               float* lpo, float* adv, float* ret, hipStream_t s);
+// returns launch forms them; of ra it reads rewards, dones, v, logp, act, T, n, A, gamma and clip_reward.
+// launch_ppo_lossgrad: the loss gradient of one epoch from the slots' current probs / logp / v and the snapshot
+// (the PPO form of launch_returns); launch_ppo_heads: + the heads' dh (the PPO form of launch_returns_heads,
+// T <= 64).
+hipError_t launch_ppo_snapshot(const ReturnsArgs& ra, double lambda, float* lpo, float* adv, float* ret, hipStream_t s);
 struct PpoLossArgs {
-  const uint8_t* dones;
-  const float *v, *probs, *logp;
-  const int32_t* act;
+  ReturnsArgs r;                  // slots, shape, coefficients, outputs, ctl (rewards, gamma, clip_reward: not read)
   const float *lpo, *adv, *ret;   // the snapshot
-  int T, n, A;
   float lo, hi;                   // (float)(1.0 - eps_clip), (float)(1.0 + eps_clip)
-  float beta, vcoef, pcoef;
-  int keep_scale;
-  float *dlogits, *dv, *loss, *ratio;   // loss, ratio: nullable
+  float* ratio;                   // nullable
   // value clipping (arl_net_set_ppo_options): vold non-null picks the value-clipped form of the two launchers
   // below, ev = (float)vclip_eps
-  const float* vold = nullptr;
-  float ev = 0.f;
+  const float* vold;
+  float ev;
 };
 hipError_t launch_ppo_lossgrad(const PpoLossArgs& p, hipStream_t s);
-hipError_t launch_ppo_heads(const PpoLossArgs& p, int64_t* ctl_snap, const float* Wpi, const float* Wv,
-                            const float* mask, float* dh, hipStream_t s);
+hipError_t launch_ppo_heads(const PpoLossArgs& p, const HeadsBwd& hb, hipStream_t s);
 // The PPO options' own launches (arl_net_set_ppo_options has the definitions; policy.hip).
 // launch_ppo_vold: vold[t, e] = v[t, e] of a live sample, else 0.  launch_ppo_normalize_adv: the adv plane in
 // place, moments = (n_live, mean, std); one workgroup.  launch_ppo_epoch_stats: one epoch's record from the
-// arrays of p (dlogits / dv / loss and the coefficients are not read, ratio is); ctl non-null: the window
+// arrays of p (p.r's dlogits / dv / loss and coefficients are not read, ratio is); ctl non-null: the window
 // counter is read there instead of `window`; count non-null: rec is the aux block, the record goes to its ring
 // and the count is advanced, else rec is the record; one workgroup.
 constexpr int PPO_LOG = ARL_PPO_LOG, PPO_STAT_FIELDS = ARL_PPO_STAT_FIELDS, PPO_AUX_HEAD = 8;
@@ -666,10 +689,6 @@ hipError_t launch_ppo_epoch_stats(const PpoLossArgs& p, const int64_t* ctl, doub
 // launch_policy_fc of the bootstrap slot (no draw) + launch_returns_heads for the same n envs, one launch
 // (policy.hip policy_fc_returns_kernel; v(s_T) handed over in LDS); bit-identical to the two launches
 hipError_t launch_policy_fc_returns(const float* slab, int n, const float* fc_bias, float* hfc, const PolicyArgs& pa,
-                                    const float* rewards, const uint8_t* dones, const float* v, const float* probs,
-                                    const float* logp, const int32_t* act, int T, double gamma, float beta,
-                                    float vcoef, int clip_reward, float* dlogits, float* dv, float* loss,
-                                    int64_t* ctl_snap, float pcoef, int keep_scale, const float* mask, float* dh,
-                                    hipStream_t s, double lambda = 1.0);
+                                    const ReturnsArgs& ra, double lambda, const HeadsBwd& hb, hipStream_t s);
 
 }  // namespace arl

@@ -101,7 +101,6 @@ struct EpiConvMask {
     out[i] = mask[i] > 0.f ? v : 0.f;
   }
 };
-#define ARL_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return _e; } while (0)
 
 struct NPlans {
   int heads_w, fc_w, c3_w, c2_w, c1_w;
@@ -256,16 +255,12 @@ hipError_t nature_learn(Net& net, double gamma, float beta, float vcoef, int cli
   const int n = net.N, T = net.T, A = net.A, S = T * n;
   const NPlans pl = nature_plans(net);
   float* slab = net.at<float>(net.w_slab);
-  float* dl = net.at<float>(net.w_dlogits);
-  float* dv = net.at<float>(net.w_dv);
   // n-step returns + loss gradient (a3c.py:82-126)
-  net.win_gamma = gamma;
-  net.win_clip_reward = clip_reward;
-  net.win_lambda = net.gae_lambda;
-  ARL_TRY(launch_returns(net.at<float>(net.w_rewards), net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v),
-                         net.at<float>(net.w_probs), net.at<float>(net.w_logp), net.at<int32_t>(net.w_act), T, n, A,
-                         gamma, beta, vcoef, clip_reward, dl, dv, net.at<float>(net.w_loss), s,
-                         net.at<int64_t>(net.w_ctl), net.pi_coef, net.keep_scale, net.gae_lambda));
+  const ReturnsArgs ra = window_returns_args(net, gamma, beta, vcoef, clip_reward);
+  const float* dl = ra.dlogits;
+  const float* dv = ra.dv;
+  note_returns_launch(net, gamma, clip_reward);
+  ARL_TRY(launch_returns(ra, net.gae_lambda, s));
   const float* h = net.at<float>(net.w_hfc);
   // heads: weight grads (ones column = bias) and dfc = dh * (h > 0)
   ARL_TRY((launch_gemm<16, 64, 32, 1, 4, GS, GM>(HeadsGA{dl, dv, A}, OnesColB{h, NHID},

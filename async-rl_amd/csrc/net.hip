@@ -49,7 +49,6 @@ struct Conv2A {         // A(m, k) = a1[s][ic][2oy+ky][2ox+kx], m = s*81 + p, k 
     return a1[(int64_t)s * A1 + ic * C1_P + (2 * oy + ky) * 20 + 2 * ox + kx];
   }
 };
-#define ARL_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return _e; } while (0)
 
 // Where the LSTM step's FC split-K partials are reduced: in the gate kernel's staging (XRED) for
 // launches under 512 envs, by the FC's last-arriver ticket for 512 and more (fc_fwd_big_kernel's
@@ -323,16 +322,106 @@ static hipError_t fc_forward(const Net& net, int n, const float* a2, float* hfc,
                        hfc, s);
 }
 
-// policy / value heads of window slot t (rows n of env 0..n-1) reading h
-static PolicyArgs slot_policy_args(const Net& net, int t, int mode) {
+// policy / value heads of window slot t (rows of env e0, e0 + 1, ..) reading h
+static PolicyArgs slot_policy_args(const Net& net, int t, int mode, int e0 = 0) {
   const float* P = net.p;
   const int A = net.A;
-  const int64_t o = (int64_t)t * net.N;
+  const int64_t o = (int64_t)t * net.N + e0;
   return make_policy_args(P + net.o_piW, P + net.o_pib, P + net.o_vW, P + net.o_vb, A, net.seed,
-                          net.at<int64_t>(net.w_ctl), t, net.env_offset, mode, net.at<float>(net.w_logits) + o * A,
+                          net.at<int64_t>(net.w_ctl), t, net.env_offset + e0, mode, net.at<float>(net.w_logits) + o * A,
                           net.at<float>(net.w_probs) + o * A, net.at<float>(net.w_logp) + o * A,
                           net.at<float>(net.w_v) + o, net.at<float>(net.w_ent) + o, net.at<int32_t>(net.w_act) + o,
                           net.at<float>(net.w_logpa) + o);
+}
+
+// ---- the launches a window and its isolated stages (net_stage) share, each with its argument list here only
+
+// conv1 + conv2 of window slot t from the frame ring for envs [e0, e0 + ne) (ne < 0: all).  bwd_outputs: also a1
+// and the a2 > 0 bits, which only the backward reads (the ring-frame kernels skip those stores: 25.6 KB an env)
+static hipError_t conv_fwd_slot(const Net& net, int t, int e0, int ne, bool bwd_outputs, hipStream_t s) {
+  const float* P = net.p;
+  const int n = net.N;
+  return launch_conv_fwd(net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid), net.at<int64_t>(net.w_ctl), n,
+                         net.dR, t, P + net.o_c1W, P + net.o_c1b, P + net.o_c2W, P + net.o_c2b,
+                         bwd_outputs ? net.at<float>(net.w_a1) + (int64_t)t * n * A1 : nullptr,
+                         net.at<float>(net.w_a2) + (int64_t)t * n * A2, s, net.layout, e0, ne,
+                         bwd_outputs ? a2_mask(net, t) : nullptr);
+}
+
+// The LSTM step of slot t for envs [e0, e0 + ne): the gates with the cell in their epilogue.  The FC's split-K
+// partials are reduced + bias + relu in the gate kernel's staging (XRED) or were by the FC's last-arriver ticket
+// (lstm_xred of the launch's env count); h goes to row t + 1 of hbuf
+static hipError_t lstm_gates_step(const Net& net, int t, int e0, int ne, hipStream_t s) {
+  const float* P = net.p;
+  const int n = net.N;
+  const bool xred = lstm_xred(ne);
+  const int64_t r0 = (int64_t)t * n + e0;
+  float* hfc = net.at<float>(net.w_hfc) + r0 * HID;
+  return launch_lstm_gates(xred ? nullptr : hfc, net.at<float>(net.w_hbuf) + r0 * HID,
+                           net.at<uint8_t>(net.w_reset) + r0, P + net.o_luW, P + net.o_llW, P + net.o_lub,
+                           net.at<float>(net.w_gates) + r0 * GATES, net.at<float>(net.w_cbuf) + r0 * HID,
+                           net.at<float>(net.w_cbuf) + (r0 + n) * HID, net.at<float>(net.w_hbuf) + (r0 + n) * HID, ne,
+                           true, s, xred ? net.at<float>(net.w_slab) + (int64_t)FC_SPLIT * e0 * HID : nullptr,
+                           xred ? P + net.o_fcb : nullptr, xred ? hfc : nullptr);
+}
+
+// One BPTT step t -> t - 1 (t >= 1): dh_{t-1} = (dG_t Wl) * (no reset at t) and step t - 1's cell in one launch
+// (lstm.hip)
+static hipError_t lstm_bptt_step(const Net& net, int t, hipStream_t s) {
+  const int n = net.N;
+  const int64_t o = (int64_t)t * n, op = o - n;
+  float* dG = net.at<float>(net.w_dG);
+  const float* cbuf = net.at<float>(net.w_cbuf);
+  const uint8_t* rs = net.at<uint8_t>(net.w_reset);
+  return launch_lstm_bptt(dG + o * GATES, net.p + net.o_llW, rs + o, net.at<float>(net.w_gates) + op * GATES,
+                          cbuf + (op + n) * HID, cbuf + op * HID, rs + op, net.at<float>(net.w_dh) + op * HID,
+                          net.at<float>(net.w_dcn), dG + op * GATES, net.at<float>(net.w_dhn), n, true, s);
+}
+
+// the fused conv backward per sample (conv_bwd.hip), its slabs left for the reduce
+static hipError_t conv_bwd_slabs(const Net& net, hipStream_t s) {
+  return launch_conv_bwd(net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid), net.at<int64_t>(net.w_ctl),
+                         net.dN, net.dR, net.T * net.N, net.at<float>(net.w_a1), net.at<float>(net.w_da2),
+                         net.p + net.o_c2W, net.at<float>(net.w_slab), net.g + net.o_c2W, net.g + net.o_c2b,
+                         net.g + net.o_c1W, net.g + net.o_c1b, s, /*reduce=*/false, net.layout);
+}
+// and that reduce, with the folded clip norm's partials when nf.parts is set
+static hipError_t conv_bwd_reduce(const Net& net, const NormFold& nf, hipStream_t s) {
+  return launch_conv_reduce(net.at<float>(net.w_slab), net.T * net.N, net.g + net.o_c2W, net.g + net.o_c2b,
+                            net.g + net.o_c1W, net.g + net.o_c1b, s, net.layout, nf);
+}
+
+// ---- the loss-gradient launches' arguments from the net (declared in arl_internal.hpp: nature.hip shares them)
+
+ReturnsArgs window_returns_args(const Net& net, double gamma, float beta, float vcoef, int clip_reward) {
+  ReturnsArgs ra{};
+  ra.rewards = net.at<float>(net.w_rewards); ra.dones = net.at<uint8_t>(net.w_dones); ra.v = net.at<float>(net.w_v);
+  ra.probs = net.at<float>(net.w_probs); ra.logp = net.at<float>(net.w_logp); ra.act = net.at<int32_t>(net.w_act);
+  ra.T = net.T; ra.n = net.N; ra.A = net.A;
+  ra.gamma = gamma; ra.clip_reward = clip_reward;
+  ra.beta = beta; ra.vcoef = vcoef; ra.pcoef = net.pi_coef; ra.keep_scale = net.keep_scale;
+  ra.dlogits = net.at<float>(net.w_dlogits); ra.dv = net.at<float>(net.w_dv); ra.loss = net.at<float>(net.w_loss);
+  ra.ctl = net.at<int64_t>(net.w_ctl);   // every window launch snapshots the step counter
+  return ra;
+}
+
+HeadsBwd window_heads_bwd(const Net& net) {
+  const bool L = net.arch == ARCH_LSTM;
+  return HeadsBwd{net.p + net.o_piW, net.p + net.o_vW, L ? nullptr : net.at<float>(net.w_hfc),
+                  L ? net.at<float>(net.w_dh) : net.at<float>(net.w_dfc)};
+}
+
+// one PPO epoch's arguments: the window's slots (shared with window_returns_args), the snapshot's planes and the
+// options as they stand
+static PpoLossArgs window_ppo_args(const Net& net, float beta, float vcoef) {
+  const int64_t S = (int64_t)net.T * net.N;
+  float* snap = net.ppo_snap;
+  PpoLossArgs p{};
+  p.r = window_returns_args(net, 0.0, beta, vcoef, 0);
+  p.lpo = snap; p.adv = snap + S; p.ret = snap + 2 * S; p.ratio = snap + 3 * S;
+  p.lo = net.ppo_lo; p.hi = net.ppo_hi;
+  p.vold = net.ppo_vold; p.ev = net.ppo_ev;   // (vold null: the form without value clipping)
+  return p;
 }
 
 // One lockstep step (conv -> fc [-> LSTM] -> policy) for envs [e0, e0 + ne)
@@ -348,7 +437,7 @@ hipError_t net_act(Net& net, int t, int mode, hipStream_t s, int e0, int ne) {
     if (e0 != 0 || ne != net.N || mode > 2) return hipErrorInvalidValue;
     return nature_act(net, t, mode, s);
   }
-  const int n = net.N, A = net.A;
+  const int n = net.N;
   const int part = mode & (ACT_CONV_ONLY | ACT_AFTER_CONV);
   mode &= 3;
   // an env range forks from the caller's stream: stale planes rebuilt on one chain's stream would race
@@ -358,52 +447,33 @@ hipError_t net_act(Net& net, int t, int mode, hipStream_t s, int e0, int ne) {
   // a fused bootstrap launch whose learn never followed (a dropped window) must not make a later
   // window's learn skip its returns: any act of a window's step t < T starts a new window
   if (t < net.T) net.returns_done = false;
-  // the bootstrap slot T feeds only the FC / heads forward: no backward reads its a1 or a2 mask
-  // (the ring-frame conv kernels skip those stores: 25.6 KB an env)
-  float* a1 = net.at<float>(net.w_a1) + (int64_t)t * n * A1;
-  float* a1_bwd = t < net.T ? a1 : nullptr;
-  uint32_t* mask_bwd = t < net.T ? a2_mask(net, t) : nullptr;
   float* a2 = net.at<float>(net.w_a2) + (int64_t)t * n * A2;
   float* hfc = net.at<float>(net.w_hfc) + ((int64_t)t * n + e0) * HID;
   const float* P = net.p;
   if (!(part & ACT_AFTER_CONV) && net.states) {
     if (e0 != 0 || ne != n) return hipErrorInvalidValue;   // one launch over all envs
-    ARL_TRY(states_conv_fwd(net, t, a1, a2, s));
+    ARL_TRY(states_conv_fwd(net, t, net.at<float>(net.w_a1) + (int64_t)t * n * A1, a2, s));
     ARL_TRY(stamp(net, STAGE_CONV_FWD, s));
   } else if (!(part & ACT_AFTER_CONV)) {
-    ARL_TRY(launch_conv_fwd(net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid),
-                            net.at<int64_t>(net.w_ctl), n, net.dR, t, P + net.o_c1W, P + net.o_c1b, P + net.o_c2W,
-                            P + net.o_c2b, a1_bwd, a2, s, net.layout, e0, ne, mask_bwd));
+    // the bootstrap slot T feeds only the FC / heads forward: no backward reads its a1 or a2 mask
+    ARL_TRY(conv_fwd_slot(net, t, e0, ne, t < net.T, s));
     ARL_TRY(stamp(net, STAGE_CONV_FWD, s));
   }
   if (part & ACT_CONV_ONLY) return hipSuccess;
-  const int64_t o = (int64_t)t * n + e0;
   float* fc_slab = net.at<float>(net.w_slab) + (int64_t)FC_SPLIT * e0 * HID;
-  const PolicyArgs pa = make_policy_args(P + net.o_piW, P + net.o_pib, P + net.o_vW, P + net.o_vb, A, net.seed,
-                                         net.at<int64_t>(net.w_ctl), t, net.env_offset + e0, t < net.T ? mode : 0,
-                                         net.at<float>(net.w_logits) + o * A, net.at<float>(net.w_probs) + o * A,
-                                         net.at<float>(net.w_logp) + o * A, net.at<float>(net.w_v) + o,
-                                         net.at<float>(net.w_ent) + o, net.at<int32_t>(net.w_act) + o,
-                                         net.at<float>(net.w_logpa) + o);
+  const PolicyArgs pa = slot_policy_args(net, t, t < net.T ? mode : 0, e0);
   if (net.arch != ARCH_LSTM) {   // FF: split-K partials, reduce + relu + heads in one policy_fc launch
     ARL_TRY(launch_fc_fwd(a2 + (int64_t)e0 * A2, ne, fc_planes(net), P + net.o_fcb, fc_slab, nullptr, nullptr, s));
     ARL_TRY(stamp(net, STAGE_FC_FWD, s));
     // + the learner's returns (one env group); not while the update runs as PPO epochs (arl_ppo_begin / arl_ppo_learn)
     if (t == net.T && net.fuse_returns && net.ppo_snap == nullptr && e0 == 0 && ne == n) {
       const Net::ReturnsCfg& r = net.ret;
-      ARL_TRY(launch_policy_fc_returns(fc_slab, ne, P + net.o_fcb, hfc, pa, net.at<float>(net.w_rewards),
-                                       net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v),
-                                       net.at<float>(net.w_probs), net.at<float>(net.w_logp),
-                                       net.at<int32_t>(net.w_act), net.T, r.gamma, r.beta, r.vcoef, r.clip_reward,
-                                       net.at<float>(net.w_dlogits), net.at<float>(net.w_dv),
-                                       net.at<float>(net.w_loss), net.at<int64_t>(net.w_ctl), net.pi_coef,
-                                       net.keep_scale, net.at<float>(net.w_hfc), net.at<float>(net.w_dfc), s,
-                                       net.gae_lambda));
+      ARL_TRY(launch_policy_fc_returns(fc_slab, ne, P + net.o_fcb, hfc, pa,
+                                       window_returns_args(net, r.gamma, r.beta, r.vcoef, r.clip_reward),
+                                       net.gae_lambda, window_heads_bwd(net), s));
       net.returns_done = true;
       net.norm_ready = false;   // a new gradient (as LEARN_RETURNS)
-      net.win_gamma = r.gamma;
-      net.win_clip_reward = r.clip_reward;
-      net.win_lambda = net.gae_lambda;
+      note_returns_launch(net, r.gamma, r.clip_reward);
       return stamp(net, STAGE_POLICY, s);
     }
     ARL_TRY(launch_policy_fc(fc_slab, ne, P + net.o_fcb, hfc, pa, s));
@@ -415,15 +485,9 @@ hipError_t net_act(Net& net, int t, int mode, hipStream_t s, int e0, int ne) {
   ARL_TRY(launch_fc_fwd(a2 + (int64_t)e0 * A2, ne, fc_planes(net), P + net.o_fcb, fc_slab,
                         xred ? nullptr : net.at<int>(net.w_tick) + fc_fwd_tiles(e0), xred ? nullptr : hfc, s));
   ARL_TRY(stamp(net, STAGE_FC_FWD, s));
-  const int64_t r0 = (int64_t)t * n + e0;
-  float* hout = net.at<float>(net.w_hbuf) + (r0 + n) * HID;
-  ARL_TRY(launch_lstm_gates(xred ? nullptr : hfc, net.at<float>(net.w_hbuf) + r0 * HID,
-                            net.at<uint8_t>(net.w_reset) + r0, P + net.o_luW, P + net.o_llW, P + net.o_lub,
-                            net.at<float>(net.w_gates) + r0 * GATES, net.at<float>(net.w_cbuf) + r0 * HID,
-                            net.at<float>(net.w_cbuf) + (r0 + n) * HID, hout, ne, true, s, xred ? fc_slab : nullptr,
-                            xred ? P + net.o_fcb : nullptr, xred ? hfc : nullptr));
+  ARL_TRY(lstm_gates_step(net, t, e0, ne, s));
   ARL_TRY(stamp(net, STAGE_LSTM_GATES, s));
-  ARL_TRY(launch_policy_args(hout, ne, pa, s, HID));
+  ARL_TRY(launch_policy_args(net.at<float>(net.w_hbuf) + ((int64_t)(t + 1) * n + e0) * HID, ne, pa, s, HID));
   return stamp(net, STAGE_POLICY, s);
 }
 
@@ -502,15 +566,9 @@ static NormFold norm_fold_args(const Net& net) {
 // the fused conv backward (per-sample slabs) and its slab reduce (with the folded clip norm's
 // partials when nf.parts is set): the learner's last part
 static hipError_t conv_backward(Net& net, hipStream_t s, const NormFold& nf) {
-  const int S = net.T * net.N;
-  float* slab = net.at<float>(net.w_slab);
-  ARL_TRY(launch_conv_bwd(net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid), net.at<int64_t>(net.w_ctl),
-                          net.dN, net.dR, S, net.at<float>(net.w_a1), net.at<float>(net.w_da2), net.p + net.o_c2W, slab,
-                          net.g + net.o_c2W, net.g + net.o_c2b, net.g + net.o_c1W, net.g + net.o_c1b, s,
-                          /*reduce=*/false, net.layout));
+  ARL_TRY(conv_bwd_slabs(net, s));
   ARL_TRY(stamp(net, STAGE_CONV_BWD, s));
-  ARL_TRY(launch_conv_reduce(slab, S, net.g + net.o_c2W, net.g + net.o_c2b, net.g + net.o_c1W, net.g + net.o_c1b, s,
-                             net.layout, nf));
+  ARL_TRY(conv_bwd_reduce(net, nf, s));
   return stamp(net, STAGE_CONV_REDUCE, s);
 }
 
@@ -533,24 +591,21 @@ hipError_t net_learn(Net& net, double gamma, float beta, float vcoef, int clip_r
 hipError_t net_ppo_begin(Net& net, double gamma, int clip_reward, hipStream_t s) {
   const int64_t S = (int64_t)net.T * net.N;
   float* snap = net.ppo_snap;
+  const ReturnsArgs ra = window_returns_args(net, gamma, 0.f, 0.f, clip_reward);
   net.returns_done = false;
-  net.win_gamma = gamma;   // as a returns launch: the window statistics repeat the snapshot's returns
-  net.win_clip_reward = clip_reward;
-  net.win_lambda = net.gae_lambda;
-  ARL_TRY(launch_ppo_snapshot(net.at<float>(net.w_rewards), net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v),
-                              net.at<float>(net.w_logp), net.at<int32_t>(net.w_act), net.T, net.N, net.A, gamma,
-                              net.gae_lambda, clip_reward, snap, snap + S, snap + 2 * S, s));
+  note_returns_launch(net, gamma, clip_reward);   // the window statistics repeat the snapshot's returns
+  ARL_TRY(launch_ppo_snapshot(ra, net.gae_lambda, snap, snap + S, snap + 2 * S, s));
   net.ppo_begun = true;
   net.ppo_epoch = 0;
   ARL_TRY(stamp(net, STAGE_OTHER, s));
   // arl_net_set_ppo_options: v_old of the window, then the adv plane normalised in place (each with a stamp
   // of its own; with the options off nothing more is launched)
   if (net.ppo_vold != nullptr) {
-    ARL_TRY(launch_ppo_vold(net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v), net.ppo_vold, net.T, net.N, s));
+    ARL_TRY(launch_ppo_vold(ra.dones, ra.v, net.ppo_vold, net.T, net.N, s));
     ARL_TRY(stamp(net, STAGE_OTHER, s));
   }
   if (net.ppo_norm_adv) {
-    ARL_TRY(launch_ppo_normalize_adv(net.at<uint8_t>(net.w_dones), snap + S, net.T, net.N, net.ppo_aux + 1, s));
+    ARL_TRY(launch_ppo_normalize_adv(ra.dones, snap + S, net.T, net.N, net.ppo_aux + 1, s));
     ARL_TRY(stamp(net, STAGE_OTHER, s));
   }
   return hipSuccess;
@@ -559,18 +614,10 @@ hipError_t net_ppo_begin(Net& net, double gamma, int clip_reward, hipStream_t s)
 // One epoch's gradient: the PPO loss gradient + heads dh (it also snapshots the step counter, as the returns
 // launch it stands in for), then the trunk and conv parts unchanged
 hipError_t net_ppo_learn(Net& net, float beta, float vcoef, hipStream_t s) {
-  const int64_t S = (int64_t)net.T * net.N;
-  float* snap = net.ppo_snap;
-  PpoLossArgs p{net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v), net.at<float>(net.w_probs),
-                net.at<float>(net.w_logp), net.at<int32_t>(net.w_act), snap, snap + S, snap + 2 * S, net.T, net.N,
-                net.A, net.ppo_lo, net.ppo_hi, beta, vcoef, net.pi_coef, net.keep_scale,
-                net.at<float>(net.w_dlogits), net.at<float>(net.w_dv), net.at<float>(net.w_loss), snap + 3 * S};
-  p.vold = net.ppo_vold;   // (null: the form without value clipping, the launch it always was)
-  p.ev = net.ppo_ev;
+  const PpoLossArgs p = window_ppo_args(net, beta, vcoef);
   net.norm_ready = false;   // a new gradient, no folded norm
   net.returns_done = false;
-  ARL_TRY(launch_ppo_heads(p, net.at<int64_t>(net.w_ctl), net.p + net.o_piW, net.p + net.o_vW,
-                           net.at<float>(net.w_hfc), net.at<float>(net.w_dfc), s));
+  ARL_TRY(launch_ppo_heads(p, window_heads_bwd(net), s));
   ARL_TRY(stamp(net, STAGE_RETURNS, s));
   net.ppo_epoch += 1;
   if (net.ppo_aux != nullptr) {   // the epoch's record, while its ratio plane and the slots' log_probs / v stand
@@ -609,9 +656,7 @@ static hipError_t fc_backward(Net& net, hipStream_t s) {
 // One part of the NIPS learner (LEARN_* in arl_internal.hpp), in order on one stream
 hipError_t net_learn_part(Net& net, int part, double gamma, float beta, float vcoef, int clip_reward, hipStream_t s) {
   if (net.arch == ARCH_FF_NATURE) return hipErrorInvalidValue;
-  const int n = net.N, T = net.T, A = net.A;
-  const float* P = net.p;
-  const bool L = net.arch == ARCH_LSTM;
+  const int n = net.N, T = net.T;
   if (part == LEARN_RETURNS) {
     if (net.returns_done) {   // the bootstrap policy launch ran it (net_act, fuse_returns)
       net.returns_done = false;
@@ -620,16 +665,9 @@ hipError_t net_learn_part(Net& net, int part, double gamma, float beta, float vc
     // n-step returns + loss gradient wrt logits / v (a3c.py:82-126); also snapshots the step counter for
     // the optimizer's fused advance and, in the same launch, the heads' backward dh (FF: dfc = dh * (hfc > 0))
     net.norm_ready = false;   // a new gradient: no folded norm until net_learn's reduce
-    net.win_gamma = gamma;
-    net.win_clip_reward = clip_reward;
-    net.win_lambda = net.gae_lambda;
-    ARL_TRY(launch_returns_heads(net.at<float>(net.w_rewards), net.at<uint8_t>(net.w_dones), net.at<float>(net.w_v),
-                                 net.at<float>(net.w_probs), net.at<float>(net.w_logp), net.at<int32_t>(net.w_act), T,
-                                 n, A, gamma, beta, vcoef, clip_reward, net.at<float>(net.w_dlogits),
-                                 net.at<float>(net.w_dv), net.at<float>(net.w_loss), s, net.at<int64_t>(net.w_ctl),
-                                 net.pi_coef, net.keep_scale, P + net.o_piW, P + net.o_vW,
-                                 L ? nullptr : net.at<float>(net.w_hfc),
-                                 L ? net.at<float>(net.w_dh) : net.at<float>(net.w_dfc), net.gae_lambda));
+    note_returns_launch(net, gamma, clip_reward);
+    ARL_TRY(launch_returns_heads(window_returns_args(net, gamma, beta, vcoef, clip_reward), net.gae_lambda,
+                                 window_heads_bwd(net), s));
     return stamp(net, STAGE_RETURNS, s);
   }
   if (part == LEARN_CONV) {
@@ -643,26 +681,19 @@ hipError_t net_learn_part(Net& net, int part, double gamma, float beta, float vc
   }
   if (part != LEARN_TRUNK) return hipErrorInvalidValue;
   // LSTM: truncated BPTT over the window (a3c.py:144), then the gate weight gradients and dfc
-  if (L) {
-    const float* gates = net.at<float>(net.w_gates);
+  if (net.arch == ARCH_LSTM) {
     const float* cbuf = net.at<float>(net.w_cbuf);
-    const uint8_t* rs = net.at<uint8_t>(net.w_reset);
-    float* dG = net.at<float>(net.w_dG);
-    float* dhn = net.at<float>(net.w_dhn);
-    float* dcn = net.at<float>(net.w_dcn);
-    const float* dH = net.at<float>(net.w_dh);
     const int64_t cnt = (int64_t)n * HID;
-    // step T-1's cell, then per step t: dh_{t-1} = (dG_t Wl) * (no reset at t) and step t-1's cell in one
-    // launch (lstm.hip)
+    // step T-1's cell, then one BPTT step per t = T-1 .. 1
     const int64_t oT = (int64_t)(T - 1) * n;
-    hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, gates + oT * GATES,
-                       cbuf + (oT + n) * HID, cbuf + oT * HID, rs + oT, dH + oT * HID, dhn, dcn, dG + oT * GATES, 1, cnt);
+    hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s,
+                       net.at<float>(net.w_gates) + oT * GATES, cbuf + (oT + n) * HID, cbuf + oT * HID,
+                       net.at<uint8_t>(net.w_reset) + oT, net.at<float>(net.w_dh) + oT * HID, net.at<float>(net.w_dhn),
+                       net.at<float>(net.w_dcn), net.at<float>(net.w_dG) + oT * GATES, 1, cnt);
     ARL_TRY(hipGetLastError());
     ARL_TRY(stamp(net, STAGE_LSTM_CELL, s));
     for (int t = T - 1; t > 0; --t) {
-      const int64_t o = (int64_t)t * n, op = o - n;
-      ARL_TRY(launch_lstm_bptt(dG + o * GATES, P + net.o_llW, rs + o, gates + op * GATES, cbuf + (op + n) * HID,
-                               cbuf + op * HID, rs + op, dH + op * HID, dcn, dG + op * GATES, dhn, n, true, s));
+      ARL_TRY(lstm_bptt_step(net, t, s));
       ARL_TRY(stamp(net, STAGE_LSTM_BPTT, s));
     }
     ARL_TRY(lstm_wgrad(net, s));
@@ -678,9 +709,8 @@ hipError_t net_learn_part(Net& net, int part, double gamma, float beta, float vc
 // the same launches the window makes, isolated for timing.
 hipError_t net_stage(Net& net, int stage, int t, hipStream_t s) {
   if (net.arch == ARCH_FF_NATURE) return nature_stage(net, stage, t, s);
-  const int n = net.N, S = net.T * n;
+  const int n = net.N;
   const float* P = net.p;
-  float* G = net.g;
   float* slab = net.at<float>(net.w_slab);
   float* a2 = net.at<float>(net.w_a2);
   float* hfc = net.at<float>(net.w_hfc);
@@ -690,11 +720,8 @@ hipError_t net_stage(Net& net, int stage, int t, hipStream_t s) {
     return stage == STAGE_CONV_BWD ? states_conv_bwd(net, s) : hipSuccess;   // (no separate slab reduce)
   }
   switch (stage) {
-    case STAGE_CONV_FWD:
-      return launch_conv_fwd(net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid),
-                             net.at<int64_t>(net.w_ctl), n, net.dR, t, P + net.o_c1W, P + net.o_c1b, P + net.o_c2W,
-                             P + net.o_c2b, net.at<float>(net.w_a1) + (int64_t)t * n * A1, a2 + (int64_t)t * n * A2,
-                             s, net.layout, 0, -1, a2_mask(net, t));
+    case STAGE_CONV_FWD:   // all envs, with the backward's outputs whatever the slot
+      return conv_fwd_slot(net, t, 0, -1, true, s);
     case STAGE_FC_FWD:   // as in net_act: FF (and the LSTM's XRED gate kernel) reduce the partials downstream
       ARL_TRY(ensure_fc_planes(net, s));
       if (net.arch != ARCH_LSTM || lstm_xred(n))
@@ -709,39 +736,19 @@ hipError_t net_stage(Net& net, int stage, int t, hipStream_t s) {
     case STAGE_FC_BWD:   // with the heads' weight gradients (job C), as in LEARN_TRUNK
       return fc_backward(net, s);
     case STAGE_CONV_BWD:
-      return launch_conv_bwd(net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid),
-                             net.at<int64_t>(net.w_ctl), net.dN, net.dR, S, net.at<float>(net.w_a1),
-                             net.at<float>(net.w_da2), P + net.o_c2W, slab, G + net.o_c2W, G + net.o_c2b,
-                             G + net.o_c1W, G + net.o_c1b, s, /*reduce=*/false, net.layout);
+      return conv_bwd_slabs(net, s);
     case STAGE_RETURNS:   // the LEARN_RETURNS launch (returns + loss gradient + heads dh), default coefficients
       return net_learn_part(net, LEARN_RETURNS, 0.99, 0.01f, 0.5f, 1, s);
     case STAGE_CONV_REDUCE:
-      return launch_conv_reduce(slab, S, G + net.o_c2W, G + net.o_c2b, G + net.o_c1W, G + net.o_c1b, s, net.layout,
-                                norm_fold_args(net));   // as arl_learn launches it
+      return conv_bwd_reduce(net, norm_fold_args(net), s);   // as arl_learn launches it
     case STAGE_GRAD_SQNORM:
       return launch_grad_sqnorm(net.g, net.param_floats, net.at<double>(net.w_norm), net.norm_blocks, s);
-    case STAGE_LSTM_GATES: {   // as net_act's LSTM step over all envs
+    case STAGE_LSTM_GATES:   // as net_act's LSTM step over all envs
       if (net.arch != ARCH_LSTM) return hipErrorInvalidValue;
-      const int64_t r0 = (int64_t)t * n;
-      const bool xred = lstm_xred(n);
-      return launch_lstm_gates(xred ? nullptr : hfc + r0 * HID, net.at<float>(net.w_hbuf) + r0 * HID,
-                               net.at<uint8_t>(net.w_reset) + r0, P + net.o_luW, P + net.o_llW, P + net.o_lub,
-                               net.at<float>(net.w_gates) + r0 * GATES, net.at<float>(net.w_cbuf) + r0 * HID,
-                               net.at<float>(net.w_cbuf) + (r0 + n) * HID, net.at<float>(net.w_hbuf) + (r0 + n) * HID,
-                               n, true, s, xred ? slab : nullptr, xred ? P + net.o_fcb : nullptr,
-                               xred ? hfc + r0 * HID : nullptr);
-    }
-    case STAGE_LSTM_BPTT: {    // the BPTT step t -> t - 1 (t = T - 1 when t is 0)
+      return lstm_gates_step(net, t, 0, n, s);
+    case STAGE_LSTM_BPTT:    // the BPTT step t -> t - 1 (t = T - 1 when t is 0)
       if (net.arch != ARCH_LSTM || net.T < 2) return hipErrorInvalidValue;
-      const int tt = t > 0 && t < net.T ? t : net.T - 1;
-      const int64_t o = (int64_t)tt * n, op = o - n;
-      float* dG = net.at<float>(net.w_dG);
-      const float* cbuf = net.at<float>(net.w_cbuf);
-      const uint8_t* rs = net.at<uint8_t>(net.w_reset);
-      return launch_lstm_bptt(dG + o * GATES, P + net.o_llW, rs + o, net.at<float>(net.w_gates) + op * GATES,
-                              cbuf + (op + n) * HID, cbuf + op * HID, rs + op, net.at<float>(net.w_dh) + op * HID,
-                              net.at<float>(net.w_dcn), dG + op * GATES, net.at<float>(net.w_dhn), n, true, s);
-    }
+      return lstm_bptt_step(net, t > 0 && t < net.T ? t : net.T - 1, s);
     case STAGE_LSTM_WGRAD:
       if (net.arch != ARCH_LSTM) return hipErrorInvalidValue;
       return lstm_wgrad(net, s);

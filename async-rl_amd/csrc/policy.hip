@@ -136,22 +136,8 @@ hipError_t launch_policy(const float* h, int64_t n, const float* Wpi, const floa
 // summed in the reference's order (t = T-1 .. 0) through LDS.  ctl != null:
 // also snapshot the step counter (CTL_STEP_SNAP) for the optimizer's fused
 // advance.  Block = EB envs x T steps (EB = 256 / T), env fastest.
-struct ReturnsArgs {
-  const float* rewards;
-  const uint8_t* dones;
-  const float* v;
-  const float* probs;
-  const float* logp;
-  const int32_t* act;
-  int T, n, A;
-  double gamma;
-  float beta, vcoef, pcoef;
-  int clip_reward, keep_scale;
-  float* dlogits;
-  float* dv;
-  float* loss;
-  int64_t* ctl;
-};
+// The arguments: ReturnsArgs (arl_internal.hpp; it stays arl::ReturnsArgs with its fields in that order -- the
+// name is part of the kernels' mangled names and the layout is what they read) and the forms derived from it here.
 // The launch's form G, compile time: the n-step advantage, the GAE one, or a clipped-surrogate (PPO) epoch on a
 // window's snapshot (arl_net_set_ppo).  false / true in a template argument list are RF_NSTEP / RF_GAE.
 // (ints, not an unnamed enum: the forms appear in the kernels' mangled names through ReturnsArgsT, and an unnamed
@@ -619,6 +605,9 @@ policy_fc_returns_kernel(const float* __restrict__ slab, int n, const float* __r
   rh_finish<AM, RB, G>(ra, mask, dh, e, st, lpi, lv, sdl, w);
 }
 
+// ---------------------------------------------------------------- the loss-gradient launches
+// Each launcher picks its form G once (RF_NSTEP / RF_GAE by gae_on(lambda), RF_PPO / RF_PPO_VC by vold) and hands
+// that form's arguments to its kernel's launch template below.
 // gl = gamma * lambda: one f64 product, formed here on the host
 static ReturnsArgsGae gae_args(const ReturnsArgs& ra, double lambda) {
   ReturnsArgsGae rg;
@@ -627,120 +616,106 @@ static ReturnsArgsGae gae_args(const ReturnsArgs& ra, double lambda) {
   return rg;
 }
 
-hipError_t launch_returns(const float* rewards, const uint8_t* dones, const float* v, const float* probs,
-                          const float* logp, const int32_t* act, int T, int n, int A, double gamma, float beta,
-                          float vcoef, int clip_reward, float* dlogits, float* dv, float* loss, hipStream_t s,
-                          int64_t* ctl_snap, float pcoef, int keep_scale, double lambda) {
-  if (n <= 0) return hipSuccess;
-  if (T < 1 || T > 256) return hipErrorInvalidValue;
-  const int EB = 256 / T;
-  const ReturnsArgs ra{rewards, dones, v, probs, logp, act, T, n, A, gamma, beta, vcoef, pcoef, clip_reward,
-                       keep_scale, dlogits, dv, loss, ctl_snap};
-  if (gae_on(lambda))
-    hipLaunchKernelGGL(returns_kernel<true>, dim3((n + EB - 1) / EB), dim3(256), 0, s, gae_args(ra, lambda));
-  else
-    hipLaunchKernelGGL(returns_kernel<false>, dim3((n + EB - 1) / EB), dim3(256), 0, s, ra);
-  return hipGetLastError();
-}
-
-hipError_t launch_returns_heads(const float* rewards, const uint8_t* dones, const float* v, const float* probs,
-                                const float* logp, const int32_t* act, int T, int n, int A, double gamma, float beta,
-                                float vcoef, int clip_reward, float* dlogits, float* dv, float* loss, hipStream_t s,
-                                int64_t* ctl_snap, float pcoef, int keep_scale, const float* Wpi, const float* Wv,
-                                const float* mask, float* dh, double lambda) {
-  if (n <= 0) return hipSuccess;
-  if (T < 1 || T > 64 || A < 1 || A > MAXA) return hipErrorInvalidValue;
-  const ReturnsArgs ra{rewards, dones, v, probs, logp, act, T, n, A, gamma, beta, vcoef, pcoef, clip_reward,
-                       keep_scale, dlogits, dv, loss, ctl_snap};
-  const dim3 grid(n), blk(256);
-  if (gae_on(lambda)) {
-    const ReturnsArgsGae rg = gae_args(ra, lambda);
-    if (T > 8) hipLaunchKernelGGL((returns_heads_kernel<MAXA, 32, true>), grid, blk, 0, s, rg, Wpi, Wv, mask, dh);
-    else if (A <= 4) hipLaunchKernelGGL((returns_heads_kernel<4, 8, true>), grid, blk, 0, s, rg, Wpi, Wv, mask, dh);
-    else if (A <= 8) hipLaunchKernelGGL((returns_heads_kernel<8, 8, true>), grid, blk, 0, s, rg, Wpi, Wv, mask, dh);
-    else hipLaunchKernelGGL((returns_heads_kernel<MAXA, 8, true>), grid, blk, 0, s, rg, Wpi, Wv, mask, dh);
-    return hipGetLastError();
-  }
-  if (T <= 8) {
-    if (A <= 4) hipLaunchKernelGGL((returns_heads_kernel<4, 8>), grid, blk, 0, s, ra, Wpi, Wv, mask, dh);
-    else if (A <= 8) hipLaunchKernelGGL((returns_heads_kernel<8, 8>), grid, blk, 0, s, ra, Wpi, Wv, mask, dh);
-    else hipLaunchKernelGGL((returns_heads_kernel<MAXA, 8>), grid, blk, 0, s, ra, Wpi, Wv, mask, dh);
-  } else {
-    hipLaunchKernelGGL((returns_heads_kernel<MAXA, 32>), grid, blk, 0, s, ra, Wpi, Wv, mask, dh);
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_ppo_snapshot(const float* rewards, const uint8_t* dones, const float* v, const float* logp,
-                               const int32_t* act, int T, int n, int A, double gamma, double lambda, int clip_reward,
-                               float* lpo, float* adv, float* ret, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  if (T < 1 || T > 256) return hipErrorInvalidValue;
-  const int EB = 256 / T;
-  SnapArgs a;
-  static_cast<ReturnsArgs&>(a) = ReturnsArgs{rewards, dones, v, logp, logp, act, T, n, A, gamma, 0.f, 0.f, 0.f, clip_reward,
-                                             0, nullptr, nullptr, nullptr, nullptr};
-  a.gl = gamma * lambda;
-  a.lpo_out = lpo;
-  a.adv_out = adv;
-  a.ret_out = ret;
-  const dim3 grid((n + EB - 1) / EB), blk(256);
-  if (gae_on(lambda)) hipLaunchKernelGGL(ppo_snapshot_kernel<RF_GAE>, grid, blk, 0, s, a);
-  else hipLaunchKernelGGL(ppo_snapshot_kernel<RF_NSTEP>, grid, blk, 0, s, a);
-  return hipGetLastError();
-}
-
-static ReturnsArgsPpo ppo_args(const PpoLossArgs& p, int64_t* ctl_snap) {
+static ReturnsArgsPpo ppo_args(const PpoLossArgs& p) {
   ReturnsArgsPpo a;
-  static_cast<ReturnsArgs&>(a) = ReturnsArgs{nullptr, p.dones, p.v, p.probs, p.logp, p.act, p.T, p.n, p.A, 0.0, p.beta,
-                                             p.vcoef, p.pcoef, 0, p.keep_scale, p.dlogits, p.dv, p.loss, ctl_snap};
-  a.lpo = p.lpo;
-  a.adv = p.adv;
-  a.ret = p.ret;
-  a.ratio = p.ratio;
-  a.lo = p.lo;
-  a.hi = p.hi;
+  static_cast<ReturnsArgs&>(a) = p.r;
+  a.rewards = nullptr; a.gamma = 0.0; a.clip_reward = 0;   // not read: the same launch whatever a caller left there
+  a.lpo = p.lpo; a.adv = p.adv; a.ret = p.ret; a.ratio = p.ratio;
+  a.lo = p.lo; a.hi = p.hi;
   return a;
 }
 
 // p.vold set: the value-clipped form's arguments
-static ReturnsArgsPpoVc ppo_vc_args(const PpoLossArgs& p, int64_t* ctl_snap) {
+static ReturnsArgsPpoVc ppo_vc_args(const PpoLossArgs& p) {
   ReturnsArgsPpoVc a;
-  static_cast<ReturnsArgsPpo&>(a) = ppo_args(p, ctl_snap);
+  static_cast<ReturnsArgsPpo&>(a) = ppo_args(p);
   a.vold = p.vold;
   a.ev = p.ev;
   return a;
 }
 
-hipError_t launch_ppo_lossgrad(const PpoLossArgs& p, hipStream_t s) {
-  if (p.n <= 0) return hipSuccess;
-  if (p.T < 1 || p.T > 256) return hipErrorInvalidValue;
-  const int EB = 256 / p.T;
-  const dim3 grid((p.n + EB - 1) / EB), blk(256);
-  if (p.vold != nullptr) hipLaunchKernelGGL(returns_kernel<RF_PPO_VC>, grid, blk, 0, s, ppo_vc_args(p, nullptr));
-  else hipLaunchKernelGGL(returns_kernel<RF_PPO>, grid, blk, 0, s, ppo_args(p, nullptr));
+// The register shapes of the heads kernels, the one place that chooses them: AM = the action count and RB = the
+// rows (steps) a pass their register arrays are sized for (RhState).  f(AM, RB) launches, the two as
+// std::integral_constants.
+template <class F>
+static hipError_t with_heads_shape(int T, int A, F&& f) {
+  if (T < 1 || T > 64 || A < 1 || A > MAXA) return hipErrorInvalidValue;
+  using std::integral_constant;
+  if (T > 8) f(integral_constant<int, MAXA>{}, integral_constant<int, 32>{});
+  else if (A <= 4) f(integral_constant<int, 4>{}, integral_constant<int, 8>{});
+  else if (A <= 8) f(integral_constant<int, 8>{}, integral_constant<int, 8>{});
+  else f(integral_constant<int, MAXA>{}, integral_constant<int, 8>{});
   return hipGetLastError();
 }
 
-hipError_t launch_ppo_heads(const PpoLossArgs& p, int64_t* ctl_snap, const float* Wpi, const float* Wv,
-                            const float* mask, float* dh, hipStream_t s) {
-  if (p.n <= 0) return hipSuccess;
-  if (p.T < 1 || p.T > 64 || p.A < 1 || p.A > MAXA) return hipErrorInvalidValue;
-  const dim3 grid(p.n), blk(256);
-  if (p.vold != nullptr) {
-    const ReturnsArgsPpoVc a = ppo_vc_args(p, ctl_snap);
-    if (p.T > 8) hipLaunchKernelGGL((returns_heads_kernel<MAXA, 32, RF_PPO_VC>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
-    else if (p.A <= 4) hipLaunchKernelGGL((returns_heads_kernel<4, 8, RF_PPO_VC>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
-    else if (p.A <= 8) hipLaunchKernelGGL((returns_heads_kernel<8, 8, RF_PPO_VC>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
-    else hipLaunchKernelGGL((returns_heads_kernel<MAXA, 8, RF_PPO_VC>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
-    return hipGetLastError();
-  }
-  const ReturnsArgsPpo a = ppo_args(p, ctl_snap);
-  if (p.T > 8) hipLaunchKernelGGL((returns_heads_kernel<MAXA, 32, RF_PPO>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
-  else if (p.A <= 4) hipLaunchKernelGGL((returns_heads_kernel<4, 8, RF_PPO>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
-  else if (p.A <= 8) hipLaunchKernelGGL((returns_heads_kernel<8, 8, RF_PPO>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
-  else hipLaunchKernelGGL((returns_heads_kernel<MAXA, 8, RF_PPO>), grid, blk, 0, s, a, Wpi, Wv, mask, dh);
+template <int G>
+static hipError_t returns_form(const ReturnsArgsT<G>& a, hipStream_t s) {
+  if (a.n <= 0) return hipSuccess;
+  if (a.T < 1 || a.T > 256) return hipErrorInvalidValue;
+  const int EB = 256 / a.T;
+  hipLaunchKernelGGL(returns_kernel<G>, dim3((a.n + EB - 1) / EB), dim3(256), 0, s, a);
   return hipGetLastError();
+}
+
+template <int G>
+static hipError_t returns_heads_form(const ReturnsArgsT<G>& a, const HeadsBwd& hb, hipStream_t s) {
+  if (a.n <= 0) return hipSuccess;
+  return with_heads_shape(a.T, a.A, [&](auto am, auto rb) {
+    hipLaunchKernelGGL((returns_heads_kernel<decltype(am)::value, decltype(rb)::value, G>), dim3(a.n), dim3(256), 0, s,
+                       a, hb.Wpi, hb.Wv, hb.mask, hb.dh);
+  });
+}
+
+template <int G>
+static hipError_t policy_fc_returns_form(const float* slab, const float* fc_bias, float* hfc, const PolicyArgs& pa,
+                                         const ReturnsArgsT<G>& ra, const HeadsBwd& hb, hipStream_t s) {
+  return with_heads_shape(ra.T, ra.A, [&](auto am, auto rb) {
+    hipLaunchKernelGGL((policy_fc_returns_kernel<decltype(am)::value, decltype(rb)::value, G>), dim3(ra.n), dim3(256),
+                       0, s, slab, ra.n, fc_bias, hfc, pa, ra, hb.mask, hb.dh);
+  });
+}
+
+hipError_t launch_returns(const ReturnsArgs& ra, double lambda, hipStream_t s) {
+  return gae_on(lambda) ? returns_form<RF_GAE>(gae_args(ra, lambda), s) : returns_form<RF_NSTEP>(ra, s);
+}
+
+hipError_t launch_returns_heads(const ReturnsArgs& ra, double lambda, const HeadsBwd& hb, hipStream_t s) {
+  return gae_on(lambda) ? returns_heads_form<RF_GAE>(gae_args(ra, lambda), hb, s)
+                        : returns_heads_form<RF_NSTEP>(ra, hb, s);
+}
+
+// hb.Wpi / hb.Wv are not read: the heads' weights are the policy's own (pa)
+hipError_t launch_policy_fc_returns(const float* slab, int n, const float* fc_bias, float* hfc, const PolicyArgs& pa,
+                                    const ReturnsArgs& ra, double lambda, const HeadsBwd& hb, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (ra.n != n || ra.A != pa.A) return hipErrorInvalidValue;   // one set of rows, one set of heads
+  return gae_on(lambda) ? policy_fc_returns_form<RF_GAE>(slab, fc_bias, hfc, pa, gae_args(ra, lambda), hb, s)
+                        : policy_fc_returns_form<RF_NSTEP>(slab, fc_bias, hfc, pa, ra, hb, s);
+}
+
+hipError_t launch_ppo_snapshot(const ReturnsArgs& ra, double lambda, float* lpo, float* adv, float* ret, hipStream_t s) {
+  if (ra.n <= 0) return hipSuccess;
+  if (ra.T < 1 || ra.T > 256) return hipErrorInvalidValue;
+  const int EB = 256 / ra.T;
+  SnapArgs a{};   // the coefficients and dlogits / dv / loss / ctl stay 0 / null: the kernel has no use for them
+  a.rewards = ra.rewards; a.dones = ra.dones; a.v = ra.v; a.logp = ra.logp; a.act = ra.act;
+  a.probs = ra.logp;   // (any readable (T, n, A) array)
+  a.T = ra.T; a.n = ra.n; a.A = ra.A;
+  a.gamma = ra.gamma; a.clip_reward = ra.clip_reward; a.gl = ra.gamma * lambda;
+  a.lpo_out = lpo; a.adv_out = adv; a.ret_out = ret;
+  const dim3 grid((ra.n + EB - 1) / EB), blk(256);
+  if (gae_on(lambda)) hipLaunchKernelGGL(ppo_snapshot_kernel<RF_GAE>, grid, blk, 0, s, a);
+  else hipLaunchKernelGGL(ppo_snapshot_kernel<RF_NSTEP>, grid, blk, 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_ppo_lossgrad(const PpoLossArgs& p, hipStream_t s) {
+  return p.vold != nullptr ? returns_form<RF_PPO_VC>(ppo_vc_args(p), s) : returns_form<RF_PPO>(ppo_args(p), s);
+}
+
+hipError_t launch_ppo_heads(const PpoLossArgs& p, const HeadsBwd& hb, hipStream_t s) {
+  return p.vold != nullptr ? returns_heads_form<RF_PPO_VC>(ppo_vc_args(p), hb, s)
+                           : returns_heads_form<RF_PPO>(ppo_args(p), hb, s);
 }
 
 // ---------------------------------------------------------------- PPO options (arl_net_set_ppo_options)
@@ -971,53 +946,12 @@ hipError_t launch_ppo_normalize_adv(const uint8_t* dones, float* adv, int T, int
 
 hipError_t launch_ppo_epoch_stats(const PpoLossArgs& p, const int64_t* ctl, double window, double epoch, int64_t* count,
                                   double* rec, hipStream_t s) {
-  if (p.n <= 0) return hipSuccess;
-  if (p.T < 1 || p.T > 256 || p.A < 1 || p.A > MAXA || p.ratio == nullptr) return hipErrorInvalidValue;
-  const EpochStatsArgs a{p.dones, p.v, p.logp, p.act, p.lpo, p.adv, p.ret, p.ratio, p.vold, p.T, p.n, p.A,
+  const ReturnsArgs& r = p.r;
+  if (r.n <= 0) return hipSuccess;
+  if (r.T < 1 || r.T > 256 || r.A < 1 || r.A > MAXA || p.ratio == nullptr) return hipErrorInvalidValue;
+  const EpochStatsArgs a{r.dones, r.v, r.logp, r.act, p.lpo, p.adv, p.ret, p.ratio, p.vold, r.T, r.n, r.A,
                          p.lo, p.hi, p.ev, ctl, window, epoch, count, rec};
   hipLaunchKernelGGL(ppo_epoch_stats_kernel, dim3(1), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_policy_fc_returns(const float* slab, int n, const float* fc_bias, float* hfc, const PolicyArgs& pa,
-                                    const float* rewards, const uint8_t* dones, const float* v, const float* probs,
-                                    const float* logp, const int32_t* act, int T, double gamma, float beta,
-                                    float vcoef, int clip_reward, float* dlogits, float* dv, float* loss,
-                                    int64_t* ctl_snap, float pcoef, int keep_scale, const float* mask, float* dh,
-                                    hipStream_t s, double lambda) {
-  if (n <= 0) return hipSuccess;
-  const int A = pa.A;
-  if (T < 1 || T > 64 || A < 1 || A > MAXA) return hipErrorInvalidValue;
-  const ReturnsArgs ra{rewards, dones, v, probs, logp, act, T, n, A, gamma, beta, vcoef, pcoef, clip_reward,
-                       keep_scale, dlogits, dv, loss, ctl_snap};
-  const dim3 grid(n), blk(256);
-  if (gae_on(lambda)) {
-    const ReturnsArgsGae rg = gae_args(ra, lambda);
-    if (T > 8)
-      hipLaunchKernelGGL((policy_fc_returns_kernel<MAXA, 32, true>), grid, blk, 0, s, slab, n, fc_bias, hfc, pa, rg,
-                         mask, dh);
-    else if (A <= 4)
-      hipLaunchKernelGGL((policy_fc_returns_kernel<4, 8, true>), grid, blk, 0, s, slab, n, fc_bias, hfc, pa, rg, mask,
-                         dh);
-    else if (A <= 8)
-      hipLaunchKernelGGL((policy_fc_returns_kernel<8, 8, true>), grid, blk, 0, s, slab, n, fc_bias, hfc, pa, rg, mask,
-                         dh);
-    else
-      hipLaunchKernelGGL((policy_fc_returns_kernel<MAXA, 8, true>), grid, blk, 0, s, slab, n, fc_bias, hfc, pa, rg,
-                         mask, dh);
-    return hipGetLastError();
-  }
-  if (T <= 8) {
-    if (A <= 4)
-      hipLaunchKernelGGL((policy_fc_returns_kernel<4, 8>), grid, blk, 0, s, slab, n, fc_bias, hfc, pa, ra, mask, dh);
-    else if (A <= 8)
-      hipLaunchKernelGGL((policy_fc_returns_kernel<8, 8>), grid, blk, 0, s, slab, n, fc_bias, hfc, pa, ra, mask, dh);
-    else
-      hipLaunchKernelGGL((policy_fc_returns_kernel<MAXA, 8>), grid, blk, 0, s, slab, n, fc_bias, hfc, pa, ra, mask,
-                         dh);
-  } else {
-    hipLaunchKernelGGL((policy_fc_returns_kernel<MAXA, 32>), grid, blk, 0, s, slab, n, fc_bias, hfc, pa, ra, mask, dh);
-  }
   return hipGetLastError();
 }
 

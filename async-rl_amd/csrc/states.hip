@@ -58,7 +58,6 @@ SPlans states_plans(const Net& net) {
   return p;
 }
 
-#define ARL_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return _e; } while (0)
 
 }  // namespace
 

@@ -188,19 +188,25 @@ N, T, A, PL = 64, 5, 4, 6
 LR2 = 8e-3     # the update between the epochs: see test_epoch_two_against_the_oracle
 
 
-def state_pools():
-    return make_state_pools(np.random.default_rng(N + T + A), PL, N, p_done=0.2)
+# (N, T, A) of the nets whose first epoch is compared with the A3C learn: one for each shape the loss-gradient
+# launch's register forms are built for -- A <= 4, A <= 8, wider (all T <= 8), and T > 8
+NET_SHAPES = [(64, 5, 4), (5, 5, 6), (5, 5, 18), (5, 9, 4)]
 
 
-def rollout(gpu, pools, lam, ppo):
+def state_pools(shape=(N, T, A)):
+    return make_state_pools(np.random.default_rng(sum(shape)), PL, shape[0], p_done=0.2)
+
+
+def rollout(gpu, pools, lam, ppo, shape=(N, T, A)):
     from asyncrl_amd import A3CFF
-    model = A3CFF(A, n_envs=N, t_max=T, seed=99, init_seed=3, frames="states", device=gpu)
+    n, t_max, n_actions = shape
+    model = A3CFF(n_actions, n_envs=n, t_max=t_max, seed=99, init_seed=3, frames="states", device=gpu)
     net = model.net
     net.reset()
     net.set_gae(lam)
     if ppo:
         net.set_ppo(EPS)
-    for t in range(T + 1):
+    for t in range(t_max + 1):
         net.observe_act(t, *pools, PL, force_reset=(t == 0))
     return net
 
@@ -221,12 +227,14 @@ def dev_acts(net):
 
 
 @pytest.mark.parametrize("lam", [1.0, 0.95])
-def test_epoch_one_is_the_a3c_gradient(gpu, lam):
-    pools = tuple(dev(x, gpu) for x in state_pools())
-    a3c = rollout(gpu, pools, lam, False)
+@pytest.mark.parametrize("shape", NET_SHAPES, ids=lambda sh: "N%d-T%d-A%d" % sh)
+def test_epoch_one_is_the_a3c_gradient(gpu, shape, lam):
+    n, t_max, _ = shape
+    pools = tuple(dev(x, gpu) for x in state_pools(shape))
+    a3c = rollout(gpu, pools, lam, False, shape)
     a3c.learn(GAMMA, BETA, VCOEF, True)
     want = learner_outputs(a3c)
-    ppo = rollout(gpu, pools, lam, True)
+    ppo = rollout(gpu, pools, lam, True, shape)
     with pytest.raises(Exception, match="arl_ppo_begin"):
         ppo.ppo_learn(BETA, VCOEF)
     ppo.ppo_begin(GAMMA, True)
@@ -236,7 +244,7 @@ def test_epoch_one_is_the_a3c_gradient(gpu, lam):
         assert tbits(got[k], want[k]), k
         assert float(want[k].abs().max()) > 0
     ratio = ppo.ppo_planes()["ratio"]
-    dones = ppo.buffer("dones", torch.uint8, (T, N))
+    dones = ppo.buffer("dones", torch.uint8, (t_max, n))
     assert bool((ratio == 1).all()) and int(dones.max()) <= 1
     ctl = ppo.buffer("ctl", torch.int64)
     assert int(ctl[2]) == int(ctl[0])                               # the step snapshot the fused advance reads

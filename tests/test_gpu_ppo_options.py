@@ -189,11 +189,31 @@ def test_granular_epoch_record_is_the_restatement(gpu, i, with_v_old):
 
 
 # ------------------------------------------------------------------ 4, 5. a net's epochs
-def net_rollout(gpu, pools, lam, norm_adv, vclip):
-    net = G.rollout(gpu, pools, lam, True)
+def net_rollout(gpu, pools, lam, norm_adv, vclip, shape=(G.N, G.T, G.A)):
+    net = G.rollout(gpu, pools, lam, True, shape)
     if norm_adv or vclip is not None:
         net.set_ppo_options(norm_adv, vclip)
     return net
+
+
+@pytest.mark.parametrize("lam", [1.0, 0.95])
+@pytest.mark.parametrize("shape", G.NET_SHAPES, ids=lambda sh: "N%d-T%d-A%d" % sh)
+def test_epoch_one_with_value_clip_is_the_plain_epoch(gpu, shape, lam):
+    """The net-level counterpart of test_value_clip_at_v_old_equal_to_v_is_the_plain_lossgrad, at every shape the
+    loss-gradient launch has a register form for: in epoch one v == v_old on every live sample, so the value-clipped
+    form takes the unclipped square and leaves the plain form's gradient, bit for bit."""
+    pools = tuple(dev(x, gpu) for x in G.state_pools(shape))
+    outs = []
+    for vclip in (None, 0.2):
+        net = net_rollout(gpu, pools, lam, False, vclip, shape)
+        assert (net.ppo_v_old is None) == (vclip is None)
+        net.ppo_begin(GAMMA, True)
+        net.ppo_learn(BETA, VCOEF)
+        outs.append(G.learner_outputs(net))
+    want, got = outs
+    for k in want:
+        assert tbits(got[k], want[k]), k
+        assert float(want[k].abs().max()) > 0
 
 
 @pytest.mark.parametrize("lam", [1.0, 0.95])
