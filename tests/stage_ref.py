@@ -2,7 +2,8 @@
 synthetic operands they are tested on, and the launch geometry of the HIP
 kernels that run them (tests/test_stage_ref.py pins all of it on the CPU,
 tests/test_gpu_stages.py and tests/test_gpu_gemm_stages.py compare
-arl_run_stage with it).  Nothing here touches a device.
+arl_run_stage with it, tests/test_gpu_lossgrad_stages.py the loss-gradient
+launches in their GAE, PPO and fused forms).  Nothing here touches a device.
 
 Every reduction over the window's S = t_max * n_envs samples is accumulated
 in float64 and rounded to float32 once, as oracle.gmm / oracle.gsum do, and
@@ -296,45 +297,149 @@ def lstm_bptt_chain_ref(Wl, reset, gates, cbuf, dH):
 
 
 # ---------------------------------------------------------------- returns
+RW = 8   # policy.hip: windows up to RW steps are scanned from registers
+
+# mistake=: the deliberate mistakes of tests/test_stage_ref.py's sensitivity checks, None everywhere else
+
+
+def segment_factor(dones, keep_scale=True, mistake=None):
+    """keep_loss_scale_same (a3c.py:116-121) as returns_compute applies it: the loss terms of a live
+    step whose segment -- from the step after the previous terminal to the first terminal at or after
+    it -- a terminal closed after len < T steps carry T / len; every other step 1.  dones (T, N) with
+    bit 0 = terminal, bit 1 = past a truncated window's end.  Returns (T, N) float64.
+    mistake "seg_start": the segment's start ignores the terminal before t."""
+    T, N = dones.shape
+    f = np.ones((T, N))
+    if not keep_scale:
+        return f
+    term = (np.asarray(dones).astype(np.int64) & 1) != 0
+    for e in range(N):
+        start = 0
+        for t in range(T):
+            if term[t, e]:
+                if t - start + 1 < T:
+                    f[start:t + 1, e] = T / (t - start + 1)
+                start = t + 1 if mistake != "seg_start" else start
+    return f
+
+
+def _heads_dh(dlogits, dv, Wpi, Wv, hfc, live):
+    """dh = dlogits Wpi + dv Wv, times (hfc > 0) with hfc, 0 on the rows that are not live."""
+    dh = dlogits @ np.asarray(Wpi, F64) + dv[..., None] * np.asarray(Wv, F64).reshape(-1)
+    if hfc is not None:
+        dh = dh * (np.asarray(hfc) > 0)
+    return dh * live[..., None]
+
+
 def returns_heads_ref(rewards, dones, v, probs, logp, actions, Wpi, Wv, hfc=None, gamma=0.99, beta=0.01, vcoef=0.5,
-                      clip_reward=True, lam=1.0):
+                      clip_reward=True, lam=1.0, pi_loss_coef=1.0, keep_loss_scale_same=False, mistake=None):
     """The returns stage (returns_heads_kernel, policy.hip) in float64 from the f32
     buffers: oracle.returns_and_lossgrad's mathematics (R restarted at terminals,
     rewards clipped to +-1) on rewards / dones (T, N), v (T + 1, N) with slot T the
     bootstrap value, probs / logp (T, N, A), actions (T, N); the heads' backward
     dh = dlogits Wpi + dv Wv, and with hfc (T, N, 256) dfc = dh * (hfc > 0).
+    dones: bit 0 = terminal, bit 1 = past a truncated window's end (arl_truncate_window):
+    there dlogits, dv, dh and the loss terms are 0.
     lam != 1: the policy term's advantage is GAE(lambda) (arl_net_set_gae: delta_k =
     r_k + gamma v_{k+1} - v_k with v_{k+1} = 0 at a terminal, the scan cut there);
     the value target stays the n-step return.
+    pi_loss_coef / vcoef scale the two loss terms, and with keep_loss_scale_same both
+    carry segment_factor's T / len.
     Returns dlogits (T, N, A), dv (T, N), loss (N, 2) = per-env (pi, v) losses and
-    dh (or dfc) (T, N, hidden width)."""
+    dh (or dfc) (T, N, hidden width).
+    mistake (GAE): "vnext_rw" v[k + 1] taken from v[k] at k = RW - 1, "no_boot" the bootstrap value
+    dropped from the delta of step T - 1, "keep_G" a terminal that does not cut G; "seg_start"."""
     T, N = rewards.shape
     r = np.asarray(rewards, F64)
     if clip_reward:
         r = np.clip(r, -1.0, 1.0)
+    dn = np.asarray(dones).astype(np.int64)
+    term, live = (dn & 1) != 0, (dn & 2) == 0
     v, p, lp = np.asarray(v, F64), np.asarray(probs, F64), np.asarray(logp, F64)
     R, Rs = v[T].copy(), np.empty((T, N))
     for t in reversed(range(T)):
-        R = np.where(dones[t] != 0, 0.0, R) * gamma + r[t]
+        R = np.where(term[t], 0.0, R) * gamma + r[t]
         Rs[t] = R
     adv = Rs - v[:T]
     if lam != 1.0:
         G, adv = np.zeros(N), np.empty((T, N))
         for t in reversed(range(T)):
-            term = dones[t] != 0
-            G = (r[t] + gamma * np.where(term, 0.0, v[t + 1]) - v[t]) + gamma * lam * np.where(term, 0.0, G)
+            vn = v[t] if mistake == "vnext_rw" and t == RW - 1 else v[t + 1]
+            vn = np.where(term[t] | (mistake == "no_boot" and t == T - 1), 0.0, vn)
+            G = (r[t] + gamma * vn - v[t]) + gamma * lam * np.where(term[t] & (mistake != "keep_G"), 0.0, G)
             adv[t] = G
+    scale = segment_factor(dn, keep_loss_scale_same, mistake) * live
+    pf, vf = pi_loss_coef * scale, vcoef * scale
     H = -(p * lp).sum(-1)
     onehot = np.zeros_like(p)
     np.put_along_axis(onehot, np.asarray(actions, np.int64)[..., None], 1.0, axis=2)
-    dlogits = -adv[..., None] * (onehot - p) + beta * p * (lp + H[..., None])
-    dv = vcoef * (v[:T] - Rs)
+    dlogits = pf[..., None] * (-adv[..., None] * (onehot - p) + beta * p * (lp + H[..., None]))
+    dv = vf * (v[:T] - Rs)
     lp_a = np.take_along_axis(lp, np.asarray(actions, np.int64)[..., None], 2)[..., 0]
-    loss = np.stack([-(lp_a * adv + beta * H).sum(0), (vcoef * (v[:T] - Rs) ** 2 / 2).sum(0)], 1)
-    dh = dlogits @ np.asarray(Wpi, F64) + dv[..., None] * np.asarray(Wv, F64).reshape(-1)
-    if hfc is not None:
-        dh = dh * (np.asarray(hfc) > 0)
-    return dlogits, dv, loss, dh
+    loss = np.stack([-(pf * (lp_a * adv + beta * H)).sum(0), (vf * (v[:T] - Rs) ** 2 / 2).sum(0)], 1)
+    return dlogits, dv, loss, _heads_dh(dlogits, dv, Wpi, Wv, hfc, live)
+
+
+def clip_range(clip_eps):
+    """lo, hi of the clipped surrogate as the host forms them: one float64 operation each, rounded to f32."""
+    return F32(1.0 - float(clip_eps)), F32(1.0 + float(clip_eps))
+
+
+def ppo_heads_ref(dones, v, probs, logp, actions, logp_old, adv, ret, Wpi, Wv, hfc=None, clip_eps=0.2, beta=0.01,
+                  vcoef=0.5, pi_loss_coef=1.0, keep_loss_scale_same=False, v_old=None, vclip_eps=None, mistake=None):
+    """One clipped-surrogate epoch's loss gradient and heads backward (the RF_PPO / RF_PPO_VC forms of
+    returns_heads_kernel) in float64 from the f32 buffers: the snapshot logp_old / adv / ret (T, N), the
+    current v (>= T, N), probs / logp (T, N, A), actions (T, N).  rho = exp(logp[a] - logp_old); a sample is
+    active while rho <= hi (adv >= 0) or rho >= lo (adv < 0): its policy gradient is that of rho * adv and
+    its loss term rho * adv, else no policy gradient and the term hi * adv or lo * adv.  With v_old and
+    vclip_eps the value loss is max((v - ret)^2, (v_c - ret)^2) / 2, v_c = v_old + clamp(v - v_old, +-
+    vclip_eps); dv is 0 where the clipped square is the larger one.  Rows past a truncated window's end
+    (dones bit 1) are 0 throughout, the ratio included.
+    Returns dlogits (T, N, A), dv (T, N), ratio (T, N), loss (N, 2) and dh (or dfc).
+    mistake: "neg_side" the clip applied on the hi side for adv < 0 too, "no_ratio" the ratio not applied to
+    the gradient, "swap" lo / hi swapped, "vc_grad" a clipped-away value sample keeps its gradient, "vc_plus"
+    v_old + ev where v_old - ev belongs; "seg_start"."""
+    dn = np.asarray(dones).astype(np.int64)
+    T, N = dn.shape
+    live = (dn & 2) == 0
+    vi, p, lp = np.asarray(v, F64)[:T], np.asarray(probs, F64)[:T], np.asarray(logp, F64)[:T]
+    ac = np.asarray(actions, np.int64)[:T, :, None]
+    lpo, adv, Rf = np.asarray(logp_old, F64), np.asarray(adv, F64), np.asarray(ret, F64)
+    lo, hi = (F64(x) for x in clip_range(clip_eps)[::-1 if mistake == "swap" else 1])
+    scale = segment_factor(dn, keep_loss_scale_same, mistake) * live
+    pf, vf = pi_loss_coef * scale, vcoef * scale
+    rho = np.exp(np.take_along_axis(lp, ac, 2)[..., 0] - lpo)
+    pos = adv >= 0
+    active = np.where(pos | (mistake == "neg_side"), rho <= hi, rho >= lo)
+    surr = np.where(active, rho * adv, np.where(pos | (mistake == "neg_side"), hi, lo) * adv)
+    w = np.where(active, adv if mistake == "no_ratio" else rho * adv, 0.0)
+    H = -(p * lp).sum(-1)
+    onehot = np.zeros_like(p)
+    np.put_along_axis(onehot, ac, 1.0, axis=2)
+    dlogits = pf[..., None] * (-w[..., None] * (onehot - p) + beta * p * (lp + H[..., None]))
+    dvv = vi - Rf
+    lsq, taken = dvv * dvv, np.zeros((T, N), bool)
+    if v_old is not None:
+        ev = F64(F32(vclip_eps))
+        dvo = vi - np.asarray(v_old, F64)
+        lc = (np.asarray(v_old, F64) + np.clip(dvo, ev if mistake == "vc_plus" else -ev, ev) - Rf) ** 2
+        taken = (np.abs(dvo) > ev) & (lc > lsq)
+        lsq = np.where(taken, lc, lsq)
+    dv = np.where(taken & (mistake != "vc_grad"), 0.0, vf * dvv)
+    loss = np.stack([-(pf * (surr + beta * H)).sum(0), (vf * lsq * 0.5).sum(0)], 1)
+    return dlogits, dv, rho * live, loss, _heads_dh(dlogits, dv, Wpi, Wv, hfc, live)
+
+
+def fused_bootstrap_ref(a2T, Wfc, bfc, Wpi, bpi, Wv, bv, rewards, dones, v, probs, logp, actions, hfc=None, **kw):
+    """The bootstrap step with the learner's first launch folded in (policy_fc_returns_kernel) in float64:
+    hfc[T] = relu(a2[T] Wfc^T + b) from a2T (N, 2592), the heads of slot T through policy_ref, then
+    returns_heads_ref with that v[T] as the bootstrap value (v: (>= T, N), rows 0 .. T - 1 are read).
+    Returns (hfc[T], policy_ref's dict of slot T, returns_heads_ref's tuple)."""
+    T = rewards.shape[0]
+    hT = np.maximum(mm64(a2T, np.asarray(Wfc).T) + np.asarray(bfc, F64), 0.0)
+    pol = policy_ref(hT, Wpi, bpi, Wv, bv)
+    vv = np.concatenate([np.asarray(v, F64)[:T], pol["v"][None]])
+    return hT, pol, returns_heads_ref(rewards, dones, vv, probs, logp, actions, Wpi, Wv, hfc, **kw)
 
 
 # ---------------------------------------------------------------- data recipes
@@ -508,6 +613,97 @@ def returns_data(t_max, n_actions, n_envs, lstm=False, seed=0):
             "Wpi": weight_like(rng, (A, HID)), "Wv": weight_like(rng, (1, HID))}
 
 
+# the loss-gradient stage tests' coefficients (none a default, so a hard-coded default shows) and PPO settings
+COEF = {"gamma": 0.9, "beta": 0.02, "vcoef": 0.25, "pi_loss_coef": 0.5}
+PPO_CLIP, PPO_VCLIP = 0.2, 0.1
+PPO_GRID = np.array([-0.6, -0.35, -0.1, 0.1, 0.35, 0.6], F32)      # log ratios: exp() on both sides of lo and hi
+VCLIP_GRID = np.array([-0.3, -0.15, -0.05, 0.05, 0.15, 0.3], F32)   # v - v_old: on both sides of +-PPO_VCLIP
+MARGIN = 1e-3   # relative distance of every decision from its threshold
+
+
+def near_threshold(d):
+    """(T, N) bool: the samples of lossgrad_data's d on which a decision of the PPO forms lies within MARGIN
+    (relative) of its threshold: rho against lo / hi, |v - v_old| against ev, the clipped square against the
+    unclipped one (where the value is outside the clip range), and a nonzero adv against 0 (an exact zero
+    takes no decision: rho * 0, hi * 0 and lo * 0 are the same 0)."""
+    T = d["T"]
+    lo, hi = (F64(x) for x in clip_range(PPO_CLIP))
+    ev = F64(F32(PPO_VCLIP))
+    lpa = np.take_along_axis(np.asarray(d["logp"], F64), np.asarray(d["actions"], np.int64)[..., None], 2)[..., 0]
+    rho = np.exp(lpa - np.asarray(d["logp_old"], F64))
+    v, vo, Rf, adv = (np.asarray(x, F64) for x in (d["v"][:T], d["v_old"], d["ret"], d["adv"]))
+    dvo = v - vo
+    lu, lc = (v - Rf) ** 2, (vo + np.clip(dvo, -ev, ev) - Rf) ** 2
+    bad = (np.abs(rho - lo) < MARGIN * lo) | (np.abs(rho - hi) < MARGIN * hi)
+    bad |= np.abs(np.abs(dvo) - ev) < MARGIN * ev
+    bad |= (np.abs(dvo) > ev) & (np.abs(lc - lu) < MARGIN * np.maximum(lc, lu))
+    bad |= (adv != 0) & (np.abs(adv) < MARGIN * np.abs(adv).max())
+    return bad
+
+
+def lossgrad_data(t_max, n_actions, n_envs, lstm=False, t_len=None, seed=0):
+    """returns_data plus what the GAE / PPO forms and a truncated window need.
+    t_len: a terminal on every env at step t_len - 1; rewards_t / dones_t are the window as
+    arl_truncate_window(t_len) leaves it (rows >= t_len: dones 2, rewards 0), else the window itself.
+    The PPO snapshot: logp_old = logp[a] - delta with delta from PPO_GRID, adv normal with ~10 % exact
+    zeros, ret the f32 n-step return at COEF's gamma, v_old = v - d with d from VCLIP_GRID.  A sample with
+    a decision within MARGIN of its threshold (near_threshold) is drawn again, none is exempted; `redrawn`
+    counts the draws that took."""
+    d = returns_data(t_max, n_actions, n_envs, lstm, seed)
+    T, N = t_max, n_envs
+    rng = np.random.default_rng([seed, t_max, n_actions, n_envs, 13])
+    d["rewards_t"], d["dones_t"] = d["rewards"], d["dones"]
+    if t_len is not None:
+        d["dones"][t_len - 1] = 1
+        d["rewards_t"], d["dones_t"] = d["rewards"].copy(), d["dones"].copy()
+        d["rewards_t"][t_len:], d["dones_t"][t_len:] = 0, 2
+    R, ret = np.asarray(d["v"][T], F64), np.empty((T, N), F32)
+    for t in reversed(range(T)):
+        R = np.where(d["dones_t"][t] & 1, 0.0, R) * COEF["gamma"] + np.clip(np.asarray(d["rewards_t"][t], F64), -1.0, 1.0)
+        ret[t] = R
+    lpa = np.take_along_axis(d["logp"], d["actions"][..., None].astype(np.int64), 2)[..., 0]
+
+    def draw():
+        adv = rng.standard_normal((T, N), F32) * (rng.random((T, N)) >= 0.1)
+        return ((lpa - rng.choice(PPO_GRID, (T, N))).astype(F32), adv.astype(F32),
+                (d["v"][:T] - rng.choice(VCLIP_GRID, (T, N))).astype(F32))
+
+    d["ret"] = ret
+    d["logp_old"], d["adv"], d["v_old"] = draw()
+    if T * N >= 8:
+        d["adv"][T // 2, N - 1] = 0   # (an exact zero in every case but the smallest)
+    d["redrawn"] = 0
+    for _ in range(100):
+        bad = near_threshold(d)
+        if not bad.any():
+            break
+        d["redrawn"] += int(bad.sum())
+        for k, fresh in zip(("logp_old", "adv", "v_old"), draw()):
+            d[k][bad] = fresh[bad]
+    assert not near_threshold(d).any()
+    return d
+
+
+def fused_data(t_max, n_actions, n_envs, seed=0):
+    """lossgrad_data plus the bootstrap slot's forward: the FC's and the heads' parameters and a2T (N, 2592),
+    post-ReLU with exact zeros.  An env whose FC pre-activation has a unit within MARGIN of 0 (relative
+    to the largest) is drawn again."""
+    d = lossgrad_data(t_max, n_actions, n_envs, seed=seed)
+    rng = np.random.default_rng([seed, t_max, n_actions, n_envs, 14])
+    d["Wfc"], d["bfc"] = weight_like(rng, (HID, A2)), rng.uniform(-1 / 51, 1 / 51, HID).astype(F32)
+    d["bpi"], d["bv"] = rng.uniform(-1 / 16, 1 / 16, n_actions).astype(F32), rng.uniform(-1 / 16, 1 / 16, 1).astype(F32)
+    a2T = act_like(rng, (n_envs, A2))
+    for _ in range(100):
+        z = mm64(a2T, d["Wfc"].T) + d["bfc"]
+        bad = (np.abs(z) < MARGIN * np.abs(z).max()).any(1)
+        if not bad.any():
+            break
+        a2T[bad] = act_like(rng, (int(bad.sum()), A2))
+    assert not bad.any()
+    d["a2T"], d["zT"] = a2T, z
+    return d
+
+
 # the cases of tests/test_gpu_stages.py, (n_envs, t_max); tests/test_stage_ref.py runs the
 # sensitivity check on the same list
 FC_CASES = [(1, 1), (43, 3), (109, 11), (240, 5), (241, 5), (400, 5)]
@@ -525,6 +721,43 @@ BPTT_CHAIN_CASES = [(37, 5), (1, 5)]
 # returns (t_max, n_actions, n_envs): one case for each returns_heads_kernel<AM, RB> and row-pass count
 RETURNS_CASES = [(1, 1, 1), (8, 4, 3), (8, 5, 3), (8, 8, 2), (8, 9, 2), (9, 4, 3), (32, 32, 2), (33, 6, 2), (64, 32, 2)]
 RETURNS_LSTM_CASE = (5, 6, 3)
+# tests/test_gpu_lossgrad_stages.py: every RETURNS_CASES case in each form of the loss-gradient launch
+LOSSGRAD_FORMS = ("nstep", "gae", "ppo", "ppo_vc")
+GAE_LAMBDA = 0.95
+GAE0_CASES = [(8, 8, 2), (33, 6, 2)]                                    # also at lambda = 0
+TRUNC_CASES = [((8, 4, 3), 5), ((33, 6, 2), 32), ((64, 32, 2), 33)]     # (case, t_len); 32: the second row pass all dead
+FUSED_CASES = [(8, 4, 3), (8, 8, 2), (9, 4, 3), (33, 6, 2), (64, 32, 2)]
+# returns_kernel / ppo_snapshot_kernel packing (t_max, n_envs) at 6 actions: T = 1; the last register-window length;
+# EB = 4 with a one-env tail; EB = 3 with an idle thread and a one-env tail; EB = 2; the first EB = 1; the largest T
+PACK_CASES = [(1, 257), (8, 33), (64, 5), (85, 4), (128, 3), (129, 2), (256, 2)]
+PACK_A = 6
+
+
+def lossgrad_runs():
+    """The heads-kernel runs of tests/test_gpu_lossgrad_stages.py, (case, form, lambda, t_len, lstm); each runs with
+    keep_loss_scale_same off and on."""
+    runs = [(c, f, GAE_LAMBDA if f == "gae" else 1.0, None, False) for c in RETURNS_CASES for f in LOSSGRAD_FORMS]
+    runs += [(c, "gae", 0.0, None, False) for c in GAE0_CASES]
+    runs += [(RETURNS_LSTM_CASE, "gae", GAE_LAMBDA, None, True)]
+    runs += [(c, f, GAE_LAMBDA if f == "gae" else 1.0, tl, False) for c, tl in TRUNC_CASES for f in ("gae", "ppo")]
+    return runs
+
+
+def lossgrad_ref(d, form, keep, lam=1.0, lstm=False, mistake=None):
+    """The reference of one run on lossgrad_data's d at COEF: {dlogits, dv, loss, dh, ratio (PPO forms)}."""
+    T = d["T"]
+    hfc = None if lstm else d["hfc"][:T]
+    kw = dict(beta=COEF["beta"], vcoef=COEF["vcoef"], pi_loss_coef=COEF["pi_loss_coef"], keep_loss_scale_same=keep,
+              mistake=mistake)
+    if form in ("ppo", "ppo_vc"):
+        if form == "ppo_vc":
+            kw.update(v_old=d["v_old"], vclip_eps=PPO_VCLIP)
+        dl, dv, ratio, loss, dh = ppo_heads_ref(d["dones_t"], d["v"], d["probs"], d["logp"], d["actions"], d["logp_old"],
+                                                d["adv"], d["ret"], d["Wpi"], d["Wv"], hfc, PPO_CLIP, **kw)
+        return {"dlogits": dl, "dv": dv, "loss": loss, "dh": dh, "ratio": ratio}
+    dl, dv, loss, dh = returns_heads_ref(d["rewards_t"], d["dones_t"], d["v"], d["probs"], d["logp"], d["actions"], d["Wpi"],
+                                         d["Wv"], hfc, gamma=COEF["gamma"], lam=lam, **kw)
+    return {"dlogits": dl, "dv": dv, "loss": loss, "dh": dh}
 
 
 # ================================================================ the generic implicit-GEMM paths

@@ -336,15 +336,16 @@ def manual_window(net, pools, P, first, truncate=None):
     net.optimize(advance=True)
 
 
-@pytest.mark.parametrize("n,T,truncate,c_call", [(40, 5, None, True), (300, 2, None, False), (5, 9, 7, False)])
+@pytest.mark.parametrize("n,T,truncate,c_call", [(40, 5, None, True), (300, 2, None, False), (5, 9, 7, False),
+                                                 (33, 8, None, False)])
 def test_window_statistics_record_the_gae_advantage(gpu, n, T, truncate, c_call):
     """lambda 0.95 with the record on: fields 12, 13 equal the float64 replay of the record's summation order over
     the replay's advantage bit for bit; so do fields 2..11 over the window's own buffers (window_replay.replay).
     Against the lambda = 1 record of the same window, fields 0..4 and 6..11 are equal bit for bit.  Field 5,
     pi_loss, is the one field of 0..11 that must differ: the policy loss is computed with the GAE advantage.
     40 envs through arl_run_window (the fused launch), 300 envs (threads own two envs; whole stacks as the
-    observation, 34 MB instead of 240 MB of frame pairs), and t_max 9 truncated to 7 (the record's loop over
-    memory)."""
+    observation, 34 MB instead of 240 MB of frame pairs), t_max 9 truncated to 7 (the record's loop over
+    memory), and 33 envs at t_max 8 (the last length the record's register window, WS_RW, holds)."""
     A, P = 4, T + 2
     rewards, dones = case_pools(1, P, n)
     if n > 256:

@@ -25,8 +25,9 @@ F32 = np.float32
 GAMMA, BETA, VCOEF, EPS = 0.99, 0.01, 0.5, 0.2
 GRID = np.array([-0.6, -0.35, -0.1, 0.1, 0.35, 0.6], F32)
 # (T, n, A): EB = 51 envs a block at T = 5, so 75 envs leave a partial second block; T = 9 takes the looped path
-# past RW = 8; one env and the widest action set the register forms are built for
-SHAPES = [(5, 75, 4), (9, 33, 6), (5, 1, 18)]
+# past RW = 8; one env and the widest action set the register forms are built for; T = 8, the last length the
+# register windows (RW, PO_RW) hold
+SHAPES = [(5, 75, 4), (9, 33, 6), (5, 1, 18), (8, 33, 6)]
 
 
 def dev(x, gpu):

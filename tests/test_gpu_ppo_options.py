@@ -22,8 +22,9 @@ pytestmark = pytest.mark.gpu
 F32, F64 = np.float32, np.float64
 GAMMA, BETA, VCOEF, EPS, VEPS = 0.99, 0.01, 0.5, 0.2, 0.1
 # test_gpu_ppo.py's three (a partial second block, the looped path past RW = 8, one env) and one whose 600 envs make
-# a thread of the single workgroup walk three envs, the last pass ragged (600 = 2 * 256 + 88)
-SHAPES = [(5, 75, 4), (9, 33, 6), (5, 1, 18), (4, 600, 4)]
+# a thread of the single workgroup walk three envs, the last pass ragged (600 = 2 * 256 + 88); and T = 8, the last
+# length the one-workgroup kernels' register window (PO_RW) holds
+SHAPES = [(5, 75, 4), (9, 33, 6), (5, 1, 18), (4, 600, 4), (8, 33, 6)]
 VGRID = np.array([-0.3, -0.15, -0.05, 0.05, 0.15, 0.3], F32)
 
 _CASES = {}

@@ -835,3 +835,216 @@ def test_fc_fwd_second_m_tile_sensitivity():
     pert = h.copy()
     pert[64:] = 0
     assert (h[64:] > 0).any() and _worst([pert], [h]) >= 10
+
+
+# ================================================================ the loss-gradient forms (GAE, PPO, the fused bootstrap)
+def _pinned(got, want, what):
+    ok, err = close_normscaled(got, want, 1e-6)
+    print(f"{what}: {err:.3g} of the scale from the restatement")
+    assert ok, (what, err)
+
+
+def test_lossgrad_refs_equal_the_restatements():
+    """returns_heads_ref with pi_loss_coef, keep_loss_scale_same and a truncated tail, and ppo_heads_ref, on a
+    T = 8 window closed at t_len = 6 with terminals inside it, against oracle.returns_and_lossgrad,
+    gae_replay, ppo_ref.lossgrad and ppo_options_ref.lossgrad_vclip (each the device's own f32 order of
+    operations), within 1e-6 of the scale; the heads' dh against the same product of the restatements'
+    dlogits / dv."""
+    import ppo_options_ref
+    import ppo_ref
+    from gae_replay import returns_and_lossgrad_gae
+    d = R.lossgrad_data(8, 5, 3, t_len=6)
+    T, c = d["T"], R.COEF
+    dn = d["dones_t"].astype(np.int64)
+    term, valid = (dn & 1).astype(np.uint8), (dn & 2) == 0
+    assert term[:5].sum() >= 2 and (~valid).sum() == 6 and d["redrawn"] == 0
+    hfc = d["hfc"][:T]
+
+    def dh_of(dl, dv):
+        return (dl @ d["Wpi"] + dv[..., None] * d["Wv"][0]) * (hfc > 0)
+
+    okw = dict(gamma=c["gamma"], beta=c["beta"], v_loss_coef=c["vcoef"], clip_reward=True, pi_loss_coef=c["pi_loss_coef"],
+               keep_loss_scale_same=True, valid=valid)
+    oargs = (d["rewards_t"], term, d["v"][:T], d["v"][T], d["probs"], d["logp"], d["actions"])
+    for form, lam, want in (("nstep", 1.0, O.returns_and_lossgrad(*oargs, **okw)),
+                            ("gae", 0.95, returns_and_lossgrad_gae(*oargs, lam=0.95, **okw))):
+        ref = R.lossgrad_ref(d, form, True, lam)
+        _, _, dl_o, dv_o, pil, vl = want
+        _pinned(ref["dlogits"], dl_o, form + " dlogits")
+        _pinned(ref["dv"], dv_o, form + " dv")
+        _pinned(ref["dh"], dh_of(dl_o, dv_o), form + " dfc")
+        assert np.allclose(ref["loss"].sum(0), [pil, vl], rtol=1e-6, atol=0)
+        assert (ref["dh"][~valid] == 0).all() and (ref["dlogits"][~valid] == 0).all()
+    assert not close_normscaled(R.lossgrad_ref(d, "nstep", False)["dlogits"], R.lossgrad_ref(d, "nstep", True)["dlogits"],
+                                1e-3)[0]   # (the scale does something on this window)
+    pargs = (dn, d["v"], d["probs"], d["logp"], d["actions"], d["logp_old"], d["adv"], d["ret"])
+    for form, o in (("ppo", ppo_ref.lossgrad(*pargs, R.PPO_CLIP, c["beta"], c["pi_loss_coef"], c["vcoef"], True)),
+                    ("ppo_vc", ppo_options_ref.lossgrad_vclip(*pargs, d["v_old"], R.PPO_CLIP, R.PPO_VCLIP, c["beta"],
+                                                              c["pi_loss_coef"], c["vcoef"], True))):
+        ref = R.lossgrad_ref(d, form, True)
+        for k in ("dlogits", "dv", "loss", "ratio"):
+            _pinned(ref[k], o[k], f"{form} {k}")
+        _pinned(ref["dh"], dh_of(o["dlogits"], o["dv"]), form + " dfc")
+        assert 0 < o["active"].sum() < valid.sum() and (ref["ratio"][~valid] == 0).all()
+        if form == "ppo_vc":
+            assert o["taken"].any() and o["inside"].any() and o["outside_kept"].any() and (ref["dv"][o["taken"]] == 0).all()
+
+
+def test_fused_bootstrap_ref_equals_oracle():
+    """fused_bootstrap_ref against the oracle's f32 FC, heads and softmax of slot T and its
+    returns_and_lossgrad with that value as the bootstrap, within 1e-6 of the scale."""
+    d = R.fused_data(8, 5, 3)
+    T, c = d["T"], R.COEF
+    hT, pol, (dl, dv, loss, dfc) = R.fused_bootstrap_ref(
+        d["a2T"], d["Wfc"], d["bfc"], d["Wpi"], d["bpi"], d["Wv"], d["bv"], d["rewards"], d["dones"], d["v"], d["probs"],
+        d["logp"], d["actions"], d["hfc"][:T], gamma=c["gamma"], beta=c["beta"], vcoef=c["vcoef"],
+        pi_loss_coef=c["pi_loss_coef"], keep_loss_scale_same=True)
+    h_o = np.maximum(O.linear(d["a2T"], d["Wfc"], d["bfc"]), 0)
+    lo, v_o = O.linear(h_o, d["Wpi"], d["bpi"]), O.linear(h_o, d["Wv"], d["bv"])[:, 0]
+    for got, want, what in ((hT, h_o, "hfc[T]"), (pol["logits"], lo, "logits"), (pol["v"], v_o, "v[T]"),
+                            (pol["probs"], O.softmax(lo), "probs"), (pol["logp"], O.log_softmax(lo), "logp")):
+        _pinned(got, want, what)
+    _, _, dl_o, dv_o, pil, vl = O.returns_and_lossgrad(
+        d["rewards"], d["dones"], d["v"][:T], v_o, d["probs"], d["logp"], d["actions"], gamma=c["gamma"], beta=c["beta"],
+        v_loss_coef=c["vcoef"], pi_loss_coef=c["pi_loss_coef"], keep_loss_scale_same=True)
+    _pinned(dl, dl_o, "dlogits")
+    _pinned(dv, dv_o, "dv")
+    _pinned(dfc, (dl_o @ d["Wpi"] + dv_o[..., None] * d["Wv"][0]) * (d["hfc"][:T] > 0), "dfc")
+    assert np.allclose(loss.sum(0), [pil, vl], rtol=1e-6, atol=0)
+    assert (np.abs(d["zT"]) >= R.MARGIN * np.abs(d["zT"]).max()).all() and (d["zT"] < 0).any()
+    assert not np.array_equal(d["v"][T], pol["v"].astype(np.float32))
+
+
+def test_lossgrad_data_keeps_every_decision_off_its_threshold():
+    """Every sample of every GPU case, truncated ones included: near_threshold is empty (lossgrad_data redraws,
+    nothing is exempted), both signs of adv, exact zeros in it, and on both sides of every PPO threshold."""
+    cases = [(c, None) for c in R.RETURNS_CASES] + R.TRUNC_CASES
+    n = {k: 0 for k in ("pos", "neg", "zero", "below", "between", "above", "inside", "outside")}
+    lo, hi = R.clip_range(R.PPO_CLIP)
+    for case, t_len in cases:
+        d = R.lossgrad_data(*case, t_len=t_len)
+        assert not R.near_threshold(d).any()
+        T = d["T"]
+        lpa = np.take_along_axis(d["logp"], d["actions"][..., None].astype(np.int64), 2)[..., 0]
+        rho = np.exp(np.asarray(lpa, np.float64) - d["logp_old"])
+        dvo = np.abs(np.asarray(d["v"][:T], np.float64) - d["v_old"])
+        for k, m in (("pos", d["adv"] > 0), ("neg", d["adv"] < 0), ("zero", d["adv"] == 0), ("below", rho < lo),
+                     ("between", (rho > lo) & (rho < hi)), ("above", rho > hi), ("inside", dvo < R.PPO_VCLIP),
+                     ("outside", dvo > R.PPO_VCLIP)):
+            n[k] += int(m.sum())
+        if d["adv"].size >= 24:
+            assert (d["adv"] > 0).any() and (d["adv"] < 0).any() and (d["adv"] == 0).any()
+    total = n["pos"] + n["neg"] + n["zero"]
+    print(n)
+    assert all(v > 0 for v in n.values()) and n["zero"] < 0.2 * total
+    for case in R.FUSED_CASES:
+        z = R.fused_data(*case)["zT"]
+        assert (np.abs(z) >= R.MARGIN * np.abs(z).max()).all()
+
+
+def _run_mistakes(d, form, keep, lam, lstm):
+    """{mistake: perturbed reference} of one heads-kernel run: every mistake of the issue's list that can show on
+    the run's data; the comments say when one cannot."""
+    T = d["T"]
+    dn = d["dones_t"].astype(np.int64)
+    term, live = (dn & 1) != 0, (dn & 2) == 0
+    ref = R.lossgrad_ref(d, form, keep, lam, lstm)
+    out = {}
+
+    def run(m):
+        return R.lossgrad_ref(d, form, keep, lam, lstm, mistake=m)
+
+    if form == "gae":
+        # step RW - 1 must exist, be live and not a terminal (else v[k + 1] is not read there): not at T < RW,
+        # not in the T = 8 window truncated to 5 steps
+        if T >= R.RW and (live & ~term)[R.RW - 1].any():
+            out["v[k + 1] from v[k] at k = RW - 1"] = run("vnext_rw")
+        # step T - 1 must be live and not a terminal: not in a truncated window, not in the one-sample case
+        if (live & ~term)[T - 1].any():
+            out["bootstrap value dropped from the last delta"] = run("no_boot")
+        # G is carried only at lambda > 0, and across a terminal only where one has a live step before it
+        if lam > 0 and term[1:].any():
+            out["a terminal not cutting G"] = run("keep_G")
+        # gl multiplies a carried G: a live step that is not a terminal below another live one (not at T = 1)
+        if (live[:-1] & ~term[:-1]).any():
+            out["gamma where gl belongs"] = R.lossgrad_ref(d, form, keep, 1.0, lstm)
+    if form in ("ppo", "ppo_vc"):
+        rho, adv = ref["ratio"], np.asarray(d["adv"], np.float64)
+        lo, hi = R.clip_range(R.PPO_CLIP)
+        # a live sample with adv < 0 whose ratio is outside [lo, hi]: there the two sides decide differently
+        if (live & (adv < 0) & ((rho > hi) | (rho < lo))).any():
+            out["the clip on the wrong side for adv < 0"] = run("neg_side")
+        # only the gradient changes, which is identically 0 with one action (the one-sample case)
+        if d["A"] > 1 and (live & (adv != 0)).any():
+            out["the ratio not applied to the gradient"] = run("no_ratio")
+        if (live & (adv != 0)).any():
+            out["lo / hi swapped"] = run("swap")
+    if form == "ppo_vc":
+        v, vo, Rf = (np.asarray(x, np.float64) for x in (d["v"][:T], d["v_old"], d["ret"]))
+        ev = np.float64(np.float32(R.PPO_VCLIP))
+        lu, lc, lw = (v - Rf) ** 2, (vo - ev - Rf) ** 2, (vo + ev - Rf) ** 2
+        taken = live & (ref["dv"] == 0) & (v != Rf)
+        # a live sample whose clipped square is the larger one
+        if taken.any():
+            out["a clipped-away value sample keeping its gradient"] = run("vc_grad")
+        # a live sample below v_old - ev on which the larger square changes: where the unclipped square is the
+        # largest of the three (ret above v_old + ev), the loss and the gradient are the unclipped ones either way
+        if (live & (v - vo < -ev) & (np.maximum(lu, lc) != np.maximum(lu, lw))).any():
+            out["v_old + ev where v_old - ev belongs"] = run("vc_plus")
+    if T > 32:
+        again = dict(ref)
+        again["dh"] = ref["dh"].copy()
+        again["dh"][32:] = ref["dh"][:T - 32]
+        out["rows >= 32 given rows 0..'s dh"] = again
+    if not live.all():   # the dead rows' dh as if they were live steps
+        asif = R.lossgrad_ref({**d, "dones_t": (dn & 1).astype(np.uint8)}, form, keep, lam, lstm)
+        kept = dict(ref)
+        kept["dh"] = np.where(live[..., None], ref["dh"], asif["dh"])
+        out["a truncated row's dh not zeroed"] = kept
+    # an env with two live terminals: the second one's segment starts after the first
+    if keep and ((term & live).sum(0) >= 2).any():
+        out["seg_start ignoring the terminal before t"] = run("seg_start")
+    return ref, out
+
+
+LOSSGRAD_MISTAKES = 12   # of the issue's 13; the 13th is the fused form's, below
+
+
+def test_lossgrad_tolerance_catches_mistakes():
+    """Every mistake of _run_mistakes on every heads-kernel run's own data, keep_loss_scale_same off and on, misses
+    close_normscaled(1e-5) by more than 10x; each of the mistakes is shown by at least one run.  Prints the
+    smallest ratio of each."""
+    worst = {}
+    for case, form, lam, t_len, lstm in R.lossgrad_runs():
+        d = R.lossgrad_data(*case, lstm=lstm, t_len=t_len)
+        for keep in (False, True):
+            ref, perts = _run_mistakes(d, form, keep, lam, lstm)
+            for what, pert in perts.items():
+                f = _worst([pert[k] for k in ref], [ref[k] for k in ref])
+                assert f >= 10, (what, case, form, lam, t_len, keep, f)
+                worst[what] = min(worst.get(what, np.inf), f)
+    for what, f in worst.items():
+        print(f"lossgrad {what}: at least {f:.3g} x the bound")
+    assert len(worst) == LOSSGRAD_MISTAKES, sorted(worst)
+
+
+def test_fused_tolerance_catches_the_wrong_bootstrap_slot():
+    """The fused form bootstrapping from slot T - 1's value (the last the policy stored before it) instead of its
+    own row's: more than 10x the bound on every fused case (each has an env whose last step is no terminal)."""
+    worst = np.inf
+    for case in R.FUSED_CASES:
+        d = R.fused_data(*case)
+        T, c = d["T"], R.COEF
+        assert (d["dones"][T - 1] == 0).any()
+        for lam in (1.0, R.GAE_LAMBDA):
+            for keep in (False, True):
+                kw = dict(gamma=c["gamma"], beta=c["beta"], vcoef=c["vcoef"], pi_loss_coef=c["pi_loss_coef"],
+                          keep_loss_scale_same=keep, lam=lam)
+                args = (d["probs"], d["logp"], d["actions"], d["Wpi"], d["Wv"], d["hfc"][:T])
+                ref = R.fused_bootstrap_ref(d["a2T"], d["Wfc"], d["bfc"], d["Wpi"], d["bpi"], d["Wv"], d["bv"], d["rewards"],
+                                            d["dones"], d["v"], d["probs"], d["logp"], d["actions"], d["hfc"][:T], **kw)[2]
+                vb = np.concatenate([d["v"][:T], d["v"][T - 1:T]])
+                f = _worst(R.returns_heads_ref(d["rewards"], d["dones"], vb, *args, **kw), ref)
+                assert f >= 10, (case, lam, keep, f)
+                worst = min(worst, f)
+    print(f"fused bootstrapping from slot T - 1: at least {worst:.3g} x the bound")
