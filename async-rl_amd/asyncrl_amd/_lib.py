@@ -65,6 +65,7 @@ SIGNATURES = {
     "arl_net_set_weight_decay": (c_int, [c_void_p, c_double]),
     "arl_net_set_gae": (c_int, [c_void_p, c_double]),
     "arl_net_set_ppo": (c_int, [c_void_p, c_void_p, c_double]),
+    "arl_net_set_ppo_state": (c_int, [c_void_p, c_void_p]),
     "arl_ppo_begin": (c_int, [c_void_p, c_double, c_int, c_void_p]),
     "arl_ppo_learn": (c_int, [c_void_p, c_double, c_double, c_void_p]),
     "arl_ppo_snapshot": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_double,

@@ -222,8 +222,11 @@ class A3C:
         (PPO) epochs on the window's rollout (an extension; DeviceNet.set_ppo,
         DESIGN.md "PPO epochs"): K gradient steps, the slots re-forwarded from
         the frame ring before epochs 2..K; ppo_clip is the ratio's clip range.
-        FF models with the NIPS head, one rank.  The default 1 runs exactly
-        what ran without it and never touches set_ppo.
+        FF or LSTM models with the NIPS head, one rank; on the LSTM the
+        re-forward starts from the window's own initial recurrent state and
+        the next window from the rollout's final one (DESIGN.md "PPO epochs
+        on the LSTM").  The default 1 runs exactly what ran without it and
+        never touches set_ppo.
         gae_lambda: GAE(lambda) advantages in the policy term (an extension,
         the reference has none; DeviceNet.set_gae).  The default 1 is the
         reference's n-step advantage and runs exactly what ran without it.
@@ -287,7 +290,7 @@ class A3C:
         if self.ppo_epochs > 1:
             if self.collectives:
                 raise ValueError("A3C: ppo_epochs > 1 runs on one rank (collectives=False)")
-            self.net.set_ppo(self.ppo_clip)   # (refuses the LSTM and the Nature head)
+            self.net.set_ppo(self.ppo_clip)   # (an LSTM also gets its carry buffer; refuses the Nature head)
         self.ppo_norm_adv = bool(ppo_norm_adv)
         self.ppo_vclip = None if ppo_vclip is None else float(ppo_vclip)
         if self.ppo_norm_adv or self.ppo_vclip is not None:   # (the default never touches set_ppo_options)
@@ -393,7 +396,8 @@ class A3C:
     def _update_ppo(self, stream=None):
         """K epochs on the window's rollout: the snapshot, then per epoch [the
         slots' forward again with the current parameters, over all envs on
-        one stream,] the PPO gradient and one update; the last ends the window."""
+        one stream, t ascending (the LSTM's slot t reads slot t - 1's state),]
+        the PPO gradient and one update; the last ends the window."""
         net, K = self.net, self.ppo_epochs
         net.ppo_begin(self.gamma, self.clip_reward, stream=stream)
         for j in range(1, K + 1):

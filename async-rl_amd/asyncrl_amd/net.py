@@ -360,17 +360,27 @@ class DeviceNet:
     # ------------------------------------------------------------ PPO epochs
     ppo_snap = None   # (4, t_max, n_envs) f32: logp_old, adv, ret, ratio; allocated by the first set_ppo
     ppo_clip = None   # clip_eps while PPO is on, else None
+    ppo_carry = None  # LSTM: (2, n_envs, 256) f32, the rollout's (h_T, c_T) of the window; allocated by the first set_ppo
 
     def set_ppo(self, clip_eps: float | None = 0.2):
         """Run the window's update as clipped-surrogate epochs (arl_net_set_ppo):
         ppo_begin after the bootstrap forward, then per epoch [act(t, mode=0)
-        for t < t_max,] ppo_learn and optimize.  FF nets with the NIPS head
-        only.  None switches it off.  run_window (the one-call window) refuses
-        while it is on."""
+        for t < t_max, t ascending,] ppo_learn and optimize.  FF and LSTM nets
+        with the NIPS head; an LSTM also registers its carry buffer
+        (arl_net_set_ppo_state), so the next window starts from the rollout's
+        recurrent state whatever the epoch count.  None switches it off.
+        run_window (the one-call window) refuses while it is on."""
+        lstm = self.base_arch == ARCH_LSTM
         if clip_eps is None:
             check(lib.arl_net_set_ppo(self._h, None, 0.0), "arl_net_set_ppo")
+            if lstm and self.ppo_carry is not None:
+                check(lib.arl_net_set_ppo_state(self._h, None), "arl_net_set_ppo_state")
             self.ppo_clip = None
             return
+        if lstm:
+            if self.ppo_carry is None:
+                self.ppo_carry = torch.zeros((2, self.n_envs, 256), dtype=torch.float32, device=self.device)
+            check(lib.arl_net_set_ppo_state(self._h, ptr(self.ppo_carry)), "arl_net_set_ppo_state")
         if self.ppo_snap is None:
             self.ppo_snap = torch.zeros((4, self.t_max, self.n_envs), dtype=torch.float32, device=self.device)
         check(lib.arl_net_set_ppo(self._h, ptr(self.ppo_snap), float(clip_eps)), "arl_net_set_ppo")

@@ -458,6 +458,27 @@ int arl_net_set_gae(arl_net* h, double lambda) {
   return ARL_OK;
 }
 
+// the nets that run PPO epochs: FF with the NIPS head; the LSTM once it has a carry buffer (arl_net_set_ppo_state)
+static bool ppo_arch_ok(const arl::Net& n) {
+  return n.arch == arl::ARCH_FF || (n.arch == arl::ARCH_LSTM && n.ppo_carry != nullptr);
+}
+static const char* const PPO_ARCH_REFUSAL =
+    "FF nets with the NIPS head only (the LSTM needs a carry buffer first, arl_net_set_ppo_state; not the Nature head)";
+
+int arl_net_set_ppo_state(arl_net* h, float* carry) {
+  if (!h) return fail(ARL_EINVAL, "null net");
+  arl::Net& n = h->net;
+  if (n.arch != arl::ARCH_LSTM) return fail(ARL_ESTATE, "set_ppo_state: LSTM nets only (an FF net carries no state)");
+  if (!carry) {
+    if (n.ppo_snap) return fail(ARL_ESTATE, "set_ppo_state: PPO is set on the net, switch it off first (arl_net_set_ppo)");
+    n.ppo_carry = nullptr;
+    return ARL_OK;
+  }
+  if (!aligned(carry, 16)) return fail(ARL_EINVAL, "set_ppo_state: carry must be 16-byte aligned");
+  n.ppo_carry = carry;
+  return ARL_OK;
+}
+
 int arl_net_set_ppo(arl_net* h, float* snap, double clip_eps) {
   if (!h) return fail(ARL_EINVAL, "null net");
   arl::Net& n = h->net;
@@ -468,8 +489,7 @@ int arl_net_set_ppo(arl_net* h, float* snap, double clip_eps) {
   }
   if (!(clip_eps > 0.0 && clip_eps < 1.0)) return fail(ARL_EINVAL, "set_ppo: clip_eps must be finite and in (0, 1)");
   if (!aligned(snap, 16)) return fail(ARL_EINVAL, "set_ppo: snap must be 16-byte aligned");
-  if (n.arch != arl::ARCH_FF)
-    return fail(ARL_ESTATE, "set_ppo: FF nets with the NIPS head only (not the LSTM, not the Nature head)");
+  if (!ppo_arch_ok(n)) return fail(ARL_ESTATE, std::string("set_ppo: ") + PPO_ARCH_REFUSAL);
   n.ppo_snap = snap;
   n.ppo_lo = (float)(1.0 - clip_eps);
   n.ppo_hi = (float)(1.0 + clip_eps);
@@ -488,8 +508,7 @@ int arl_net_set_ppo_options(arl_net* h, int norm_adv, double vclip_eps, float* v
   if (!aligned(v_old, 16) || !aligned(aux, 8))
     return fail(ARL_EINVAL, "set_ppo_options: v_old must be 16-byte and aux 8-byte aligned");
   const bool on = norm_adv || vclip_eps > 0.0 || aux;
-  if (on && n.arch != arl::ARCH_FF)
-    return fail(ARL_ESTATE, "set_ppo_options: FF nets with the NIPS head only (not the LSTM, not the Nature head)");
+  if (on && !ppo_arch_ok(n)) return fail(ARL_ESTATE, std::string("set_ppo_options: ") + PPO_ARCH_REFUSAL);
   n.ppo_norm_adv = norm_adv != 0;
   n.ppo_vold = vclip_eps > 0.0 ? v_old : nullptr;
   n.ppo_ev = (float)vclip_eps;

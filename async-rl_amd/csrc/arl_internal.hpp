@@ -287,7 +287,10 @@ struct Net {
   float ppo_ev = 0.f;
   double* ppo_aux = nullptr;
   int ppo_epoch = 0;
-  int hid;               // width of the layer the heads read (256 NIPS / LSTM, 512 Nature)
+  // arl_net_set_ppo_state (LSTM): non-null = the carry buffer, 2 planes (h, c) of N * HID f32.  arl_ppo_begin saves
+  // rows T of hbuf / cbuf there; the advancing update puts them back before anything advances (net_ppo_restore)
+  float* ppo_carry = nullptr;
+  int hid;              // width of the layer the heads read (256 NIPS / LSTM, 512 Nature)
   int env_offset;          // global id of env 0 on this rank (RNG stream)
   uint64_t seed;
   std::vector<ParamInfo> params;
@@ -686,6 +689,9 @@ hipError_t launch_ppo_vold(const uint8_t* dones, const float* v, float* vold, in
 hipError_t launch_ppo_normalize_adv(const uint8_t* dones, float* adv, int T, int n, double* moments, hipStream_t s);
 hipError_t launch_ppo_epoch_stats(const PpoLossArgs& p, const int64_t* ctl, double window, double epoch, int64_t* count,
                                   double* rec, hipStream_t s);
+// The LSTM's recurrent carry of a PPO window (ppo_state.hip): rows T of hbuf / cbuf -> carry (planes h then c,
+// n * HID f32 each), or with restore the other way; one launch moves both planes.
+hipError_t launch_ppo_carry(float* hbuf, float* cbuf, float* carry, int T, int n, bool restore, hipStream_t s);
 // launch_policy_fc of the bootstrap slot (no draw) + launch_returns_heads for the same n envs, one launch
 // (policy.hip policy_fc_returns_kernel; v(s_T) handed over in LDS); bit-identical to the two launches
 hipError_t launch_policy_fc_returns(const float* slab, int n, const float* fc_bias, float* hfc, const PolicyArgs& pa,

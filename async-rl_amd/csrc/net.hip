@@ -587,7 +587,8 @@ hipError_t net_learn(Net& net, double gamma, float beta, float vcoef, int clip_r
   return hipSuccess;
 }
 
-// PPO epochs (arl_net_set_ppo; FF nets): the window's snapshot from the workspace, after its bootstrap forward
+// PPO epochs (arl_net_set_ppo; FF nets, and LSTM nets with a carry buffer): the window's snapshot from the
+// workspace, after its bootstrap forward
 hipError_t net_ppo_begin(Net& net, double gamma, int clip_reward, hipStream_t s) {
   const int64_t S = (int64_t)net.T * net.N;
   float* snap = net.ppo_snap;
@@ -598,6 +599,12 @@ hipError_t net_ppo_begin(Net& net, double gamma, int clip_reward, hipStream_t s)
   net.ppo_begun = true;
   net.ppo_epoch = 0;
   ARL_TRY(stamp(net, STAGE_OTHER, s));
+  // LSTM: the rollout's (h_T, c_T), before the re-forwards of epochs >= 2 overwrite rows T (net_ppo_restore)
+  if (net.arch == ARCH_LSTM) {
+    if (net.ppo_carry == nullptr) return hipErrorInvalidValue;   // (arl_net_set_ppo refuses an LSTM without one)
+    ARL_TRY(launch_ppo_carry(net.at<float>(net.w_hbuf), net.at<float>(net.w_cbuf), net.ppo_carry, net.T, net.N, false, s));
+    ARL_TRY(stamp(net, STAGE_OTHER, s));
+  }
   // arl_net_set_ppo_options: v_old of the window, then the adv plane normalised in place (each with a stamp
   // of its own; with the options off nothing more is launched)
   if (net.ppo_vold != nullptr) {
@@ -765,9 +772,20 @@ hipError_t net_stage(Net& net, int stage, int t, hipStream_t s) {
   }
 }
 
+// The carry of a PPO window on the LSTM: rows T of hbuf / cbuf back to the rollout's (h_T, c_T) that
+// net_ppo_begin saved, before anything advances -- the last epoch's BPTT and heads weight gradient read the
+// re-forwarded rows T, so this belongs to the update, not to net_ppo_learn.  FF nets, and windows without a
+// snapshot: nothing is launched.
+static hipError_t net_ppo_restore(Net& net, hipStream_t s) {
+  if (net.arch != ARCH_LSTM || !net.ppo_begun || net.ppo_carry == nullptr) return hipSuccess;
+  ARL_TRY(launch_ppo_carry(net.at<float>(net.w_hbuf), net.at<float>(net.w_cbuf), net.ppo_carry, net.T, net.N, true, s));
+  return stamp(net, STAGE_OTHER, s);
+}
+
 hipError_t net_optimize(Net& net, double lr0, int64_t total_steps, int64_t n_total, double alpha, double eps,
                         float clip, hipStream_t s, bool advance) {
   double* parts = net.at<double>(net.w_norm);
+  if (advance) ARL_TRY(net_ppo_restore(net, s));
   const bool do_clip = clip > 0.f;
   // arl_learn left the step snapshot (returns kernel), so the update kernel
   // can also advance the window
@@ -821,6 +839,7 @@ hipError_t net_optimize(Net& net, double lr0, int64_t total_steps, int64_t n_tot
 hipError_t net_advance(Net& net, hipStream_t s) {
   const bool L = net.arch == ARCH_LSTM;
   const int64_t cnt = L ? (int64_t)net.N * HID : net.N;
+  ARL_TRY(net_ppo_restore(net, s));
   net.ppo_begun = false;
   hipLaunchKernelGGL(advance_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, net.at<int64_t>(net.w_ctl),
                      net.T, net.at<uint8_t>(net.w_reset), net.N, L ? net.at<float>(net.w_hbuf) : nullptr,

@@ -315,8 +315,9 @@ int arl_net_set_gae(arl_net* net, double lambda);
  * caller-owned, 16-byte aligned, planes (t_max, n_envs) in this order: logp_old,
  * adv, ret, ratio.  NULL switches it off.  Host state of the handle, like
  * arl_net_set_adam (works on an unbound handle).  clip_eps not finite or outside
- * (0, 1), a misaligned snap: ARL_EINVAL.  Only FF nets with the NIPS head
- * (whatever their observation flag); the LSTM and the Nature head: ARL_ESTATE.
+ * (0, 1), a misaligned snap: ARL_EINVAL.  FF nets with the NIPS head, and LSTM
+ * nets that have a carry buffer (arl_net_set_ppo_state below), whatever their
+ * observation flag; an LSTM without one and the Nature head: ARL_ESTATE.
  * While set, the bootstrap arl_act does not fuse the returns
  * (arl_net_set_returns_fusion is ignored) and arl_run_window returns ARL_ESTATE:
  * a single-call window has no epochs.
@@ -327,7 +328,8 @@ int arl_net_set_gae(arl_net* net, double lambda);
  *   for j = 1 .. K:
  *     j > 1: arl_act_mode(net, t, 0, stream), t = 0 .. t_max - 1    re-forward from the frame ring;
  *            mode 0 touches neither actions nor the Philox counters; the bootstrap slot is not
- *            re-forwarded (ret and adv are fixed)
+ *            re-forwarded (ret and adv are fixed).  LSTM: t ascending is part of the contract,
+ *            slot t reads the state slot t - 1 wrote
  *     arl_ppo_learn(net, beta, v_loss_coef, stream)       loss gradient + heads dh, then
  *                                                         ARL_LEARN_TRUNK and ARL_LEARN_CONV
  *     arl_optimize (j < K) / arl_optimize_advance (j == K)
@@ -342,8 +344,37 @@ int arl_net_set_gae(arl_net* net, double lambda);
  * that epoch's losses; returns and advantages recomputed from the current v).
  * Fields 12 / 13 (adv_sum, adv_sumsq) stay the un-normalised advantage whatever
  * arl_net_set_ppo_options sets.
- * Not built: minibatches within an epoch, several ranks. */
+ *
+ * The LSTM (ARL_ARCH_LSTM).  Rollout, snapshot, loss gradient and epoch record
+ * are the FF net's: they read v, log_probs, probs, actions and dones only.
+ *   Re-forward.  The LSTM step of slot t reads rows t of hbuf / cbuf / reset and
+ * writes rows t + 1, and nothing writes rows 0 between two advances; so
+ * arl_act_mode(net, t, 0, stream) for t = 0 .. t_max - 1 ascending recomputes the
+ * window from the window's own initial state (rows 0 and the reset rows as the
+ * rollout left them) with the current parameters.  Reset flags and the frame
+ * ring are not touched.  BPTT is truncated to the window, as in arl_learn, on the
+ * re-forwarded gates / cbuf / hbuf rows.
+ *   Carry.  The state that enters the next window is the rollout's (h_T, c_T),
+ * computed at theta_old: the rows the advance copies when no epoch re-forwards.
+ * arl_ppo_begin saves rows T of hbuf and cbuf into the carry buffer (one launch,
+ * after the snapshot's); the advancing update (arl_optimize_advance, or
+ * arl_advance after arl_optimize) puts them back before anything advances (one
+ * launch, before the window statistics and the update), when arl_ppo_begin ran in
+ * this window.  The last epoch's BPTT and heads weight gradient read the
+ * re-forwarded rows T, which is why the restore belongs to the update: the call
+ * sequence above is the FF one unchanged.  After arl_truncate_window the same rows
+ * are saved and restored, so row 0 after the advance is bit for bit what one
+ * gradient step per window leaves.  The pi_and_v evaluation state is not touched.
+ *
+ * arl_net_set_ppo_state(net, carry): carry = 2 * n_envs * 256 f32, caller-owned,
+ * 16-byte aligned, planes h then c.  Host state of the handle (works on an
+ * unbound handle).  It is the LSTM's opt-in: arl_net_set_ppo and
+ * arl_net_set_ppo_options accept an LSTM net only once a carry buffer is set.
+ * Not an LSTM net: ARL_ESTATE.  A misaligned carry: ARL_EINVAL.  NULL unsets it;
+ * NULL while PPO is set on the net: ARL_ESTATE (switch PPO off first).
+ * Not built: the Nature head, minibatches within an epoch, several ranks. */
 int arl_net_set_ppo(arl_net* net, float* snap, double clip_eps);
+int arl_net_set_ppo_state(arl_net* net, float* carry);
 int arl_ppo_begin(arl_net* net, double gamma, int clip_reward, void* stream);
 int arl_ppo_learn(arl_net* net, double beta, double v_loss_coef, void* stream);
 
