@@ -134,6 +134,10 @@ SIGNATURES = {
     "arl_breakout_reset": (c_int, [c_void_p, c_i64, c_int, c_u64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "arl_breakout_step": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_int, c_u64, c_int, c_void_p, c_void_p, c_void_p,
                                   c_void_p]),
+    "arl_pong_state_bytes": (c_i64, [c_i64]),
+    "arl_pong_reset": (c_int, [c_void_p, c_i64, c_int, c_u64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "arl_pong_step": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_int, c_u64, c_int, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
     "arl_net_set_env": (c_int, [c_void_p, c_int, c_void_p]),
     "arl_env_reset": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "arl_env_step": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
@@ -166,6 +170,17 @@ ENV_BREAKOUT = 2       # ARL_ENV_BREAKOUT: the device-resident Breakout
 ENV_GAME_OVER_ONLY = 0x100   # ARL_ENV_GAME_OVER_ONLY, or'ed into the Breakout kind: a life loss is not a terminal
 BREAKOUT_STATE_INTS = 16     # [bx, by, vx, vy, px, lives, serves, steps_in_episode, game, game_steps, score,
                              #  bricks_left, b0, b1, b2, b3]
+ENV_PONG = 4                 # ARL_ENV_PONG: the device-resident Pong; its kind carries the points of a game
+PONG_STATE_INTS = 12         # [bx, by, vx, vy, py, oy, serves, steps_in_episode, game, game_steps, score_agent,
+                             #  score_opp]
+PONG_POINTS_MAX = 21
+
+
+def env_pong_points(points: int) -> int:
+    """ARL_ENV_PONG_POINTS(points): or'ed into ENV_PONG; 1..21, and 0 means 21."""
+    return points << 16
+
+
 CTL_ADAM_T = 3         # ARL_CTL_ADAM_T: the control block's count of Adam updates made (buffer "ctl", int64[16])
 EPISODE_LOG = 8        # ARL_EPISODE_LOG: episodes per env the device-side episode log keeps
 # the 8 doubles of arl_episode_stats, in order

@@ -19,7 +19,10 @@ phi pre-stage is the GPU kernel, so the adapter stops at the raw frame pair:
                  are one HIP kernel (csrc/catch.hip), so the loop env -> phi ->
                  forward -> sample -> env closes on the device;
   DeviceBreakout the same for Breakout (csrc/breakout.hip): bricks, lives,
-                 rewards of 1, 4 and 7, episodes of different lengths.
+                 rewards of 1, 4 and 7, episodes of different lengths;
+  DevicePong     and for Pong (csrc/pong.hip): an opponent, rewards of both
+                 signs inside a game, games of hundreds of steps, a
+                 background that is not black.
 
 Batched convention: a step whose action ends the episode returns
 done = 1, the reward of that step, and the FIRST pair of the next episode
@@ -33,8 +36,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from ._lib import (BREAKOUT_STATE_INTS, CATCH_STATE_INTS, ENV_BREAKOUT, ENV_CATCH, ENV_GAME_OVER_ONLY, check,
-                   lib, ptr, stream_handle)
+from ._lib import (BREAKOUT_STATE_INTS, CATCH_STATE_INTS, ENV_BREAKOUT, ENV_CATCH, ENV_GAME_OVER_ONLY, ENV_PONG,
+                   PONG_POINTS_MAX, PONG_STATE_INTS, check, env_pong_points, lib, ptr, stream_handle)
 
 SCREEN = (210, 160, 3)
 
@@ -315,6 +318,33 @@ class DeviceBreakout(_DeviceEnv):
 
     def _step(self, state, parity, actions, n, env_offset, seed, *out):   # the flags go before the outputs
         check(lib.arl_breakout_step(state, parity, actions, n, env_offset, seed, self.flags, *out), "arl_breakout_step")
+
+
+class DevicePong(_DeviceEnv):
+    """Pong on the device (include/asyncrl_hip.h, "device environment"; the
+    rules are there): DeviceCatch's surface over a game against a paddle that
+    follows the ball, played to `points` (1..21).  Every point is a reward of
+    +1 or -1 that does not end the episode; done = game over (a side reached
+    `points`, or 5,000 env-steps).  Actions: 2 and 4 = up, 3 and 5 = down,
+    anything else a no-op (n_actions >= 4; 6 is ALE Pong's minimal set).  The
+    state is (2, n, 12) int32.  points=1 gives episodes of about 11 env-steps
+    under a random policy, points=21 of about 230."""
+
+    STATE_INTS = PONG_STATE_INTS
+    _state_bytes = staticmethod(lib.arl_pong_state_bytes)
+
+    def __init__(self, n_envs: int, device=None, seed: int = 0, env_offset: int = 0, points: int = 21):
+        if not 1 <= points <= PONG_POINTS_MAX:
+            raise ValueError(f"DevicePong: points must be in 1..{PONG_POINTS_MAX}")
+        super().__init__(n_envs, device, seed, env_offset)
+        self.points = int(points)
+        self.kind = ENV_PONG | env_pong_points(self.points)
+
+    def _reset(self, *args):
+        check(lib.arl_pong_reset(*args), "arl_pong_reset")
+
+    def _step(self, state, parity, actions, n, env_offset, seed, *out):   # the points go before the outputs
+        check(lib.arl_pong_step(state, parity, actions, n, env_offset, seed, self.points, *out), "arl_pong_step")
 
 
 class _null:

@@ -599,11 +599,27 @@ int arl_breakout_step(int32_t* state, int parity_in, const int32_t* actions, int
                       pair_out, reward_out, done_out, s);
 }
 
+int64_t arl_pong_state_bytes(int64_t n_envs) { return env_state_bytes(ARL_ENV_PONG, n_envs); }
+
+int arl_pong_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, int parity, uint8_t* pair_out,
+                   float* reward_out, uint8_t* done_out, void* s) {
+  return env_granular("pong_reset", ARL_ENV_PONG, state, parity, nullptr, false, n, env_offset, seed, pair_out,
+                      reward_out, done_out, s);
+}
+
+int arl_pong_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
+                  int points, uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* s) {
+  if (points < 1 || points > arl::PONG_POINTS_MAX) return fail(ARL_EINVAL, "pong_step: points out of [1, 21]");
+  return env_granular("pong_step", ARL_ENV_PONG | ARL_ENV_PONG_POINTS(points), state, parity_in, actions, true, n,
+                      env_offset, seed, pair_out, reward_out, done_out, s);
+}
+
 int arl_net_set_env(arl_net* h, int kind, int32_t* state) {
   if (!h) return fail(ARL_EINVAL, "null net");
   if (!arl::env_kind_ok(kind))
     return fail(ARL_EINVAL,
-                "set_env: unknown env kind (ARL_ENV_CATCH, or ARL_ENV_BREAKOUT [| ARL_ENV_GAME_OVER_ONLY])");
+                "set_env: unknown env kind (ARL_ENV_CATCH, ARL_ENV_BREAKOUT [| ARL_ENV_GAME_OVER_ONLY], or "
+                "ARL_ENV_PONG | ARL_ENV_PONG_POINTS(0..21))");
   if (!state) {   // detach
     h->net.env_state = nullptr;
     return ARL_OK;
@@ -611,7 +627,9 @@ int arl_net_set_env(arl_net* h, int kind, int32_t* state) {
   const arl::Net& n = h->net;
   if (n.rgb || n.stack || n.states)
     return fail(ARL_ESTATE, "set_env: the env renders frame pairs (FF / LSTM / FF_NATURE nets without a frames flag)");
-  if (n.A < 4) return fail(ARL_EINVAL, "set_env: the env needs n_actions >= 4 (NOOP / FIRE / RIGHT / LEFT)");
+  if (n.A < 4)
+    return fail(ARL_EINVAL,
+                "set_env: the env needs n_actions >= 4 (NOOP / FIRE / RIGHT / LEFT; Pong: NOOP / FIRE / UP / DOWN)");
   if (!aligned(state, 16)) return fail(ARL_EINVAL, "set_env: state must be 16-byte aligned");
   h->net.env_state = state;
   h->net.env_kind = kind;

@@ -138,13 +138,15 @@ hipError_t launch_episode_reset(char* block, int n, hipStream_t s);
 // envs in a fixed order (phi.hip episode_reduce_kernel); clear: also zero the cumulative per-env arrays
 hipError_t launch_episode_reduce(char* block, int n, double* out8, int clear, hipStream_t s);
 
-// Device-resident envs (env_kernel.hpp, with the games in catch.hip and breakout.hip; the header's "device
+// Device-resident envs (env_kernel.hpp, with the games in catch.hip, breakout.hip and pong.hip; the header's "device
 // environment"): one launch = one env-step (or the reset) of envs [e0, e0 + ne): transition + render into pool
 // entry (k + 1) % pool_len (reset: k % pool_len), k = ctl[CTL_STEP] + t read on the device; the state half read
 // is k & 1, the half written (k + 1) & 1.
 constexpr int CATCH_STATE_INTS = 8;       // [bx, by, vx, px, episode, steps_in_episode, 0, 0]
 constexpr int BREAKOUT_STATE_INTS = 16;   // [bx, by, vx, vy, px, lives, serves, steps_in_episode, game, game_steps,
                                           //  score, bricks_left, b0, b1, b2, b3]
+constexpr int PONG_STATE_INTS = 12;       // [bx, by, vx, vy, py, oy, serves, steps_in_episode, game, game_steps,
+                                          //  score_agent, score_opp]
 struct EnvArgs {
   int32_t* state;            // (2, n, the game's STATE_INTS), 16-byte aligned
   const int32_t* actions;    // (n): the actions of observation k; null: reset (episode 0 into half k & 1)
@@ -158,20 +160,35 @@ struct EnvArgs {
   int e0 = 0, ne = -1;       // env range of this launch: e0 + blockIdx.y, ne envs (-1: all n)
   int env_offset = 0;
   uint32_t seed_lo = 0, seed_hi = 0;
-  int flags = 0;             // ARL_ENV_GAME_OVER_ONLY or 0, filled by launch_env from the kind (Catch ignores it)
+  int flags = 0;             // filled by launch_env from the kind: Breakout's ARL_ENV_GAME_OVER_ONLY or 0, Pong's
+                             // points (1..21); Catch ignores it
 };
-struct Catch;      // the games: catch.hip and breakout.hip each instantiate their launch_game
+struct Catch;      // the games: catch.hip, breakout.hip and pong.hip each instantiate their launch_game
 struct Breakout;
+struct Pong;
 template <class Game> hipError_t launch_game(const EnvArgs& a, hipStream_t s);   // env_kernel.hpp
 extern template hipError_t launch_game<Catch>(const EnvArgs&, hipStream_t);
 extern template hipError_t launch_game<Breakout>(const EnvArgs&, hipStream_t);
+extern template hipError_t launch_game<Pong>(const EnvArgs&, hipStream_t);
 
-// The library's only look at an env kind (ARL_ENV_*, a Breakout's with an optional ARL_ENV_GAME_OVER_ONLY).
+// The library's only look at an env kind (ARL_ENV_*, a Breakout's with an optional ARL_ENV_GAME_OVER_ONLY, a
+// Pong's with its points in bits 16 and up: 1..21, 0 = 21; no other bit).
+constexpr int PONG_POINTS_MAX = 21;
 constexpr bool env_is_breakout(int kind) { return (kind & ~ARL_ENV_GAME_OVER_ONLY) == ARL_ENV_BREAKOUT; }
-constexpr bool env_kind_ok(int kind) { return kind == ARL_ENV_CATCH || env_is_breakout(kind); }
-constexpr int env_state_ints(int kind) { return env_is_breakout(kind) ? BREAKOUT_STATE_INTS : CATCH_STATE_INTS; }
+constexpr bool env_is_pong(int kind) {
+  return kind >= 0 && (kind & 0xffff) == ARL_ENV_PONG && (kind >> 16) <= PONG_POINTS_MAX;
+}
+constexpr int pong_points(int kind) { return (kind >> 16) ? (kind >> 16) : PONG_POINTS_MAX; }
+constexpr bool env_kind_ok(int kind) { return kind == ARL_ENV_CATCH || env_is_breakout(kind) || env_is_pong(kind); }
+constexpr int env_state_ints(int kind) {
+  return env_is_pong(kind) ? PONG_STATE_INTS : env_is_breakout(kind) ? BREAKOUT_STATE_INTS : CATCH_STATE_INTS;
+}
 inline hipError_t launch_env(int kind, const EnvArgs& a, hipStream_t s) {
   EnvArgs f = a;
+  if (env_is_pong(kind)) {
+    f.flags = pong_points(kind);
+    return launch_game<Pong>(f, s);
+  }
   f.flags = kind & ARL_ENV_GAME_OVER_ONLY;
   return env_is_breakout(kind) ? launch_game<Breakout>(f, s) : launch_game<Catch>(f, s);
 }

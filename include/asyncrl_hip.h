@@ -853,9 +853,87 @@ int arl_breakout_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed,
 int arl_breakout_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
                       int flags, uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* stream);
 
+/* A device-resident Pong, the third device environment: the game the A3C paper
+ * leads with, with what the other two lack -- rewards of both signs inside an
+ * episode that do not end it (the n-step return and the GAE recurrence run
+ * through a -1 that does not close the segment), an opponent (part of the
+ * dynamics is not the agent's), games of hundreds of env-steps (almost every
+ * window bootstraps, and the step cap is reached), a background that is not
+ * black, and ALE Pong's six-action minimal set with its aliased actions.  Same
+ * launch shape, pools and state protocol as Catch; additions to ABI 4.
+ *
+ * The game (exact in integer arithmetic; tests/pong_ref.py restates it).
+ * Screen 210 rows x 160 columns, RGB uint8, HWC.
+ * Background (144,72,17) everywhere not listed below.
+ * Walls (236,236,236): rows 24..33 and rows 194..203, full width.
+ * Opponent paddle (213,130,74): 4 x 16, columns 16..19, rows oy..oy+15, oy in
+ *   [34, 178].
+ * Agent paddle (92,186,92): 4 x 16, columns 140..143, rows py..py+15, py in
+ *   [34, 178].
+ * Ball (236,236,236): 4 x 4, left edge bx, top edge by in [34, 190].
+ * Draw order: the ball over a paddle, a paddle over the background.
+ * Actions (NOOP, FIRE, UP, DOWN, UPFIRE, DOWNFIRE): 2 and 4 move the agent up,
+ *   3 and 5 down, every other value is a no-op (any n_actions >= 4).  There is
+ *   no FIRE: the ball serves itself.
+ * One env-step is up to 4 frames; frame f does, in order:
+ *   1. up: py = max(py - 4, 34); down: py = min(py + 4, 178)
+ *   2. opponent: c = by + 2 - (oy + 8); c > 2: oy = min(oy + 2, 178); c < -2:
+ *      oy = max(oy - 2, 34) (it follows the ball at half the agent's speed,
+ *      with a dead zone)
+ *   3. by += vy; by < 34: by = 68 - by, vy = -vy; else by > 190: by = 380 - by,
+ *      vy = -vy
+ *   4. bx += vx
+ *   5. paddles: if vx > 0 && 136 <= bx < 139, and by + 4 > py && by < py + 16:
+ *      bx = 272 - bx, vx = -3, vy = 2 * (clamp(by + 2 - py, 0, 15) >> 2) - 3
+ *      (one of -3, -1, 1, 3); else if vx < 0 && 16 < bx <= 19, and by + 4 > oy
+ *      && by < oy + 16: bx = 40 - bx, vx = +3, vy from oy in the same way.
+ *      |vx| = 3 and the three-column windows: each crossing is tested once.
+ *   6. point: bx < 0: reward +1 (the agent scored); bx > 156: reward -1.  The
+ *      skip loop breaks in that frame.
+ * After the frames: game_steps += 1, and a point raises the scorer's count.
+ * The game is over when either count reaches `points` (1..21) or game_steps >=
+ * 5000; a new game then starts at once.
+ * New game: py = oy = 106, both counts 0, game_steps = 0, then a serve.  game
+ *   counts the games finished: 0 after the reset, += 1 at every game over.
+ * A point that does not end the game: a serve only; the paddles stay.
+ * Serve: with (w0, w1, w2, .) = philox4x32_10(counter = (env_offset + e,
+ *   serves, 0, 4), key = (seed & 0xffffffff, seed >> 32)): bx = 78, by = 34 +
+ *   w0 % 157, vy = 2 * (w1 % 4) - 3; in a new game vx = (w2 & 1) ? 3 : -3,
+ *   after a point vx points toward the side that conceded (-3 after a +1);
+ *   then serves += 1.  serves counts every serve of the env and starts at 0.
+ *   Counter word 3 = 4 is a stream beside 0 (window draws), 1 (pi_and_v
+ *   draws), 2 (Catch) and 3 (Breakout).
+ * Done = game over; there are no lives, so no ARL_ENV_GAME_OVER_ONLY.
+ * A step that serves -- a point, terminal or not, or the step cap -- writes
+ * both frames of the pair as the first screen after the serve (Catch's rule:
+ * a done observation is the first of the next episode).  Every other step
+ * writes pair[0] = the screen after frame 4, pair[1] = the screen after frame
+ * 3.  The reward is the raw +-1.0f or 0.0f.  steps_in_episode counts the
+ * env-steps since the last done.
+ * At points = 1 a uniform random policy scores about -0.37 and a game lasts
+ * about 11 env-steps; at 21 about -17 and 230.
+ *
+ * Env state: caller-owned device memory, (2, n_envs, 12) int32, 16-byte
+ * aligned, [bx, by, vx, vy, py, oy, serves, steps_in_episode, game,
+ * game_steps, score_agent, score_opp] per env, double-buffered by the parity
+ * of the observation index exactly as Catch's.
+ *
+ * The kind is ARL_ENV_PONG | ARL_ENV_PONG_POINTS(p), p in 1..21; p = 0 means
+ * 21.  Any other bit (0x100 included): ARL_EINVAL.
+ * Granular calls: Catch's trio; arl_pong_step takes points (1..21, anything
+ * else: ARL_EINVAL) where arl_breakout_step takes its flags. */
+#define ARL_ENV_PONG 4
+#define ARL_ENV_PONG_POINTS(p) ((p) << 16)
+int64_t arl_pong_state_bytes(int64_t n_envs);
+int arl_pong_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, int parity, uint8_t* pair_out,
+                   float* reward_out, uint8_t* done_out, void* stream);
+int arl_pong_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
+                  int points, uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* stream);
+
 /* Attached to a net (host state of the handle, like arl_net_set_adam; works on
  * an unbound handle): arl_net_set_env(net, kind, state) with kind =
- * ARL_ENV_CATCH, ARL_ENV_BREAKOUT or ARL_ENV_BREAKOUT | ARL_ENV_GAME_OVER_ONLY
+ * ARL_ENV_CATCH, ARL_ENV_BREAKOUT, ARL_ENV_BREAKOUT | ARL_ENV_GAME_OVER_ONLY or
+ * ARL_ENV_PONG | ARL_ENV_PONG_POINTS(p)
  * (any other value, the flag on Catch included: ARL_EINVAL) and state as above
  * for that env, the net's n_envs, its env_offset and seed; state == NULL
  * detaches.  arl_env_reset, arl_env_step and arl_run_window launch the

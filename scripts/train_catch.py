@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Closed-loop training on a device-resident env (asyncrl_amd.DeviceCatch, or DeviceBreakout with --env breakout):
-the learner has to learn.
+"""Closed-loop training on a device-resident env (asyncrl_amd.DeviceCatch, DeviceBreakout with --env breakout, or
+DevicePong with --env pong --points P): the learner has to learn.
 
 env -> phi -> forward -> sample -> env -> ... -> update runs on the device with no host work per step: window 0
 eagerly (first=True), then one captured window replayed.  Every --report windows the learning curve is read
@@ -8,7 +8,9 @@ from the device-side episode statistics (A3C.episode_stats(clear=True): the epis
 last read) together with the newest per-window record (A3C.window_stats).  The optimum is +1 per episode, a
 uniform random policy scores about -0.70.  With --env breakout an episode is a life (a life loss is terminal, as
 the reference trains), the return is the raw, unclipped sum of its brick values, and a uniform random policy
-scores about 0.14 per life.
+scores about 0.14 per life.  With --env pong an episode is a game to --points points against the opponent's paddle,
+the return is the agent's points minus the opponent's, and a uniform random policy scores about -0.36 at --points 1
+and about -17 at 21.
 
 Defaults are the reference's hyperparameters (RMSpropAsync lr 7e-4, alpha 0.99, eps 0.1, clip 40, beta 0.01,
 gamma 0.99) on the FF model with 256 envs; the batched learner sums the gradient of all envs, so --batch-loss
@@ -17,7 +19,8 @@ mean, --opt adam, --gae-lambda and --ppo-epochs (clipped-surrogate epochs on eac
 the epochs' advantage normalisation and clipped value loss on, and each row then also carries the last epoch's
 device-side record, A3C.ppo_epoch_stats) are there to try.  One JSON line at the end (and --out FILE).
 
-    python scripts/train_catch.py [--env catch|breakout] [--windows 4000] [--report 200] [--envs 256] [--seed 0]
+    python scripts/train_catch.py [--env catch|breakout|pong] [--points 21] [--windows 4000] [--report 200]
+                                  [--envs 256] [--seed 0]
                                   [--lr 7e-4] [--opt rmsprop|adam] [--batch-loss sum|mean] [--gae-lambda 1.0]
                                   [--arch ff|lstm] [--ppo-epochs 1] [--ppo-clip 0.2] [--ppo-norm-adv] [--ppo-vclip X]
 """
@@ -37,7 +40,7 @@ import asyncrl_amd as pkg  # noqa: E402
 
 def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", batch_loss="sum", gae_lambda=1.0,
           arch="ff", beta=1e-2, eps=None, device="cuda:0", log=print, env="catch", ppo_epochs=1, ppo_clip=0.2, ppo_norm_adv=False,
-          ppo_vclip=None):
+          ppo_vclip=None, points=21):
     """Returns the curve: one dict per report with the window count, the episodes completed since the last
     report and their mean return, and the newest window record's entropy / value / gradient norm."""
     dev = torch.device(device)
@@ -55,7 +58,10 @@ def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", ba
     net = model.net
     net.set_episode_stats(True)
     net.set_window_stats(True)
-    game = (pkg.DeviceBreakout if env == "breakout" else pkg.DeviceCatch)(envs, device=dev, seed=seed)
+    if env == "pong":
+        game = pkg.DevicePong(envs, device=dev, seed=seed, points=points)
+    else:
+        game = (pkg.DeviceBreakout if env == "breakout" else pkg.DeviceCatch)(envs, device=dev, seed=seed)
     pools = game.make_pools(P)
     net.set_env(game)
     stream = torch.cuda.Stream(device=dev)
@@ -98,7 +104,8 @@ def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", ba
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--env", choices=("catch", "breakout"), default="catch")
+    ap.add_argument("--env", choices=("catch", "breakout", "pong"), default="catch")
+    ap.add_argument("--points", type=int, default=21)
     ap.add_argument("--envs", type=int, default=256)
     ap.add_argument("--windows", type=int, default=4000)
     ap.add_argument("--report", type=int, default=200)
