@@ -141,6 +141,11 @@ SIGNATURES = {
     "arl_net_set_env": (c_int, [c_void_p, c_int, c_void_p]),
     "arl_env_reset": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "arl_env_step": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "arl_net_set_env_direct": (c_int, [c_void_p, c_int]),
+    "arl_env_reset_observe": (c_int, [c_void_p, c_int, c_void_p]),
+    "arl_env_step_observe": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "arl_env_step_screen": (c_int, [c_int, c_void_p, c_int, c_void_p, c_i64, c_int, c_u64, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -528,8 +528,8 @@ class A3C:
         self.t += 1
         return net.step_outputs(ta)["actions"].clone()
 
-    def run_window(self, pair_pool, reward_pool, done_pool, pool_len: int, first: bool = False, stream=None,
-                   split_update: bool = False, env_groups: int | None = None):
+    def run_window(self, pair_pool=None, reward_pool=None, done_pool=None, pool_len: int = 0, first: bool = False,
+                   stream=None, split_update: bool = False, env_groups: int | None = None):
         """One full lockstep window over device-resident pools (graph
         capturable when first=False): T x (phi, forward, sample), bootstrap,
         learn, [all-reduce], clip + RMSProp, advance.
@@ -538,6 +538,12 @@ class A3C:
         after each of the T sampled actions, on the stream of the chain that
         sampled them, into the pool entry the next observation reads: the
         pools are then written, and the loop runs without the host.
+
+        With a direct env (net.set_env(env, direct=True)) the pools may be
+        None: each step is act(t) then env_step_observe(t), one launch that
+        steps the env and writes observation t + 1 into the frame ring; there
+        is no observe except the reset form when first=True (no env_reset
+        before it).  Results are bit-identical to the pools path.
 
         env_groups=G > 1 splits the envs into G contiguous ranges whose T + 1
         forward steps run as independent chains on G streams (envs are
@@ -554,6 +560,9 @@ class A3C:
         if ppo and split_update:
             raise ValueError("run_window: split_update=True has no PPO epochs (ppo_epochs > 1)")
         groups = net.env_groups(net.default_env_groups() if env_groups is None else env_groups)
+        direct = net.env is not None and net.env_direct
+        if not direct and pair_pool is None:
+            raise ValueError("run_window: the pools may be None only with a direct env (set_env(env, direct=True))")
         if (WINDOW_C and not ppo and len(groups) == 1 and not split_update and not self.collectives
                 and net.arch == net.base_arch and net.base_arch in (ARCH_FF, ARCH_LSTM)):
             # one C call: T x (observe, act), bootstrap, learn, clip + RMSProp, advance (arl_run_window)
@@ -561,6 +570,9 @@ class A3C:
                            self._vcoef, self.clip_reward, stream=stream, **self.optimizer.update_args())
             self.t += T
             return
+        if direct and first:
+            # the reset form, all envs, ahead of every chain (the chains of a direct env never observe)
+            net.env_reset_observe(self.resize_mode, stream=stream)
         if len(groups) == 1:
             # FF: the learner's returns ride on the bootstrap policy launch (as arl_run_window does)
             fuse = FUSE_RETURNS and not ppo and net.base_arch == ARCH_FF and net.arch != ARCH_FF_NATURE
@@ -628,14 +640,20 @@ class A3C:
         ev = None
         stagger = envs is not None   # env groups: chain g starts after chain g-1's first kernel
 
+        direct = net.env is not None and net.env_direct
+
         def env_step(t):
             """An attached device env answers the actions of step t < T with the
-            pool entry the chain's next observation reads."""
+            pool entry the chain's next observation reads; a direct one with
+            that observation itself, in the frame ring."""
             if net.env is not None and t < T:
-                net.env_step(t, pair_pool, reward_pool, done_pool, pool_len, stream=stream, envs=envs)
+                if direct:
+                    net.env_step_observe(t, self.resize_mode, stream=stream, envs=envs)
+                else:
+                    net.env_step(t, pair_pool, reward_pool, done_pool, pool_len, stream=stream, envs=envs)
 
         for t in range(T + 1):
-            obs = t > 0 or first
+            obs = (t > 0 or first) and not direct   # (direct: run_window issued the reset form, env_step the rest)
             if stagger and ev is None:
                 if obs:                                # the first kernel is the observation
                     net.observe(t, pair_pool, reward_pool, done_pool, pool_len, force_reset=(t == 0),

@@ -262,6 +262,27 @@ class _DeviceEnv:
         self.parity ^= 1
         return pairs, r, d
 
+    def step_screen(self, actions, resize_mode: int = 0, stream=None):
+        """step() followed by phi's current_screen on the pair, as the one
+        launch of the direct-to-ring path (arl_env_step_screen): -> (screens
+        (n, 84, 84) uint8, r, d), bit-identical to the two calls; the frame
+        pair is never written.  The tensors are rewritten by the next call."""
+        a = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
+        if a.shape != (self.n,):
+            raise ValueError(f"{type(self).__name__}.step_screen: need {self.n} actions")
+        if self._screen_out is None:
+            self._screen_out = (torch.empty((self.n, 84, 84), dtype=torch.uint8, device=self.device),
+                                torch.empty(self.n, dtype=torch.float32, device=self.device),
+                                torch.empty(self.n, dtype=torch.uint8, device=self.device))
+        screens, r, d = self._screen_out
+        check(lib.arl_env_step_screen(self.kind, ptr(self.state), self.parity, ptr(a), self.n, self.env_offset,
+                                      self.seed, resize_mode, ptr(screens), ptr(r), ptr(d), stream_handle(stream)),
+              "arl_env_step_screen")
+        self.parity ^= 1
+        return screens, r, d
+
+    _screen_out = None
+
     def close(self):
         pass
 

@@ -61,7 +61,12 @@ def run_episodes(model, vec_env, n_runs: int, deterministic: bool = False, max_s
     are read once at the end from the episode log -- run k * N + i is log entry
     k of env i -- so no env may need more than EPISODE_LOG episodes.  It
     resets the net's episode statistics (the evaluation model is its own)
-    and leaves the feature switched as it found it."""
+    and leaves the feature switched as it found it.
+
+    A device env is stepped through its granular reset() / step() and observed
+    from the frame pairs they return: evaluation stays on the pairs path, the
+    direct-to-ring launch (DeviceNet.set_env(env, direct=True)) is not used
+    here."""
     net = model.net
     N, T = net.n_envs, net.t_max
     if vec_env.n != N:

@@ -558,22 +558,42 @@ class DeviceNet:
 
     # ------------------------------------------------------------ device environment
     env = None        # the attached DeviceCatch / DeviceBreakout / DevicePong (set_env), else None
+    env_direct = False   # set_env(env, direct=True): the env renders straight into the frame ring, no pools
 
-    def set_env(self, env=None):
+    def set_env(self, env=None, direct: bool = False):
         """Attach a device-resident env (envs.DeviceCatch, envs.DeviceBreakout or
         envs.DevicePong, by its `kind`; arl_net_set_env) built
         for this net's n_envs, seed and env_offset, or detach with None.  While
         attached, run_window steps it after every act(t), t < t_max, and the
         pools handed to the window are written.  A captured window keeps the
-        env it was captured with."""
+        env it was captured with.
+
+        direct=True (arl_net_set_env_direct): the env-step and the observation
+        that follows it are one launch that writes the 84x84 plane into the
+        frame ring and never the frame pair (env_reset_observe /
+        env_step_observe); windows then take None for their pools.  The ring,
+        the window buffers and every result are bit-identical to direct=False."""
         if env is None:
             check(lib.arl_net_set_env(self._h, ENV_CATCH, None), "arl_net_set_env")
-            self.env = None
+            self.env, self.env_direct = None, False
             return
         if (env.n, env.seed, env.env_offset) != (self.n_envs, self.seed, self.env_offset):
             raise ValueError("set_env: the env must be built with the net's n_envs, seed and env_offset")
         check(lib.arl_net_set_env(self._h, env.kind, ptr(env.state)), "arl_net_set_env")
-        self.env = env
+        check(lib.arl_net_set_env_direct(self._h, int(bool(direct))), "arl_net_set_env_direct")
+        self.env, self.env_direct = env, bool(direct)
+
+    def env_reset_observe(self, resize_mode: int = RESIZE_SCALAR, stream=None):
+        """Direct env: env_reset + observe(0, force_reset=True) in one launch,
+        without pools (arl_env_reset_observe)."""
+        check(lib.arl_env_reset_observe(self._h, resize_mode, stream_handle(stream)), "arl_env_reset_observe")
+
+    def env_step_observe(self, t: int, resize_mode: int = RESIZE_SCALAR, stream=None, envs=None):
+        """Direct env: env_step(t) + observe(t + 1) in one launch, without pools
+        (arl_env_step_observe); envs=(e0, ne): only that range."""
+        e0, ne = envs if envs is not None else (0, self.n_envs)
+        check(lib.arl_env_step_observe(self._h, t, e0, ne, resize_mode, stream_handle(stream)),
+              "arl_env_step_observe")
 
     def env_reset(self, pair_pool, reward_pool, done_pool, pool_len: int, stream=None):
         """Episode 0 of every env into pool entry (step counter) % pool_len
@@ -670,8 +690,9 @@ class DeviceNet:
         """A whole lockstep window in one call (arl_run_window): T x (observe,
         act), the bootstrap, learn, clip + RMSProp and the advance -- the
         launches of observe / act / learn / optimize(advance=True) in order."""
-        check_pools(pool_len, pair_pool, reward_pool, done_pool)
-        self.set_pools(pair_pool, reward_pool, done_pool)
+        if not self.env_direct:   # (a direct env reads no pools: None / 0 are fine)
+            check_pools(pool_len, pair_pool, reward_pool, done_pool)
+            self.set_pools(pair_pool, reward_pool, done_pool)
         self._sync_params()
         check(lib.arl_run_window(self._h, ptr(pair_pool), ptr(reward_pool), ptr(done_pool), pool_len, int(first),
                                  resize_mode, gamma, beta, v_loss_coef, int(clip_reward), lr0, int(total_steps),

@@ -622,6 +622,7 @@ int arl_net_set_env(arl_net* h, int kind, int32_t* state) {
                 "ARL_ENV_PONG | ARL_ENV_PONG_POINTS(0..21))");
   if (!state) {   // detach
     h->net.env_state = nullptr;
+    h->net.env_direct = false;
     return ARL_OK;
   }
   const arl::Net& n = h->net;
@@ -719,6 +720,125 @@ int arl_env_step(arl_net* h, int t, int e0, int ne, uint8_t* pair_pool, float* r
   arl::EnvArgs a;
   if (int rc = env_args(h, true, t, e0, ne, pair_pool, reward_pool, done_pool, pool_len, a)) return rc;
   return env_launch(h->net, a, s, "env_step");
+}
+
+// ---------------------------------------------------------------- direct-to-ring device env
+int arl_net_set_env_direct(arl_net* h, int on) {
+  if (!h) return fail(ARL_EINVAL, "null net");
+  arl::Net& n = h->net;
+  if (n.rgb || n.stack || n.states)
+    return fail(ARL_ESTATE,
+                "set_env_direct: the env renders frame pairs (FF / LSTM / FF_NATURE nets without a frames flag)");
+  if (on && !n.env_state) return fail(ARL_ESTATE, "set_env_direct: no env attached (arl_net_set_env)");
+  n.env_direct = on != 0;
+  return ARL_OK;
+}
+
+static int bad_resize_mode(int mode) {
+  return (mode < 0 || mode > (ARL_RESIZE_SIMD | ARL_RESIZE_CROP)) ? fail(ARL_EINVAL, "bad resize_mode") : 0;
+}
+
+// the ring half of a direct launch: the observation at window slot t of the bound net (no pools)
+static void direct_ring(const arl::Net& n, int t, int force_reset, int mode, arl::RingArgs& a) {
+  a = arl::RingArgs{};
+  a.dpool = arl::fd_make(1u);
+  a.dR = n.dR;
+  a.frames = n.at<uint8_t>(n.w_frames);
+  a.nvalid = n.at<uint8_t>(n.w_nvalid);
+  a.reset_flags = n.at<uint8_t>(n.w_reset);
+  a.rewards = n.at<float>(n.w_rewards);
+  a.dones = n.at<uint8_t>(n.w_dones);
+  a.ctl = n.at<int64_t>(n.w_ctl);
+  a.n = n.N;
+  a.R = n.R;
+  a.t = t;
+  a.mode = mode;
+  a.force_reset = force_reset;
+  a.episodes = n.episode_stats ? n.ws + n.w_episodes : nullptr;
+}
+
+// validates a direct launch of a bound net and fills its arguments (0 = ok); step == false: the reset form
+static int direct_args(arl_net* h, bool step, int t, int e0, int ne, int mode, arl::DirectArgs& a) {
+  arl::Net& n = h->net;
+  if (!n.env_state) return fail(ARL_ESTATE, "env: no env attached (arl_net_set_env)");
+  if (!n.env_direct) return fail(ARL_ESTATE, "env: direct mode is off (arl_net_set_env_direct)");
+  if (step && (t < 0 || t >= n.T)) return fail(ARL_EINVAL, "env_step_observe: t out of [0, t_max)");
+  if (int rc = bad_resize_mode(mode)) return rc;
+  if (n.N > 65535) return fail(ARL_EINVAL, "env: n_envs > 65535");
+  a = arl::DirectArgs{};
+  a.env.state = n.env_state;
+  a.env.actions = step ? n.at<int32_t>(n.w_act) + (int64_t)t * n.N : nullptr;
+  a.env.ctl = n.at<int64_t>(n.w_ctl);
+  a.env.t = step ? t : 0;
+  a.env.dpool = arl::fd_make(1u);
+  a.env.n = n.N;
+  a.env.e0 = e0;
+  a.env.ne = ne;
+  a.env.env_offset = n.env_offset;
+  a.env.seed_lo = (uint32_t)n.seed;
+  a.env.seed_hi = (uint32_t)(n.seed >> 32);
+  direct_ring(n, step ? t + 1 : 0, step ? 0 : 1, mode, a.ring);
+  a.ring.e0 = e0;
+  a.ring.ne = ne;
+  return 0;
+}
+
+static int direct_launch(const arl::Net& n, const arl::DirectArgs& a, void* s, const char* what) {
+  hipError_t e = arl::launch_env_direct(n.env_kind, a, S(s));
+  if (e == hipSuccess) e = arl::stamp(n, arl::STAGE_PHI, S(s));
+  return hip_status(e, what);
+}
+
+int arl_env_reset_observe(arl_net* h, int resize_mode, void* s) {
+  NEED_BOUND(h);
+  arl::DirectArgs a;
+  if (int rc = direct_args(h, false, 0, 0, -1, resize_mode, a)) return rc;
+  return direct_launch(h->net, a, s, "env_reset_observe");
+}
+
+int arl_env_step_observe(arl_net* h, int t, int e0, int ne, int resize_mode, void* s) {
+  NEED_BOUND(h);
+  if (!h->net.env_state) return fail(ARL_ESTATE, "env: no env attached (arl_net_set_env)");
+  if (!h->net.env_direct) return fail(ARL_ESTATE, "env: direct mode is off (arl_net_set_env_direct)");
+  if (int rc = check_env_range(h->net, e0, ne)) return rc;
+  arl::DirectArgs a;
+  if (int rc = direct_args(h, true, t, e0, ne, resize_mode, a)) return rc;
+  return direct_launch(h->net, a, s, "env_step_observe");
+}
+
+int arl_env_step_screen(int kind, int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset,
+                        uint64_t seed, int resize_mode, uint8_t* screen_out, float* reward_out, uint8_t* done_out,
+                        void* s) {
+  if (!arl::env_kind_ok(kind))
+    return fail(ARL_EINVAL,
+                "env_step_screen: unknown env kind (ARL_ENV_CATCH, ARL_ENV_BREAKOUT [| ARL_ENV_GAME_OVER_ONLY], or "
+                "ARL_ENV_PONG | ARL_ENV_PONG_POINTS(0..21))");
+  if (n < 0 || n > 65535) return fail(ARL_EINVAL, "env_step_screen: n out of [0, 65535]");
+  if (parity_in != 0 && parity_in != 1) return fail(ARL_EINVAL, "env_step_screen: parity must be 0 or 1");
+  if (int rc = bad_resize_mode(resize_mode)) return rc;
+  if (n == 0) return ARL_OK;
+  if (!state || !actions || !screen_out || !reward_out || !done_out)
+    return fail(ARL_EINVAL, "env_step_screen: null pointer");
+  if (!aligned(state, 16) || !aligned(screen_out, 4) || !aligned(reward_out, 4) || !aligned(actions, 4))
+    return fail(ARL_EINVAL, "env_step_screen: state 16-byte aligned, screens, rewards and actions 4-byte aligned");
+  arl::DirectArgs a{};
+  a.env.state = state;
+  a.env.actions = actions;
+  a.env.ctl = nullptr;
+  a.env.t = parity_in;
+  a.env.dpool = arl::fd_make(1u);
+  a.env.n = (int)n;
+  a.env.env_offset = env_offset;
+  a.env.seed_lo = (uint32_t)seed;
+  a.env.seed_hi = (uint32_t)(seed >> 32);
+  a.ring.dpool = a.ring.dR = arl::fd_make(1u);
+  a.ring.frames = screen_out;
+  a.ring.n = (int)n;
+  a.ring.R = 1;
+  a.ring.mode = resize_mode;
+  a.reward_out = reward_out;
+  a.done_out = done_out;
+  return hip_status(arl::launch_env_direct(kind, a, S(s)), "env_step_screen");
 }
 
 int arl_act_envs(arl_net* h, int t, int e0, int ne, int mode, void* s) {
@@ -839,13 +959,18 @@ int arl_run_window(arl_net* h, const uint8_t* pair_pool, const float* reward_poo
   if (n.rgb || n.stack || n.states || n.arch == arl::ARCH_FF_NATURE)
     return fail(ARL_ESTATE, "run_window: frame-pair nets with the NIPS head only (FF / LSTM)");
   if (resize_mode < 0 || resize_mode > (ARL_RESIZE_SIMD | ARL_RESIZE_CROP)) return fail(ARL_EINVAL, "bad resize_mode");
-  {   // every observation of the window reads the same pools: check them before the first launch
+  // a direct env (arl_net_set_env_direct) answers act(t) with observation t + 1 in one launch: no pools are read
+  const bool direct = n.env_state != nullptr && n.env_direct;
+  arl::DirectArgs da;
+  if (direct) {
+    if (int rc = direct_args(h, true, 0, 0, -1, resize_mode, da)) return rc;
+  } else {   // every observation of the window reads the same pools: check them before the first launch
     arl::RingArgs a;
     if (int rc = ring_args(h, 0, pair_pool, reward_pool, done_pool, pool_len, 0, resize_mode, 0, 0, 0, -1, a)) return rc;
   }
   // an attached env steps after every act(t), t < T, into the pools the next observation reads (so it writes
   // them: the signature keeps the observing calls' const)
-  const bool env = n.env_state != nullptr;
+  const bool env = n.env_state != nullptr && !direct;
   arl::EnvArgs ea;
   if (env)
     if (int rc = env_args(h, true, 0, 0, -1, const_cast<uint8_t*>(pair_pool), const_cast<float*>(reward_pool),
@@ -858,7 +983,18 @@ int arl_run_window(arl_net* h, const uint8_t* pair_pool, const float* reward_poo
   n.returns_done = false;
   n.ret = arl::Net::ReturnsCfg{gamma, (float)beta, (float)vcoef, clip_reward};
   for (int t = 0; t <= n.T; ++t) {
-    if (t > 0 || first) {   // slot 0 of a continuing window: the previous window's bootstrap observation
+    if (direct) {
+      if (t == 0 && first) {   // the reset form: episode 0 of every env, its first screen as observation 0
+        arl::DirectArgs ra;
+        int rc = direct_args(h, false, 0, 0, -1, resize_mode, ra);
+        if (rc == ARL_OK) rc = direct_launch(n, ra, s, "run_window: env_reset_observe");
+        if (rc != ARL_OK) {
+          n.fuse_returns = fuse_was;
+          n.ret = ret_was;
+          return rc;
+        }
+      }
+    } else if (t > 0 || first) {   // slot 0 of a continuing window: the previous window's bootstrap observation
       const int rc = observe_common(h, t, pair_pool, reward_pool, done_pool, pool_len, t == 0 ? 1 : 0, resize_mode, 0,
                                     0, s);
       if (rc != ARL_OK) {
@@ -872,6 +1008,16 @@ int arl_run_window(arl_net* h, const uint8_t* pair_pool, const float* reward_poo
       n.fuse_returns = fuse_was;
       n.ret = ret_was;
       return hip_status(e, "run_window: act");
+    }
+    if (direct && t < n.T) {   // the env-step and observation t + 1
+      da.env.t = t;
+      da.env.actions = n.at<int32_t>(n.w_act) + (int64_t)t * n.N;
+      da.ring.t = t + 1;
+      if (const int rc = direct_launch(n, da, s, "run_window: env_step_observe")) {
+        n.fuse_returns = fuse_was;
+        n.ret = ret_was;
+        return rc;
+      }
     }
     if (env && t < n.T) {
       ea.t = t;

@@ -193,8 +193,33 @@ inline hipError_t launch_env(int kind, const EnvArgs& a, hipStream_t s) {
   return env_is_breakout(kind) ? launch_game<Breakout>(f, s) : launch_game<Catch>(f, s);
 }
 
+// The direct-to-ring launch (env_direct.hpp; arl_net_set_env_direct): the env-step and its observation in one launch,
+// no pools.  env: launch_env's arguments without the pools (actions null: the reset form).  ring: the observation
+// this launch produces -- ring.t = env.t + 1 (the reset: 0, with force_reset), ring.n = env.n; its pools are not
+// read.  The granular call (arl_env_step_screen): ring.nvalid == null, ring.dR = 1, the planes go to ring.frames
+// (n, 84, 84) and the raw reward / done to reward_out / done_out.
+struct DirectArgs {
+  EnvArgs env;
+  RingArgs ring;
+  float* reward_out = nullptr;
+  uint8_t* done_out = nullptr;
+};
+template <class Game> hipError_t launch_game_direct(const DirectArgs& a, hipStream_t s);   // env_direct.hpp
+extern template hipError_t launch_game_direct<Catch>(const DirectArgs&, hipStream_t);
+extern template hipError_t launch_game_direct<Breakout>(const DirectArgs&, hipStream_t);
+extern template hipError_t launch_game_direct<Pong>(const DirectArgs&, hipStream_t);
+inline hipError_t launch_env_direct(int kind, const DirectArgs& a, hipStream_t s) {
+  DirectArgs f = a;
+  if (env_is_pong(kind)) {
+    f.env.flags = pong_points(kind);
+    return launch_game_direct<Pong>(f, s);
+  }
+  f.env.flags = kind & ARL_ENV_GAME_OVER_ONLY;
+  return env_is_breakout(kind) ? launch_game_direct<Breakout>(f, s) : launch_game_direct<Catch>(f, s);
+}
+
 // RGB (Doom) observations, train_a3c_doom.py:21-23 / doom_env.py:47
-constexpr int RGB_MAX_W = 2048;   // staged source rows: 12 x W x 3 bytes of LDS
+constexpr int RGB_MAX_W = 2048;  // staged source rows: 12 x W x 3 bytes of LDS
 hipError_t launch_rgb_phi(const uint8_t* imgs, int64_t n, int H, int W, float* out, int mode, hipStream_t s);
 hipError_t launch_rgb_ring(const RingArgs& a, hipStream_t s);
 hipError_t launch_stack_ring(const RingArgs& a, hipStream_t s);   // ARCH_STACK / ARCH_STATES nets
@@ -261,6 +286,9 @@ struct Net {
   // and the kind it was attached as (ARL_ENV_*, with ARL_ENV_GAME_OVER_ONLY or'ed in)
   int32_t* env_state = nullptr;
   int env_kind = 0;
+  // arl_net_set_env_direct: the attached env renders straight into the frame ring (arl_env_reset_observe,
+  // arl_env_step_observe, and arl_run_window without pools); cleared when the env is detached
+  bool env_direct = false;
   int64_t eval_draws = 0;  // sampling forward_states calls so far (Philox stream 1 counter)
   // clip norm folded into the learner's conv reduce (arl_net_set_norm_fold; only valid when
   // nothing changes the gradient between arl_learn and the update, e.g. no all-reduce):

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "env_direct.hpp"
 #include "env_kernel.hpp"
 #include "policy_rows.hpp"
 
@@ -147,6 +148,19 @@ struct Breakout {
                   second ? prev.blo : cur.blo, second ? prev.bhi : cur.bhi};
   }
   __device__ static u32x4 chunk(int r, int c, const Screen& s) { return breakout_chunk(r, c, s); }
+  // env_direct.hpp's shortcut: true if every pixel of row r has one colour, rgb = R | G << 8 | B << 16: a row
+  // without the ball and the paddle that is black, or a brick row with all 20 of its bricks or none
+  __device__ static bool plain_row(int r, const Screen& s, uint32_t& rgb) {
+    rgb = 0u;
+    if ((unsigned)(r - s.by) < (unsigned)BALL || (unsigned)(r - PADDLE_Y) < (unsigned)PADDLE_H) return false;
+    if ((unsigned)(r - BRICK_Y0) >= (unsigned)(BRICK_Y1 - BRICK_Y0)) return true;
+    const int br = (r - BRICK_Y0) / BRICK_H;
+    const uint32_t bits = brick_row_bits(s.blo, s.bhi, br);
+    if (bits == (1u << BRICK_COLS) - 1u)
+      rgb = (uint32_t)((ROW_R >> (8 * br)) & 0xffu) | (uint32_t)((ROW_G >> (8 * br)) & 0xffu) << 8 |
+            (uint32_t)((ROW_B >> (8 * br)) & 0xffu) << 16;
+    return bits == 0u || bits == (1u << BRICK_COLS) - 1u;
+  }
 
   // flags: ARL_ENV_GAME_OVER_ONLY (a life loss is not a terminal) or 0
   __device__ static void step(State& st, int act, uint32_t env_id, uint32_t seed_lo, uint32_t seed_hi, int flags,
@@ -215,5 +229,6 @@ struct Breakout {
 };
 
 template hipError_t launch_game<Breakout>(const EnvArgs&, hipStream_t);
+template hipError_t launch_game_direct<Breakout>(const DirectArgs&, hipStream_t);
 
 }  // namespace arl

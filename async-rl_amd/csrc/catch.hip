@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "env_direct.hpp"
 #include "env_kernel.hpp"
 #include "policy_rows.hpp"
 
@@ -75,6 +76,11 @@ struct Catch {
   __device__ static Screen screen_of(const State& st) { return Screen{st.bx, st.by, st.px}; }
   __device__ static Screen pick(bool second, const Screen& cur, const Screen& prev) { return second ? prev : cur; }
   __device__ static u32x4 chunk(int r, int c, const Screen& s) { return catch_chunk(r, c, s); }
+  // env_direct.hpp's shortcut: true if every pixel of row r has one colour, rgb = R | G << 8 | B << 16
+  __device__ static bool plain_row(int r, const Screen& s, uint32_t& rgb) {
+    rgb = 0u;
+    return (unsigned)(r - s.by) >= (unsigned)BALL && (unsigned)(r - PADDLE_Y) >= (unsigned)PADDLE_H;
+  }
 
   __device__ static void step(State& st, int act, uint32_t env_id, uint32_t seed_lo, uint32_t seed_hi, int /*flags*/,
                               Screen& cur, Screen& prev, Reward& reward, bool& done) {
@@ -109,5 +115,6 @@ struct Catch {
 };
 
 template hipError_t launch_game<Catch>(const EnvArgs&, hipStream_t);
+template hipError_t launch_game_direct<Catch>(const DirectArgs&, hipStream_t);
 
 }  // namespace arl

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "env_direct.hpp"
 #include "env_kernel.hpp"
 #include "policy_rows.hpp"
 
@@ -136,6 +137,14 @@ struct Pong {
                   second ? prev.oy : cur.oy};
   }
   __device__ static u32x4 chunk(int r, int c, const Screen& s) { return pong_chunk(r, c, s); }
+  // env_direct.hpp's shortcut: true if every pixel of row r has one colour (the background's or the walls': no
+  // ball, no paddle on it), rgb = R | G << 8 | B << 16
+  __device__ static bool plain_row(int r, const Screen& s, uint32_t& rgb) {
+    const bool wall = (unsigned)(r - WALL_TOP) < (unsigned)WALL_H || (unsigned)(r - WALL_BOTTOM) < (unsigned)WALL_H;
+    rgb = wall ? WALL : BG;
+    return (unsigned)(r - s.by) >= (unsigned)BALL && (unsigned)(r - s.oy) >= (unsigned)PADDLE_H &&
+           (unsigned)(r - s.py) >= (unsigned)PADDLE_H;
+  }
 
   // flags: the points a game is played to, 1..21 (launch_env takes them from the kind)
   __device__ static void step(State& st, int act, uint32_t env_id, uint32_t seed_lo, uint32_t seed_hi, int flags,
@@ -195,5 +204,6 @@ struct Pong {
 };
 
 template hipError_t launch_game<Pong>(const EnvArgs&, hipStream_t);
+template hipError_t launch_game_direct<Pong>(const DirectArgs&, hipStream_t);
 
 }  // namespace arl

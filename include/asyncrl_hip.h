@@ -962,6 +962,59 @@ int arl_env_reset(arl_net* net, uint8_t* pair_pool, float* reward_pool, uint8_t*
 int arl_env_step(arl_net* net, int t, int e0, int ne, uint8_t* pair_pool, float* reward_pool, uint8_t* done_pool,
                  int64_t pool_len, void* stream);
 
+/* Direct-to-ring device env: the env-step and the observation that follows it
+ * as ONE launch that never materialises the frame pair.  Every screen of the
+ * three games is a function of the env's handful of integers, so the launch
+ * evaluates arl_observe's arithmetic (max of the two screens, float64
+ * luminance, the fixed-point resize of resize_mode) on bytes it produces in
+ * registers and stores the 84 x 84 plane into the frame ring, with the
+ * observation's bookkeeping (nvalid, reset flag, reward, done, episode
+ * statistics) from the reward and done it just computed.  The ring, the
+ * window buffers, the env state and everything downstream are bit for bit
+ * what arl_env_step + arl_observe_envs leave; the pools do not exist.
+ * Additions to ABI 4; opt-in, off by default: with it off every call makes
+ * exactly the launches it made before, with the same arguments.
+ *
+ * arl_net_set_env_direct(net, on): host state of the handle.  on != 0 needs an
+ * attached env (else ARL_ESTATE); a net with the RGB / STACK / STATES flag is
+ * refused with ARL_ESTATE as arl_net_set_env refuses it.  Detaching the env
+ * (arl_net_set_env(net, kind, NULL)) turns it off.
+ *
+ * arl_env_reset_observe(net, resize_mode, stream): arl_env_reset +
+ * arl_observe(0, force_reset = 1) -- episode 0 of every env into state half
+ * ctl[CTL_STEP] & 1, its first screen (as both frames) into ring slot
+ * ctl[CTL_STEP] % R, nvalid 1, reset_flags[0] = 1, the running episode of the
+ * episode statistics abandoned.
+ * arl_env_step_observe(net, t, e0, ne, resize_mode, stream): arl_env_step(t) +
+ * arl_observe_envs(t + 1) of envs [e0, e0 + ne) (arl_env_step's range rules):
+ * from row t of the "actions" buffer and state half k & 1, k = ctl[CTL_STEP] +
+ * t read on the device, into half (k + 1) & 1, ring slot (k + 1) % R,
+ * rewards[t], dones[t], reset_flags[t + 1].  The reward stored is the raw one
+ * (the learner clips).
+ * Both: ARL_ESTATE on an unbound net, without an attached env or with direct
+ * mode off; ARL_EINVAL for t outside [0, t_max), a bad range or a resize_mode
+ * outside the four of arl_observe, before any launch.  Each launch is stamped
+ * ARL_STAGE_PHI.
+ *
+ * arl_run_window with direct mode on ignores the three pools and pool_len
+ * (NULL, 0 are fine) and issues act(t), step_observe(t) for t < t_max, then the
+ * bootstrap act(t_max); with first != 0 the reset form goes first (no
+ * arl_env_reset before it).  With direct mode off it is unchanged.
+ *
+ * arl_env_step_screen: the granular form, no net -- arl_<game>_step followed by
+ * arl_current_screen on the pair it would have written: one env-step from
+ * actions (n,) and half parity_in into half 1 - parity_in, screen_out (n, 84,
+ * 84) uint8, the raw rewards (n,) and dones (n,).  kind as arl_net_set_env
+ * takes it (Breakout's flag, Pong's points).  n <= 65535; ARL_EINVAL for an
+ * unknown kind, a parity other than 0 / 1, a bad resize_mode, a null or
+ * misaligned pointer (state 16 bytes; screens, rewards, actions 4). */
+int arl_net_set_env_direct(arl_net* net, int on);
+int arl_env_reset_observe(arl_net* net, int resize_mode, void* stream);
+int arl_env_step_observe(arl_net* net, int t, int e0, int ne, int resize_mode, void* stream);
+int arl_env_step_screen(int kind, int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset,
+                        uint64_t seed, int resize_mode, uint8_t* screen_out, float* reward_out, uint8_t* done_out,
+                        void* stream);
+
 /* ------------------------------------------------------------------ granular ops */
 
 /* RMSpropAsync.update_one (rmsprop_async.py:23-38) on flat f32 arrays, with

@@ -17,12 +17,15 @@ gamma 0.99) on the FF model with 256 envs; the batched learner sums the gradient
 mean, --opt adam, --gae-lambda and --ppo-epochs (clipped-surrogate epochs on each window's rollout, with
 --ppo-clip; each report row then carries A3C.ppo_stats of the last epoch; --ppo-norm-adv and --ppo-vclip X switch
 the epochs' advantage normalisation and clipped value loss on, and each row then also carries the last epoch's
-device-side record, A3C.ppo_epoch_stats) are there to try.  One JSON line at the end (and --out FILE).
+device-side record, A3C.ppo_epoch_stats) are there to try.  --direct runs the env direct-to-ring
+(DeviceNet.set_env(env, direct=True)): no frame pools are allocated, the curve is bit-identical.  One JSON line at
+the end (and --out FILE).
 
     python scripts/train_catch.py [--env catch|breakout|pong] [--points 21] [--windows 4000] [--report 200]
                                   [--envs 256] [--seed 0]
                                   [--lr 7e-4] [--opt rmsprop|adam] [--batch-loss sum|mean] [--gae-lambda 1.0]
                                   [--arch ff|lstm] [--ppo-epochs 1] [--ppo-clip 0.2] [--ppo-norm-adv] [--ppo-vclip X]
+                                  [--direct]
 """
 import argparse
 import json
@@ -40,7 +43,7 @@ import asyncrl_amd as pkg  # noqa: E402
 
 def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", batch_loss="sum", gae_lambda=1.0,
           arch="ff", beta=1e-2, eps=None, device="cuda:0", log=print, env="catch", ppo_epochs=1, ppo_clip=0.2, ppo_norm_adv=False,
-          ppo_vclip=None, points=21):
+          ppo_vclip=None, points=21, direct=False):
     """Returns the curve: one dict per report with the window count, the episodes completed since the last
     report and their mean return, and the newest window record's entropy / value / gradient norm."""
     dev = torch.device(device)
@@ -62,12 +65,13 @@ def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", ba
         game = pkg.DevicePong(envs, device=dev, seed=seed, points=points)
     else:
         game = (pkg.DeviceBreakout if env == "breakout" else pkg.DeviceCatch)(envs, device=dev, seed=seed)
-    pools = game.make_pools(P)
-    net.set_env(game)
+    pools = (None, None, None) if direct else game.make_pools(P)   # direct: the frame pairs never exist
+    net.set_env(game, direct=direct)
     stream = torch.cuda.Stream(device=dev)
     stream.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(stream):
-        net.env_reset(*pools, P, stream=stream)
+        if not direct:   # (a direct window with first=True issues the reset itself)
+            net.env_reset(*pools, P, stream=stream)
         agent.run_window(*pools, P, first=True, stream=stream)
         stream.synchronize()
         graph = torch.cuda.CUDAGraph()
@@ -121,6 +125,7 @@ def main():
     ap.add_argument("--ppo-clip", type=float, default=0.2)
     ap.add_argument("--ppo-norm-adv", action="store_true")
     ap.add_argument("--ppo-vclip", type=float, default=None)
+    ap.add_argument("--direct", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     cfg = {k: v for k, v in vars(a).items() if k != "out"}
