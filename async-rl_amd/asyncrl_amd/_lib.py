@@ -138,6 +138,10 @@ SIGNATURES = {
     "arl_pong_reset": (c_int, [c_void_p, c_i64, c_int, c_u64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "arl_pong_step": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_int, c_u64, c_int, c_void_p, c_void_p, c_void_p,
                               c_void_p]),
+    "arl_tmaze_state_bytes": (c_i64, [c_i64]),
+    "arl_tmaze_reset": (c_int, [c_void_p, c_i64, c_int, c_u64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "arl_tmaze_step": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_int, c_u64, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
     "arl_net_set_env": (c_int, [c_void_p, c_int, c_void_p]),
     "arl_env_reset": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "arl_env_step": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
@@ -179,11 +183,19 @@ ENV_PONG = 4                 # ARL_ENV_PONG: the device-resident Pong; its kind 
 PONG_STATE_INTS = 12         # [bx, by, vx, vy, py, oy, serves, steps_in_episode, game, game_steps, score_agent,
                              #  score_opp]
 PONG_POINTS_MAX = 21
+ENV_TMAZE = 8                # ARL_ENV_TMAZE: the device-resident T-maze; its kind carries the corridor's length
+TMAZE_STATE_INTS = 8         # [pos, cue, length, steps_in_episode, episode, hits, misses, lapses]
+TMAZE_LENGTH_MAX = 8
 
 
 def env_pong_points(points: int) -> int:
     """ARL_ENV_PONG_POINTS(points): or'ed into ENV_PONG; 1..21, and 0 means 21."""
     return points << 16
+
+
+def env_tmaze_length(length: int) -> int:
+    """ARL_ENV_TMAZE_LENGTH(length): or'ed into ENV_TMAZE; 1..8, and 0 means 4."""
+    return length << 16
 
 
 CTL_ADAM_T = 3         # ARL_CTL_ADAM_T: the control block's count of Adam updates made (buffer "ctl", int64[16])

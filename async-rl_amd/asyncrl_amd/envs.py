@@ -22,7 +22,10 @@ phi pre-stage is the GPU kernel, so the adapter stops at the raw frame pair:
                  rewards of 1, 4 and 7, episodes of different lengths;
   DevicePong     and for Pong (csrc/pong.hip): an opponent, rewards of both
                  signs inside a game, games of hundreds of steps, a
-                 background that is not black.
+                 background that is not black;
+  DeviceTMaze    and for a cue-recall T-maze (csrc/tmaze.hip): the cue is on
+                 an episode's first screen alone and is asked for `length`
+                 steps later -- the one env here the FF model cannot solve.
 
 Batched convention: a step whose action ends the episode returns
 done = 1, the reward of that step, and the FIRST pair of the next episode
@@ -37,7 +40,8 @@ import numpy as np
 import torch
 
 from ._lib import (BREAKOUT_STATE_INTS, CATCH_STATE_INTS, ENV_BREAKOUT, ENV_CATCH, ENV_GAME_OVER_ONLY, ENV_PONG,
-                   PONG_POINTS_MAX, PONG_STATE_INTS, check, env_pong_points, lib, ptr, stream_handle)
+                   ENV_TMAZE, PONG_POINTS_MAX, PONG_STATE_INTS, TMAZE_LENGTH_MAX, TMAZE_STATE_INTS, check,
+                   env_pong_points, env_tmaze_length, lib, ptr, stream_handle)
 
 SCREEN = (210, 160, 3)
 
@@ -366,6 +370,37 @@ class DevicePong(_DeviceEnv):
 
     def _step(self, state, parity, actions, n, env_offset, seed, *out):   # the points go before the outputs
         check(lib.arl_pong_step(state, parity, actions, n, env_offset, seed, self.points, *out), "arl_pong_step")
+
+
+class DeviceTMaze(_DeviceEnv):
+    """A cue-recall T-maze on the device (include/asyncrl_hip.h, "device
+    environment"; the rules are there): DeviceCatch's surface over a partially
+    observed task.  An episode's first screen shows a cue ("up" or "down");
+    the agent is then carried down a corridor of `length` (1..8) env-steps,
+    its actions ignored, and at the junction has to name the cue: 2 = up, 3 =
+    down, anything else no choice (n_actions >= 4).  Reward +1 for the cue's
+    arm, -1 for the other, 0 for no choice; each ends the episode, so every
+    episode lasts length + 1 env-steps and the optimum is +1.  From length 4
+    on the cue has left the 4-observation stack at the junction: the FF
+    model's expected return is exactly 0 whatever it learns, and the LSTM has
+    to carry the cue in its state.  The default length 4 makes an episode one
+    t_max = 5 window.  The state is (2, n, 8) int32."""
+
+    STATE_INTS = TMAZE_STATE_INTS
+    _state_bytes = staticmethod(lib.arl_tmaze_state_bytes)
+
+    def __init__(self, n_envs: int, device=None, seed: int = 0, env_offset: int = 0, length: int = 4):
+        if not 1 <= length <= TMAZE_LENGTH_MAX:
+            raise ValueError(f"DeviceTMaze: length must be in 1..{TMAZE_LENGTH_MAX}")
+        super().__init__(n_envs, device, seed, env_offset)
+        self.length = int(length)
+        self.kind = ENV_TMAZE | env_tmaze_length(self.length)
+
+    def _reset(self, state, n, env_offset, seed, *rest):   # the length goes before the parity
+        check(lib.arl_tmaze_reset(state, n, env_offset, seed, self.length, *rest), "arl_tmaze_reset")
+
+    def _step(self, state, parity, actions, n, env_offset, seed, *out):   # the length goes before the outputs
+        check(lib.arl_tmaze_step(state, parity, actions, n, env_offset, seed, self.length, *out), "arl_tmaze_step")
 
 
 class _null:

@@ -31,8 +31,9 @@ LSTM state and n-step bootstrap across an unrelated game without a terminal
 A device-resident env goes through the same loop unchanged (it has no host
 emulators to switch, `envs = ()`), so its life-loss switch is the caller's:
 build `DeviceBreakout(n, life_loss_terminal=False)` for evaluation -- with the
-default a "run" would be a single life.  `DeviceCatch` and `DevicePong` have
-no lives: a Pong run is one game to the env's `points`.
+default a "run" would be a single life.  `DeviceCatch`, `DevicePong` and
+`DeviceTMaze` have no lives: a Pong run is one game to the env's `points`, a
+T-maze run one episode (`length` + 1 env-steps, a score of +1, -1 or 0).
 Host-side driver code; the per-step work is the device forward.
 """
 from __future__ import annotations

@@ -614,12 +614,30 @@ int arl_pong_step(int32_t* state, int parity_in, const int32_t* actions, int64_t
                       env_offset, seed, pair_out, reward_out, done_out, s);
 }
 
+int64_t arl_tmaze_state_bytes(int64_t n_envs) { return env_state_bytes(ARL_ENV_TMAZE, n_envs); }
+
+static bool tmaze_length_ok(int length) { return length >= 1 && length <= arl::TMAZE_LENGTH_MAX; }
+
+int arl_tmaze_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, int length, int parity, uint8_t* pair_out,
+                    float* reward_out, uint8_t* done_out, void* s) {
+  if (!tmaze_length_ok(length)) return fail(ARL_EINVAL, "tmaze_reset: length out of [1, 8]");
+  return env_granular("tmaze_reset", ARL_ENV_TMAZE | ARL_ENV_TMAZE_LENGTH(length), state, parity, nullptr, false, n,
+                      env_offset, seed, pair_out, reward_out, done_out, s);
+}
+
+int arl_tmaze_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
+                   int length, uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* s) {
+  if (!tmaze_length_ok(length)) return fail(ARL_EINVAL, "tmaze_step: length out of [1, 8]");
+  return env_granular("tmaze_step", ARL_ENV_TMAZE | ARL_ENV_TMAZE_LENGTH(length), state, parity_in, actions, true, n,
+                      env_offset, seed, pair_out, reward_out, done_out, s);
+}
+
 int arl_net_set_env(arl_net* h, int kind, int32_t* state) {
   if (!h) return fail(ARL_EINVAL, "null net");
   if (!arl::env_kind_ok(kind))
     return fail(ARL_EINVAL,
-                "set_env: unknown env kind (ARL_ENV_CATCH, ARL_ENV_BREAKOUT [| ARL_ENV_GAME_OVER_ONLY], or "
-                "ARL_ENV_PONG | ARL_ENV_PONG_POINTS(0..21))");
+                "set_env: unknown env kind (ARL_ENV_CATCH, ARL_ENV_BREAKOUT [| ARL_ENV_GAME_OVER_ONLY], "
+                "ARL_ENV_PONG | ARL_ENV_PONG_POINTS(0..21), or ARL_ENV_TMAZE | ARL_ENV_TMAZE_LENGTH(0..8))");
   if (!state) {   // detach
     h->net.env_state = nullptr;
     h->net.env_direct = false;
@@ -630,7 +648,8 @@ int arl_net_set_env(arl_net* h, int kind, int32_t* state) {
     return fail(ARL_ESTATE, "set_env: the env renders frame pairs (FF / LSTM / FF_NATURE nets without a frames flag)");
   if (n.A < 4)
     return fail(ARL_EINVAL,
-                "set_env: the env needs n_actions >= 4 (NOOP / FIRE / RIGHT / LEFT; Pong: NOOP / FIRE / UP / DOWN)");
+                "set_env: the env needs n_actions >= 4 (NOOP / FIRE / RIGHT / LEFT; Pong and the T-maze: NOOP / FIRE / "
+                "UP / DOWN)");
   if (!aligned(state, 16)) return fail(ARL_EINVAL, "set_env: state must be 16-byte aligned");
   h->net.env_state = state;
   h->net.env_kind = kind;
@@ -811,8 +830,8 @@ int arl_env_step_screen(int kind, int32_t* state, int parity_in, const int32_t* 
                         void* s) {
   if (!arl::env_kind_ok(kind))
     return fail(ARL_EINVAL,
-                "env_step_screen: unknown env kind (ARL_ENV_CATCH, ARL_ENV_BREAKOUT [| ARL_ENV_GAME_OVER_ONLY], or "
-                "ARL_ENV_PONG | ARL_ENV_PONG_POINTS(0..21))");
+                "env_step_screen: unknown env kind (ARL_ENV_CATCH, ARL_ENV_BREAKOUT [| ARL_ENV_GAME_OVER_ONLY], "
+                "ARL_ENV_PONG | ARL_ENV_PONG_POINTS(0..21), or ARL_ENV_TMAZE | ARL_ENV_TMAZE_LENGTH(0..8))");
   if (n < 0 || n > 65535) return fail(ARL_EINVAL, "env_step_screen: n out of [0, 65535]");
   if (parity_in != 0 && parity_in != 1) return fail(ARL_EINVAL, "env_step_screen: parity must be 0 or 1");
   if (int rc = bad_resize_mode(resize_mode)) return rc;

@@ -138,7 +138,7 @@ hipError_t launch_episode_reset(char* block, int n, hipStream_t s);
 // envs in a fixed order (phi.hip episode_reduce_kernel); clear: also zero the cumulative per-env arrays
 hipError_t launch_episode_reduce(char* block, int n, double* out8, int clear, hipStream_t s);
 
-// Device-resident envs (env_kernel.hpp, with the games in catch.hip, breakout.hip and pong.hip; the header's "device
+// Device-resident envs (env_kernel.hpp, with the games in catch.hip, breakout.hip, pong.hip and tmaze.hip; the header's "device
 // environment"): one launch = one env-step (or the reset) of envs [e0, e0 + ne): transition + render into pool
 // entry (k + 1) % pool_len (reset: k % pool_len), k = ctl[CTL_STEP] + t read on the device; the state half read
 // is k & 1, the half written (k + 1) & 1.
@@ -147,6 +147,7 @@ constexpr int BREAKOUT_STATE_INTS = 16;   // [bx, by, vx, vy, px, lives, serves,
                                           //  score, bricks_left, b0, b1, b2, b3]
 constexpr int PONG_STATE_INTS = 12;       // [bx, by, vx, vy, py, oy, serves, steps_in_episode, game, game_steps,
                                           //  score_agent, score_opp]
+constexpr int TMAZE_STATE_INTS = 8;       // [pos, cue, length, steps_in_episode, episode, hits, misses, lapses]
 struct EnvArgs {
   int32_t* state;            // (2, n, the game's STATE_INTS), 16-byte aligned
   const int32_t* actions;    // (n): the actions of observation k; null: reset (episode 0 into half k & 1)
@@ -161,30 +162,47 @@ struct EnvArgs {
   int env_offset = 0;
   uint32_t seed_lo = 0, seed_hi = 0;
   int flags = 0;             // filled by launch_env from the kind: Breakout's ARL_ENV_GAME_OVER_ONLY or 0, Pong's
-                             // points (1..21); Catch ignores it
+                             // points (1..21), the T-maze's length (1..8); Catch ignores it
 };
-struct Catch;      // the games: catch.hip, breakout.hip and pong.hip each instantiate their launch_game
+struct Catch;      // the games: catch.hip, breakout.hip, pong.hip and tmaze.hip each instantiate their launch_game
 struct Breakout;
 struct Pong;
+struct TMaze;
 template <class Game> hipError_t launch_game(const EnvArgs& a, hipStream_t s);   // env_kernel.hpp
 extern template hipError_t launch_game<Catch>(const EnvArgs&, hipStream_t);
 extern template hipError_t launch_game<Breakout>(const EnvArgs&, hipStream_t);
 extern template hipError_t launch_game<Pong>(const EnvArgs&, hipStream_t);
+extern template hipError_t launch_game<TMaze>(const EnvArgs&, hipStream_t);
 
 // The library's only look at an env kind (ARL_ENV_*, a Breakout's with an optional ARL_ENV_GAME_OVER_ONLY, a
-// Pong's with its points in bits 16 and up: 1..21, 0 = 21; no other bit).
+// Pong's with its points in bits 16 and up: 1..21, 0 = 21, a T-maze's with its length there: 1..8, 0 = 4; no other
+// bit).
 constexpr int PONG_POINTS_MAX = 21;
+constexpr int TMAZE_LENGTH_MAX = 8, TMAZE_LENGTH_DEFAULT = 4;
 constexpr bool env_is_breakout(int kind) { return (kind & ~ARL_ENV_GAME_OVER_ONLY) == ARL_ENV_BREAKOUT; }
 constexpr bool env_is_pong(int kind) {
   return kind >= 0 && (kind & 0xffff) == ARL_ENV_PONG && (kind >> 16) <= PONG_POINTS_MAX;
 }
 constexpr int pong_points(int kind) { return (kind >> 16) ? (kind >> 16) : PONG_POINTS_MAX; }
-constexpr bool env_kind_ok(int kind) { return kind == ARL_ENV_CATCH || env_is_breakout(kind) || env_is_pong(kind); }
+constexpr bool env_is_tmaze(int kind) {
+  return kind >= 0 && (kind & 0xffff) == ARL_ENV_TMAZE && (kind >> 16) <= TMAZE_LENGTH_MAX;
+}
+constexpr int tmaze_length(int kind) { return (kind >> 16) ? (kind >> 16) : TMAZE_LENGTH_DEFAULT; }
+constexpr bool env_kind_ok(int kind) {
+  return kind == ARL_ENV_CATCH || env_is_breakout(kind) || env_is_pong(kind) || env_is_tmaze(kind);
+}
 constexpr int env_state_ints(int kind) {
-  return env_is_pong(kind) ? PONG_STATE_INTS : env_is_breakout(kind) ? BREAKOUT_STATE_INTS : CATCH_STATE_INTS;
+  return env_is_tmaze(kind)      ? TMAZE_STATE_INTS
+         : env_is_pong(kind)     ? PONG_STATE_INTS
+         : env_is_breakout(kind) ? BREAKOUT_STATE_INTS
+                                 : CATCH_STATE_INTS;
 }
 inline hipError_t launch_env(int kind, const EnvArgs& a, hipStream_t s) {
   EnvArgs f = a;
+  if (env_is_tmaze(kind)) {
+    f.flags = tmaze_length(kind);
+    return launch_game<TMaze>(f, s);
+  }
   if (env_is_pong(kind)) {
     f.flags = pong_points(kind);
     return launch_game<Pong>(f, s);
@@ -208,8 +226,13 @@ template <class Game> hipError_t launch_game_direct(const DirectArgs& a, hipStre
 extern template hipError_t launch_game_direct<Catch>(const DirectArgs&, hipStream_t);
 extern template hipError_t launch_game_direct<Breakout>(const DirectArgs&, hipStream_t);
 extern template hipError_t launch_game_direct<Pong>(const DirectArgs&, hipStream_t);
+extern template hipError_t launch_game_direct<TMaze>(const DirectArgs&, hipStream_t);
 inline hipError_t launch_env_direct(int kind, const DirectArgs& a, hipStream_t s) {
   DirectArgs f = a;
+  if (env_is_tmaze(kind)) {
+    f.env.flags = tmaze_length(kind);
+    return launch_game_direct<TMaze>(f, s);
+  }
   if (env_is_pong(kind)) {
     f.env.flags = pong_points(kind);
     return launch_game_direct<Pong>(f, s);

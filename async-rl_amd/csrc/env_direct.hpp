@@ -14,7 +14,7 @@
 // and the observation's bookkeeping (ring_obs_store: nvalid, reset flag, reward, done, episode statistics) from
 // the reward and done it just computed.  nvalid is read at slot(k) and written at slot(k + 1).
 //
-// A game file (catch.hip, breakout.hip, pong.hip) instantiates launch_game_direct<Game> beside launch_game<Game>
+// A game file (catch.hip, breakout.hip, pong.hip, tmaze.hip) instantiates launch_game_direct<Game> beside launch_game<Game>
 // and gives one hook more than env_kernel.hpp lists:
 //   plain_row(r, const Screen&, uint32_t& rgb) -> bool     every pixel of screen row r is the colour rgb (R low byte)
 #pragma once
@@ -146,7 +146,7 @@ env_direct_kernel(DirectArgs a) {
   typename Game::Reward reward = 0;
   bool done = false;
   if (reset) {
-    st = Game::start(env_id, ea.seed_lo, ea.seed_hi);
+    st = game_start<Game>(env_id, ea.seed_lo, ea.seed_hi, ea.flags, 0);
     cur = prev = Game::screen_of(st);
   } else {
     st = Game::load(reinterpret_cast<const int4*>(ea.state + ((int64_t)(k & 1) * ea.n + e) * Game::STATE_INTS));

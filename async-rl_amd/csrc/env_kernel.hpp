@@ -13,10 +13,12 @@
 // besides the state, the action and the step counter.  Grid (ENV_BANDS, envs): a band is 2,520 consecutive
 // chunks of the pair, 10 stores per lane (DESIGN.md "Device environment" has the measurements).
 //
-// A game (catch.hip, breakout.hip) is a struct of static hooks:
+// A game (catch.hip, breakout.hip, pong.hip, tmaze.hip) is a struct of static hooks:
 //   STATE_INTS                 ints of one env's state row, a multiple of 4 (the row is read and written as int4s)
 //   State, Screen, Reward      the row unpacked; what the render needs of it; int or float
-//   start(env_id, seed_lo, seed_hi) -> State                   the reset
+//   start(env_id, seed_lo, seed_hi) -> State                   the reset; a game whose reset depends on its flags
+//                              (tmaze.hip: the corridor's length) gives start(env_id, seed_lo, seed_hi, flags)
+//                              instead, and game_start below calls whichever there is
 //   load(const int4*) -> State, store(int4*, const State&)     the state row
 //   step(State&, act, env_id, seed_lo, seed_hi, flags, Screen& cur, Screen& prev, Reward&, bool& done)
 //                              up to 4 frames, then the restart / serve; cur, prev: the pair's two screens
@@ -42,6 +44,17 @@ static_assert(PAIR == PAIR_CHUNKS * 16, "frame pair bytes");
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
+// Game::start with the flags if the game takes them (the int overload wins where it is well-formed), else without
+template <class Game>
+__device__ inline auto game_start(uint32_t env_id, uint32_t seed_lo, uint32_t seed_hi, int flags, int)
+    -> decltype(Game::start(env_id, seed_lo, seed_hi, flags)) {
+  return Game::start(env_id, seed_lo, seed_hi, flags);
+}
+template <class Game>
+__device__ inline typename Game::State game_start(uint32_t env_id, uint32_t seed_lo, uint32_t seed_hi, int, long) {
+  return Game::start(env_id, seed_lo, seed_hi);
+}
+
 template <class Game>
 __global__ void __launch_bounds__(256)
 env_kernel(EnvArgs a) {
@@ -57,7 +70,7 @@ env_kernel(EnvArgs a) {
   typename Game::Reward reward = 0;
   bool done = false;
   if (reset) {
-    st = Game::start(env_id, a.seed_lo, a.seed_hi);
+    st = game_start<Game>(env_id, a.seed_lo, a.seed_hi, a.flags, 0);
     cur = prev = Game::screen_of(st);
   } else {
     st = Game::load(reinterpret_cast<const int4*>(a.state + ((int64_t)(k & 1) * a.n + e) * Game::STATE_INTS));

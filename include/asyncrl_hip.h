@@ -930,10 +930,71 @@ int arl_pong_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, int
 int arl_pong_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
                   int points, uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* stream);
 
+/* A device-resident T-maze, the fourth device environment: a cue-recall task,
+ * with what the other three lack -- partial observability.  Catch, Breakout
+ * and Pong can be read off the 4-observation stack, so the FF model does on
+ * them whatever the LSTM does; here a cue is shown on an episode's first
+ * screen only and has to be named L env-steps later, after it has left the
+ * stack: the recurrent state has to carry it.  Same launch shape, pools and
+ * state protocol as Catch; additions to ABI 4.
+ *
+ * The game (exact in integer arithmetic; tests/tmaze_ref.py restates it).
+ * Screen 210 rows x 160 columns, RGB uint8, HWC, background (0,0,0).  L = the
+ * corridor's length, 1..8.
+ * Floor (84,84,84): rows 96..111, columns 0..16L+15.
+ * Arms (84,84,84): rows 48..159, columns 16L..16L+15.
+ * Agent (92,186,92): 8 x 8, rows 100..107, left edge ax.
+ * Cue, 16 x 16, columns 0..15, drawn only on an episode's first screen:
+ *   cue 0 ("up"): rows 72..87, colour (200,72,72);
+ *   cue 1 ("down"): rows 120..135, colour (66,72,200).
+ * Draw order: the agent over the floor over the background; the cue overlaps
+ *   nothing.
+ * Episode start: pos = 0, ax = 4, steps_in_episode = 0, and with (w0, ., ., .)
+ *   = philox4x32_10(counter = (env_offset + e, episode, 0, 5), key = (seed &
+ *   0xffffffff, seed >> 32)): cue = w0 & 1.  Counter word 3 = 5 is a stream
+ *   beside 0 (window draws), 1 (pi_and_v draws), 2 (Catch), 3 (Breakout) and 4
+ *   (Pong).  episode starts at 0 and advances at every terminal.
+ * Actions: 2 = up, 3 = down, anything else is no choice (any n_actions >= 4).
+ * One env-step with pos < L: four frames, each ax += 4; after the step
+ *   pos += 1, so ax = 4 + 16 pos.  Reward 0, done 0.  pair[0] is the screen
+ *   after frame 4 and pair[1] the screen after frame 3; neither shows the cue.
+ *   The action is ignored.
+ * One env-step with pos == L (the junction): reward +1 if the choice equals
+ *   the cue, -1 if it is the other arm, 0.0 if no choice was made; done = 1 in
+ *   all three cases.  The hits, misses and lapses counters advance,
+ *   episode += 1, and the next episode starts at once: both frames of the pair
+ *   are its first screen, with its cue (Catch's rule: the terminal screen is
+ *   never shown).
+ * So every episode lasts L + 1 env-steps and the optimum is +1.  A uniform
+ * policy over A actions scores mean 0 with P(+1) = P(-1) = 1 / A, and any
+ * policy whose action at the junction does not depend on the cue has expected
+ * return exactly 0.  The cue leaves the 4-observation stack at observation 4,
+ * so for L >= 4 the FF model's input at the junction is the same for both
+ * cues.  With the default L = 4 an episode is exactly one t_max = 5 window.
+ *
+ * Env state: caller-owned device memory, (2, n_envs, 8) int32, 16-byte
+ * aligned, [pos, cue, length, steps_in_episode, episode, hits, misses, lapses]
+ * per env, double-buffered by the parity of the observation index exactly as
+ * Catch's.  The reset stores L in the row; a step keeps the L of its call
+ * there.
+ *
+ * The kind is ARL_ENV_TMAZE | ARL_ENV_TMAZE_LENGTH(l), l in 1..8; l = 0 means
+ * 4.  Any other bit (0x100 included): ARL_EINVAL.
+ * Granular calls: Catch's trio; arl_tmaze_reset and arl_tmaze_step take the
+ * length (1..8, anything else: ARL_EINVAL), the same in both. */
+#define ARL_ENV_TMAZE 8
+#define ARL_ENV_TMAZE_LENGTH(l) ((l) << 16)
+int64_t arl_tmaze_state_bytes(int64_t n_envs);
+int arl_tmaze_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, int length, int parity,
+                    uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* stream);
+int arl_tmaze_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
+                   int length, uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* stream);
+
 /* Attached to a net (host state of the handle, like arl_net_set_adam; works on
  * an unbound handle): arl_net_set_env(net, kind, state) with kind =
- * ARL_ENV_CATCH, ARL_ENV_BREAKOUT, ARL_ENV_BREAKOUT | ARL_ENV_GAME_OVER_ONLY or
- * ARL_ENV_PONG | ARL_ENV_PONG_POINTS(p)
+ * ARL_ENV_CATCH, ARL_ENV_BREAKOUT, ARL_ENV_BREAKOUT | ARL_ENV_GAME_OVER_ONLY,
+ * ARL_ENV_PONG | ARL_ENV_PONG_POINTS(p) or ARL_ENV_TMAZE |
+ * ARL_ENV_TMAZE_LENGTH(l)
  * (any other value, the flag on Catch included: ARL_EINVAL) and state as above
  * for that env, the net's n_envs, its env_offset and seed; state == NULL
  * detaches.  arl_env_reset, arl_env_step and arl_run_window launch the
@@ -964,7 +1025,7 @@ int arl_env_step(arl_net* net, int t, int e0, int ne, uint8_t* pair_pool, float*
 
 /* Direct-to-ring device env: the env-step and the observation that follows it
  * as ONE launch that never materialises the frame pair.  Every screen of the
- * three games is a function of the env's handful of integers, so the launch
+ * four games is a function of the env's handful of integers, so the launch
  * evaluates arl_observe's arithmetic (max of the two screens, float64
  * luminance, the fixed-point resize of resize_mode) on bytes it produces in
  * registers and stores the 84 x 84 plane into the frame ring, with the
@@ -1005,9 +1066,10 @@ int arl_env_step(arl_net* net, int t, int e0, int ne, uint8_t* pair_pool, float*
  * arl_current_screen on the pair it would have written: one env-step from
  * actions (n,) and half parity_in into half 1 - parity_in, screen_out (n, 84,
  * 84) uint8, the raw rewards (n,) and dones (n,).  kind as arl_net_set_env
- * takes it (Breakout's flag, Pong's points).  n <= 65535; ARL_EINVAL for an
- * unknown kind, a parity other than 0 / 1, a bad resize_mode, a null or
- * misaligned pointer (state 16 bytes; screens, rewards, actions 4). */
+ * takes it (Breakout's flag, Pong's points, the T-maze's length).  n <=
+ * 65535; ARL_EINVAL for an unknown kind, a parity other than 0 / 1, a bad
+ * resize_mode, a null or misaligned pointer (state 16 bytes; screens,
+ * rewards, actions 4). */
 int arl_net_set_env_direct(arl_net* net, int on);
 int arl_env_reset_observe(arl_net* net, int resize_mode, void* stream);
 int arl_env_step_observe(arl_net* net, int t, int e0, int ne, int resize_mode, void* stream);

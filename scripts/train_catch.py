@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Closed-loop training on a device-resident env (asyncrl_amd.DeviceCatch, DeviceBreakout with --env breakout, or
-DevicePong with --env pong --points P): the learner has to learn.
+"""Closed-loop training on a device-resident env (asyncrl_amd.DeviceCatch, DeviceBreakout with --env breakout,
+DevicePong with --env pong --points P, or DeviceTMaze with --env tmaze --length L): the learner has to learn.
 
 env -> phi -> forward -> sample -> env -> ... -> update runs on the device with no host work per step: window 0
 eagerly (first=True), then one captured window replayed.  Every --report windows the learning curve is read
@@ -10,7 +10,10 @@ uniform random policy scores about -0.70.  With --env breakout an episode is a l
 the reference trains), the return is the raw, unclipped sum of its brick values, and a uniform random policy
 scores about 0.14 per life.  With --env pong an episode is a game to --points points against the opponent's paddle,
 the return is the agent's points minus the opponent's, and a uniform random policy scores about -0.36 at --points 1
-and about -17 at 21.
+and about -17 at 21.  With --env tmaze an episode is one cue, a corridor of --length steps and one choice (+1 for the
+cue's arm, -1 for the other, 0 for none): any policy that does not remember the cue scores 0 on average, which from
+--length 4 on is every policy of the FF model; --arch lstm can reach +1.  --t-max sets the window (default 5: with
+--length 4 an episode is one window; a longer corridor needs memory across a window boundary).
 
 Defaults are the reference's hyperparameters (RMSpropAsync lr 7e-4, alpha 0.99, eps 0.1, clip 40, beta 0.01,
 gamma 0.99) on the FF model with 256 envs; the batched learner sums the gradient of all envs, so --batch-loss
@@ -21,7 +24,8 @@ device-side record, A3C.ppo_epoch_stats) are there to try.  --direct runs the en
 (DeviceNet.set_env(env, direct=True)): no frame pools are allocated, the curve is bit-identical.  One JSON line at
 the end (and --out FILE).
 
-    python scripts/train_catch.py [--env catch|breakout|pong] [--points 21] [--windows 4000] [--report 200]
+    python scripts/train_catch.py [--env catch|breakout|pong|tmaze] [--points 21] [--length 4] [--t-max 5]
+                                  [--windows 4000] [--report 200]
                                   [--envs 256] [--seed 0]
                                   [--lr 7e-4] [--opt rmsprop|adam] [--batch-loss sum|mean] [--gae-lambda 1.0]
                                   [--arch ff|lstm] [--ppo-epochs 1] [--ppo-clip 0.2] [--ppo-norm-adv] [--ppo-vclip X]
@@ -43,11 +47,11 @@ import asyncrl_amd as pkg  # noqa: E402
 
 def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", batch_loss="sum", gae_lambda=1.0,
           arch="ff", beta=1e-2, eps=None, device="cuda:0", log=print, env="catch", ppo_epochs=1, ppo_clip=0.2, ppo_norm_adv=False,
-          ppo_vclip=None, points=21, direct=False):
+          ppo_vclip=None, points=21, direct=False, length=4, t_max=5):
     """Returns the curve: one dict per report with the window count, the episodes completed since the last
     report and their mean return, and the newest window record's entropy / value / gradient norm."""
     dev = torch.device(device)
-    T, A, P = 5, 4, 2
+    T, A, P = t_max, 4, 2
     model = (pkg.A3CFF if arch == "ff" else pkg.A3CLSTM)(A, n_envs=envs, t_max=T, seed=seed, init_seed=seed,
                                                          device=dev, frames="pairs")
     if opt == "adam":
@@ -63,6 +67,8 @@ def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", ba
     net.set_window_stats(True)
     if env == "pong":
         game = pkg.DevicePong(envs, device=dev, seed=seed, points=points)
+    elif env == "tmaze":
+        game = pkg.DeviceTMaze(envs, device=dev, seed=seed, length=length)
     else:
         game = (pkg.DeviceBreakout if env == "breakout" else pkg.DeviceCatch)(envs, device=dev, seed=seed)
     pools = (None, None, None) if direct else game.make_pools(P)   # direct: the frame pairs never exist
@@ -108,8 +114,10 @@ def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", ba
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--env", choices=("catch", "breakout", "pong"), default="catch")
+    ap.add_argument("--env", choices=("catch", "breakout", "pong", "tmaze"), default="catch")
     ap.add_argument("--points", type=int, default=21)
+    ap.add_argument("--length", type=int, default=4)
+    ap.add_argument("--t-max", type=int, default=5)
     ap.add_argument("--envs", type=int, default=256)
     ap.add_argument("--windows", type=int, default=4000)
     ap.add_argument("--report", type=int, default=200)
