@@ -6,9 +6,9 @@
 // (norm = sqrt(sum of per-array squared norms); if 40/norm < 1: g *= 40/norm).
 //
 // Two launches per update, both HBM-streaming over the padded flat buffer:
-//   grad_sqnorm_kernel: per-block partial sum of g^2 (f32 per thread over a
-//     grid-stride, f64 across the block) -> partials[block] (the folded form:
-//     reduce_conv_bwd_kernel leaves the same partials, conv_bwd.hip), so the
+//   grad_sqnorm_kernel: per-block partial sum of g^2 (f64 per thread over a
+//     grid-stride and across the block) -> partials[block] (the folded form:
+//     reduce_conv_bwd_kernel leaves partials of f32 per-thread sums, conv_bwd.hip), so the
 //     clip rate needs no host round trip and no extra launch;
 //   the update kernel (update_body below, written once; rmsprop_kernel and adam_kernel are its entry points):
 //     every block sums the partials in block order (their loads in flight with its first p / state / g
@@ -60,18 +60,21 @@ __global__ void __launch_bounds__(256)
 grad_sqnorm_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ partials) {
   __shared__ double sh[8];
   const int64_t n4 = n >> 2;
-  float acc = 0.f;
+  // f64 throughout: an f32 square is exact in f64, so the sum is the f64 norm a host forms (oracle.clip_grads,
+  // exact_norm) to about 1e-16, and f32(clip / norm) is the same f32.  With f32 sums per thread the scale could
+  // come out one ulp off, which moves a parameter's last bit when the clip is active.
+  double acc = 0.0;
   const float4* g4 = reinterpret_cast<const float4*>(g);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     const float4 v = g4[i];
-    acc = __fadd_rn(acc, __fadd_rn(__fadd_rn(__fmul_rn(v.x, v.x), __fmul_rn(v.y, v.y)),
-                                   __fadd_rn(__fmul_rn(v.z, v.z), __fmul_rn(v.w, v.w))));
+    const double x = v.x, y = v.y, z = v.z, w = v.w;
+    acc += (x * x + y * y) + (z * z + w * w);
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const float v = g[(n4 << 2) + threadIdx.x];
-    acc = __fadd_rn(acc, __fmul_rn(v, v));
+    const double v = g[(n4 << 2) + threadIdx.x];
+    acc += v * v;
   }
-  const double t = block_sum_f64((double)acc, sh);
+  const double t = block_sum_f64(acc, sh);
   if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 

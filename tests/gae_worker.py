@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.join(HERE, "..", "async-rl_amd"), os.path.join(HERE, "..", "oracle"), HERE]
 from sim import make_pools  # noqa: E402
 
-CASES = [(33, 5, 4), (33, 9, 6), (5, 5, 18)]          # (n, T, A)
+CASES = [(33, 5, 4), (33, 9, 6), (5, 5, 18), (5, 33, 6)]   # (n, T, A); T = 33: a second pass over rows
 KEYS = ("dlogits", "dv", "loss", "dfc", "v")
 
 

@@ -522,18 +522,20 @@ def conv_data(n_envs, t_max, layout="ring", seed=0):
             "x": RingX(frames, nvalid, N, T, layout)}
 
 
-def conv_fwd_data(n_envs, layout="ring", seed=0):
+def conv_fwd_data(n_envs, layout="ring", seed=0, t_max=1):
     """Operands of the conv_fwd stage on a t_max = 1 net (slots 0 and 1, a ring of 5):
     frames and nvalid as conv_data (ring: nvalid from 1..4, a masked plane on env 0
     of both slots), the two convs' weights and biases, and x: RingX over both
-    slots, sample t * n_envs + e; xint: the same with integer pixel values."""
-    rng = np.random.default_rng([seed, n_envs, 1, 6])
-    N, T, R = n_envs, 1, 5
+    slots, sample t * n_envs + e; xint: the same with integer pixel values.
+    t_max > 1: a ring of t_max + 4 and all t_max + 1 slots, env 0 masked at slot
+    t_max too."""
+    rng = np.random.default_rng([seed, n_envs, t_max, 6])
+    N, T, R = n_envs, t_max, t_max + 4
     planes = {"ring": (), "stack": (4,), "rgb": (3,)}[layout]
     frames = rng.integers(0, 256, (R, N) + planes + (84, 84), dtype=np.uint8)
     if layout == "ring":
         nvalid = rng.integers(1, 5, (R, N)).astype(np.uint8)
-        nvalid[0, 0], nvalid[1, 0] = 2, 3
+        nvalid[0, 0], nvalid[1, 0], nvalid[T, 0] = 2, 3, 3
     else:
         nvalid = np.full((R, N), 4 if layout == "stack" else 3, np.uint8)
     C = 3 if layout == "rgb" else 4
@@ -568,14 +570,40 @@ def bptt_data(n_envs, t_max, t, seed=0):
             "dcn": rng.standard_normal((N, HID), F32) * F32(1e-3), "Wl": weight_like(rng, (GATES, HID))}
 
 
-def bptt_chain_data(n_envs, t_max, seed=0):
+def crafted_flags(rng, t_max, n_envs, p=0.03):
+    """(T, N) uint8 reset / terminal flags of the long-window cases (T >= 33), where a drawn 15 - 20 % would leave
+    no chain longer than a few steps: env 0 never flagged, env 1 at steps 0 and T - 1 only, env 2 once past step
+    32 (step 40, or T - 1 where the window ends before it), every other env at about p a step."""
+    T, N = t_max, n_envs
+    assert T >= 33
+    f = (rng.random((T, N)) < p).astype(np.uint8)
+    f[:, :3] = 0
+    if N > 1:
+        f[0, 1] = f[T - 1, 1] = 1
+    if N > 2:
+        f[40 if T > 41 else T - 1, 2] = 1
+    return f
+
+
+def crafted_flags_hold(f):
+    """The conditions crafted_flags exists for, on any (T, N) flags: an env with an unbroken chain over the whole
+    window, a flag at step 0, one at step T - 1 and one past step 32."""
+    f = np.asarray(f) != 0
+    return bool((~f.any(0)).any() and f[0].any() and f[-1].any() and f[32:].any())
+
+
+def bptt_chain_data(n_envs, t_max, seed=0, crafted=None):
     """Operands of LEARN_TRUNK's BPTT chain on top of lstm_data / fc_data (finite
     operands for the weight-gradient and FC launches that follow): gates and cbuf
     of every step (cbuf slot 0 a sentinel on the rows reset at step 0, slots past
-    the window sentinels), the heads' dh, the lateral weight; hbuf slot T finite."""
+    the window sentinels), the heads' dh, the lateral weight; hbuf slot T finite.
+    crafted (default: the cases of BPTT_LONG_CASES): the window's reset flags are
+    crafted_flags, from a generator of their own, instead of lstm_data's ~20 %."""
     rng = np.random.default_rng([seed, n_envs, t_max, 8])
     N, T = n_envs, t_max
     d = lstm_data(N, T, seed)
+    if (n_envs, t_max) in BPTT_LONG_CASES if crafted is None else crafted:
+        d["reset"][:T] = crafted_flags(np.random.default_rng([seed, n_envs, t_max, 15]), T, N)
     d["fc"] = fc_data(N, T, lstm=True, seed=seed)
     d["hbuf"][T] = rng.standard_normal((N, HID), F32) * F32(0.5)
     gates = np.full((T + 1, N, GATES), SENTINEL, F32)
@@ -709,7 +737,7 @@ def fused_data(t_max, n_actions, n_envs, seed=0):
 FC_CASES = [(1, 1), (43, 3), (109, 11), (240, 5), (241, 5), (400, 5)]
 FC_LSTM_ARCH_CASE = (41, 5)
 LSTM_CASES = [(1, 1), (43, 3), (256, 4), (205, 5), (400, 5)]
-CONV_CASES = [(1, 1), (255, 1), (257, 1), (52, 5), (67, 9), (513, 5)]
+CONV_CASES = [(1, 1), (255, 1), (257, 1), (52, 5), (67, 9), (513, 5), (3, 64)]
 CONV_LAYOUT_CASE = (52, 5)   # also run as rgb (DoomA3CFF) and stack
 LAUNCHES = 4                 # at Z > 1: launches in a row, each with fresh gradients
 # conv_fwd (n_envs, layout), each at slots 0 and 1 of a t_max = 1 net: from 512 envs two envs a workgroup
@@ -717,7 +745,10 @@ CONV_FWD_CASES = [(1, "ring"), (5, "ring"), (512, "ring"), (513, "ring"), (5, "r
                   (513, "stack")]
 BPTT_CASES = [(n, t) for n in (1, 33, 64) for t in (1, 2)]   # (n_envs, t) on a t_max = 3 net
 BPTT_T = 3
-BPTT_CHAIN_CASES = [(37, 5), (1, 5)]
+BPTT_LONG_CASES = [(3, 64), (33, 33)]   # crafted reset flags: a chain over the whole window (bptt_chain_data)
+BPTT_CHAIN_CASES = [(37, 5), (1, 5)] + BPTT_LONG_CASES
+CONV_FWD_LONG_CASE = (3, 64, (0, 63, 64))   # (n_envs, t_max, slots): conv_fwd on a ring of 68, slot T the bootstrap
+CONV_FWD_RING_T = 33                          # the T of the long ring-residue case: R = 37
 # returns (t_max, n_actions, n_envs): one case for each returns_heads_kernel<AM, RB> and row-pass count
 RETURNS_CASES = [(1, 1, 1), (8, 4, 3), (8, 5, 3), (8, 8, 2), (8, 9, 2), (9, 4, 3), (32, 32, 2), (33, 6, 2), (64, 32, 2)]
 RETURNS_LSTM_CASE = (5, 6, 3)
@@ -1019,6 +1050,8 @@ def states_data(n_envs, t_max, seed=0):
 # sensitivity checks on the same data
 NATURE_CASES = [(1, 1, 4), (33, 5, 18), (67, 2, 6)]    # (n_envs, t_max, n_actions)
 NATURE_HEADS_CASE = (41, 9, 4)                         # the heads and fc_bwd only
+# the heads GEMM's M = A + 1 rows in 16-row tiles: one exact tile; the second tile holds the value row alone
+NATURE_HEADS_EDGE_CASES = [(5, 3, 15), (5, 3, 16)]
 NATURE_LEARN_CASES = [(33, 5, 18), NATURE_HEADS_CASE]
 NATURE_RING_CASE = (33, 5, 18)
 STATES_CASES = [(1, 1), (33, 5)]                       # (n_envs, t_max)

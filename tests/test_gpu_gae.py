@@ -70,7 +70,7 @@ def replay_case(c, T, lam, pcoef=1.0, keep=False, clip_reward=True):
 # window and the widest action set; the smallest.  The first case carries a truncated env (dones bit 1 on its
 # tail, closed by a terminal) and the loss options.
 GRANULAR = [(5, 52, 4, dict(truncate=True, pcoef=0.5, keep=True)), (9, 29, 6, dict(clip_reward=False)),
-            (64, 5, 18, {}), (1, 3, 4, {})]
+            (64, 5, 18, {}), (1, 3, 4, {}), (5, 33, 16, {})]   # the last: A = 16, at the heads' 16-column tile edge
 _NSTEP = {}
 
 
@@ -204,7 +204,8 @@ def test_lstm_window_matches_the_replay(gpu):
 
 def test_fused_bootstrap_launch_equals_the_separate_one(gpu, tmp_path):
     """The window as one C call (the returns in policy_fc_returns_kernel) in this process against the window issued
-    step by step with the separate returns_heads_kernel launch in a child, three shapes, lambda 0.95, bit for bit."""
+    step by step with the separate returns_heads_kernel launch in a child, four shapes (one at T = 33, the 32-row forms'
+    second pass), lambda 0.95, bit for bit."""
     import gae_worker
     from asyncrl_amd import a3c
     assert a3c.WINDOW_C and a3c.FUSE_RETURNS
@@ -214,7 +215,7 @@ def test_fused_bootstrap_launch_equals_the_separate_one(gpu, tmp_path):
     subprocess.run([sys.executable, os.path.join(here, "gae_worker.py"), f1, "0.95"],
                    env=dict(os.environ, ARL_WINDOW_C="0", ARL_FUSE_RETURNS="0"), check=True, timeout=240)
     a, b = np.load(f0), np.load(f1)
-    assert sorted(a.files) == sorted(b.files) and len(a.files) == 3 * 7
+    assert sorted(a.files) == sorted(b.files) and len(a.files) == len(gae_worker.CASES) * 7 == 4 * 7
     for k in a.files:
         assert bits_equal(a[k], b[k]), k
         assert np.isfinite(a[k]).all() and (np.abs(a[k]).max() > 0 or k.endswith("dfc")), k
@@ -245,21 +246,28 @@ def test_dropin_act_with_a_truncated_window(gpu):
     """A3C(gae_lambda=0.95).act on a one-env model: an episode that ends 3 steps into a window (the truncated
     update), then a full window.  After each update the parameters equal oracle clip + RMSProp on the replay's
     gradient, 1e-5 norm-scaled as test_gpu_dropin holds the reference's trajectories."""
+    dropin_truncated_window(gpu)
+
+
+def dropin_truncated_window(gpu, T=5, cut=3):
+    """The body of the test above at t_max T, the episode ending `cut` steps into the first window."""
     from asyncrl_amd import A3C, A3CFF, GradientClipping, RMSpropAsync, dqn_phi
-    T, A, lam = 5, 4, 0.95
+    A, lam = 4, 0.95
+    calls = cut + T + 2
     model = A3CFF(A, n_envs=1, t_max=T, seed=4, init_seed=2, device=gpu)
     opt = RMSpropAsync(lr=7e-4, eps=1e-1, alpha=0.99).setup(model)
     opt.add_hook(GradientClipping(40.0))
     agent = A3C(model, opt, T, GAMMA, beta=BETA, phi=dqn_phi, gae_lambda=lam)
     net = model.net
     rng = np.random.default_rng(9)
-    stacks = rng.integers(0, 256, (10, 4, 84, 84), dtype=np.uint8)
+    stacks = rng.integers(0, 256, (calls, 4, 84, 84), dtype=np.uint8)
     rewards = [0.0, 2.0, -0.3, 0.7, 0.0, 0.5, -1.5, 0.25, 0.0, 1.0]       # reward[k]: of the transition into call k
-    terminal = [False, False, False, True] + [False] * 6
-    updates = {3: (0, 3), 9: (4, 5)}                                      # call -> (first call of its window, steps)
+    rewards = (rewards * -(-calls // 10))[:calls]
+    terminal = [False] * cut + [True] + [False] * (T + 1)
+    updates = {cut: (0, cut), cut + T + 1: (cut + 1, T)}                  # call -> (first call of its window, steps)
     acts, n_updates = {}, 0
     params, ms = net.state_dict(), net.state_dict(net.ms)
-    for k in range(10):
+    for k in range(calls):
         a = agent.act(list(stacks[k]), rewards[k], terminal[k])
         assert (a is None) == terminal[k]
         if k in updates:

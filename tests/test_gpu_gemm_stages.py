@@ -232,7 +232,7 @@ def test_nature_fc_fwd_policy_stages(gpu, case):
 
 
 # ------------------------------------------------------------------ Nature: fc_bwd
-@pytest.mark.parametrize("case", R.NATURE_CASES + [R.NATURE_HEADS_CASE])
+@pytest.mark.parametrize("case", R.NATURE_CASES + [R.NATURE_HEADS_CASE] + R.NATURE_HEADS_EDGE_CASES)
 def test_nature_fc_bwd_stage(gpu, case):
     """fc_bwd of a Nature net against nature_fc_bwd_ref: the weight gradient launch_gemm<64,
     64, GM, GM>(ColMajor dfc, OnesColB a3) with N = 3137 (the bias column alone in the
@@ -240,7 +240,10 @@ def test_nature_fc_bwd_stage(gpu, case):
     0) launch_gemm<64, 64, GK, GM> with EpiMask.  (1, 1, 4): K = 1, one slice; (33, 5, 18):
     S = 165 in slices of 96 + 69, da3 with a 37-row last tile; (67, 2, 6): 96 + 38; (41,
     9, 4): S = 369 in 192 + 177.  Two slices: four launches in a row with fresh dfc (a
-    stale slab row shows).  Every other gradient tensor keeps its prefill."""
+    stale slab row shows).  Every other gradient tensor keeps its prefill.  (5, 3, 15) and
+    (5, 3, 16): the slab sized by heads GEMMs of one exact 16-row tile and of a second tile
+    that holds the value row alone (nature_net asserts the size; the heads GEMM itself runs
+    in test_nature_learn_synthetic_window)."""
     d = nature_case(*case)
     T, S = d["T"], d["S"]
     net = nature_net(d)
@@ -301,7 +304,7 @@ def test_nature_conv_bwd_ring_residues(gpu, start):
 
 # ------------------------------------------------------------------ Nature: net.learn()
 @pytest.mark.parametrize("lam", R.GAE_LAMBDAS)
-@pytest.mark.parametrize("case", R.NATURE_LEARN_CASES)
+@pytest.mark.parametrize("case", R.NATURE_LEARN_CASES + R.NATURE_HEADS_EDGE_CASES)
 def test_nature_learn_synthetic_window(gpu, case, lam):
     """net.learn() of a Nature net on a synthetic workspace (rewards, dones, v, probs, logp,
     actions, hfc, a3, a2, a1, frames) against the chained reference nature_learn_ref: the
@@ -310,8 +313,9 @@ def test_nature_learn_synthetic_window(gpu, case, lam):
     launch_gemm<16, 64, GS, GM>(HeadsGA, OnesColB) with its MapHeads reduce, and
     heads_bwd_kernel.  (33, 5, 18): 19 rows = two M tiles of the heads GEMM, two K slices,
     one returns workgroup from registers (T <= 8); (41, 9, 4): three K slices (128 + 128 +
-    113), T > 8 (the returns scan from memory), two returns workgroups (28 envs each).
-    All 12 gradient tensors, dlogits, dv, the per-env losses and dfc."""
+    113), T > 8 (the returns scan from memory), two returns workgroups (28 envs each); (5, 3,
+    15): M = 16, one exact tile of the heads GEMM; (5, 3, 16): M = 17, the value row alone
+    in the second tile.  All 12 gradient tensors, dlogits, dv, the per-env losses and dfc."""
     d = nature_case(*case)
     N, T, A, S = d["N"], d["T"], d["A"], d["S"]
     outs, g, mag = nature_learn_case(case, lam)

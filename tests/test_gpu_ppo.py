@@ -26,8 +26,8 @@ GAMMA, BETA, VCOEF, EPS = 0.99, 0.01, 0.5, 0.2
 GRID = np.array([-0.6, -0.35, -0.1, 0.1, 0.35, 0.6], F32)
 # (T, n, A): EB = 51 envs a block at T = 5, so 75 envs leave a partial second block; T = 9 takes the looped path
 # past RW = 8; one env and the widest action set the register forms are built for; T = 8, the last length the
-# register windows (RW, PO_RW) hold
-SHAPES = [(5, 75, 4), (9, 33, 6), (5, 1, 18), (8, 33, 6)]
+# register windows (RW, PO_RW) hold; A = 16, at the edge of the heads' 16-column tiles
+SHAPES = [(5, 75, 4), (9, 33, 6), (5, 1, 18), (8, 33, 6), (5, 33, 16)]
 
 
 def dev(x, gpu):
@@ -191,7 +191,8 @@ LR2 = 8e-3     # the update between the epochs: see test_epoch_two_against_the_o
 
 # (N, T, A) of the nets whose first epoch is compared with the A3C learn: one for each shape the loss-gradient
 # launch's register forms are built for -- A <= 4, A <= 8, wider (all T <= 8), and T > 8
-NET_SHAPES = [(64, 5, 4), (5, 5, 6), (5, 5, 18), (5, 9, 4)]
+# (both 32 rows a pass: the memory form); T = 33 and 64, a second pass over rows with one row and with all 32
+NET_SHAPES = [(64, 5, 4), (5, 5, 6), (5, 5, 18), (5, 9, 4), (5, 33, 6), (3, 64, 4)]
 
 
 def state_pools(shape=(N, T, A)):
@@ -220,7 +221,8 @@ def learner_outputs(net):
     return out
 
 
-def dev_acts(net):
+def dev_acts(net, shape=(N, T, A)):
+    N, T, _ = shape
     a1 = net.buffer("a1", torch.float32, (T + 1, N, 16, 20, 20))[:T].cpu().numpy()
     a2 = net.buffer("a2", torch.float32, (T + 1, N, 32, 9, 9))[:T].cpu().numpy()
     h = net.buffer("hfc", torch.float32, (T + 1, N, 256))[:T].cpu().numpy()
@@ -257,11 +259,16 @@ def test_epoch_two_against_the_oracle(gpu):
     oracle RMSProp step puts the ratios in 0.888 .. 1.188 at lr 2e-3 (none inactive; the device measured the
     same range), 0.762 .. 1.446 at 5e-3 (15 % inactive) and 0.635 .. 1.762 at 8e-3 (36 % inactive).  The
     reference asserts that share below, before the gradient is compared."""
+    epoch_two_against_the_oracle(gpu, (N, T, A), LR2)
+
+
+def epoch_two_against_the_oracle(gpu, shape, lr):
     from asyncrl_amd import A3CFF
     lam = 0.95
-    states, rewards, dones = state_pools()
+    N, T, A = shape
+    states, rewards, dones = state_pools(shape)
     pools = tuple(dev(x, gpu) for x in (states, rewards, dones))
-    net = rollout(gpu, pools, lam, True)
+    net = rollout(gpu, pools, lam, True, shape)
     net.ppo_begin(GAMMA, True)
     net.ppo_learn(BETA, VCOEF)
     torch.cuda.synchronize()
@@ -269,7 +276,7 @@ def test_epoch_two_against_the_oracle(gpu):
     acts_t = net.buffer("actions", torch.int32, (T + 1, N)).clone()
     boot = {k: v.clone() for k, v in net.step_outputs(T).items()}
     step0 = int(net.buffer("ctl", torch.int64)[0])
-    net.optimize(lr0=LR2, alpha=0.99, eps=0.1, clip=40.0)
+    net.optimize(lr0=lr, alpha=0.99, eps=0.1, clip=40.0)
     for t in range(T):
         net.act(t, mode=0)
     net.ppo_learn(BETA, VCOEF)
@@ -303,7 +310,7 @@ def test_epoch_two_against_the_oracle(gpu):
                             for k in ("logp_old", "adv", "ret", "ratio"))
     with ppo_ref.patched(lpo, adv, ret, EPS, rho=ratio):
         g, aux = O.ff_window_grads(params, x, acts, r, d, bstate, gamma=GAMMA, beta=BETA, v_loss_coef=VCOEF,
-                                   dev_acts=dev_acts(net))
+                                   dev_acts=dev_acts(net, shape))
     lg = aux["logits"].reshape(T * N, A)
     own = ppo_ref.lossgrad(d, aux["v"], O.softmax(lg).reshape(T, N, A), O.log_softmax(lg).reshape(T, N, A), acts, lpo, adv,
                            ret, EPS, BETA, 1.0, VCOEF)

@@ -26,9 +26,11 @@ HID, GATES = 256, 1024
 LR1 = 7e-4      # the plain A3C update that ends the first window
 LR2 = 2e-2      # the update between epochs 1 and 2: see test_epoch_two_against_the_oracle
 # (N, T, A), the smallest that reach each path: a full 32-row tile plus a ragged row; wide heads; the T > 8 memory
-# forms; no BPTT step; one BPTT step
-SHAPES = [(33, 5, 6), (5, 5, 18), (5, 9, 4), (5, 1, 4), (64, 2, 4)]
+# forms; no BPTT step; one BPTT step; 32 and 63 BPTT steps with the loss-gradient launch's second row pass
+SHAPES = [(33, 5, 6), (5, 5, 18), (5, 9, 4), (5, 1, 4), (64, 2, 4), (3, 33, 6), (2, 64, 4)]
 N, T, A = SHAPES[0]
+LONG = (3, 33, 6)   # the re-forward and the carry once more over 33 steps (hbuf / cbuf / the carry's rows 0 and 33)
+LONG_TRUNCATE = 20
 
 _POOLS = {}
 
@@ -113,17 +115,18 @@ def test_epoch_one_is_the_a3c_lstm_gradient(gpu, shape, lam):
 _E2 = {}
 
 
-def epoch_two(gpu):
-    """The net of tests 2 and 3, run once: epoch 1, an RMSProp update at LR2, the re-forward and epoch 2 on the
-    second window of a (33, 5, 6) net at lambda 0.95; with what has to be compared later, cloned at its time."""
-    if _E2:
-        return _E2
-    _, pools = pools_of(gpu, SHAPES[0])
-    net = second_window(gpu, pools, 0.95, True)
+def epoch_two(gpu, shape=SHAPES[0]):
+    """The net of tests 2 and 3, run once a shape: epoch 1, an RMSProp update at LR2, the re-forward and epoch 2 on
+    the second window of a (33, 5, 6) net at lambda 0.95; with what has to be compared later, cloned at its time."""
+    if shape in _E2:
+        return _E2[shape]
+    N, T, A = shape
+    _, pools = pools_of(gpu, shape)
+    net = second_window(gpu, pools, 0.95, True, shape)
     net.ppo_begin(GAMMA, True)
     net.ppo_learn(BETA, VCOEF)
     torch.cuda.synchronize()
-    k = _E2
+    k = _E2[shape] = {}
     k["net"] = net
     k["snap"] = {n_: v.clone() for n_, v in net.ppo_planes().items()}
     k["actions"] = net.buffer("actions", torch.int32, (T + 1, N)).clone()
@@ -147,10 +150,15 @@ def epoch_two(gpu):
 
 
 def test_the_reforward_is_the_forward(gpu):
+    reforward_is_the_forward(gpu, SHAPES[0])
+
+
+def reforward_is_the_forward(gpu, shape):
     from asyncrl_amd import A3CLSTM
-    k = epoch_two(gpu)
+    N, T, A = shape
+    k = epoch_two(gpu, shape)
     net = k["net"]
-    _, pools = pools_of(gpu, SHAPES[0])
+    _, pools = pools_of(gpu, shape)
     # what must not have moved
     assert tbits(net.buffer("actions", torch.int32, (T + 1, N)), k["actions"])
     for name, v in net.step_outputs(T).items():
@@ -250,8 +258,13 @@ def two_epochs(net):
 
 @pytest.mark.parametrize("fused", [True, False], ids=["optimize_advance", "optimize-then-advance"])
 def test_the_carry_is_the_rollouts_state(gpu, fused):
-    _, pools = pools_of(gpu, SHAPES[0])
-    net = second_window(gpu, pools, 0.95, True)
+    carry_is_the_rollouts_state(gpu, fused, SHAPES[0])
+
+
+def carry_is_the_rollouts_state(gpu, fused, shape):
+    T = shape[1]
+    _, pools = pools_of(gpu, shape)
+    net = second_window(gpu, pools, 0.95, True, shape)
     hT, cT = two_epochs(net)
     rsT = reset_rows(net)[T].clone()
     if fused:
@@ -269,14 +282,18 @@ def test_the_carry_is_the_rollouts_state(gpu, fused):
 
 
 def test_the_carry_after_a_truncated_window(gpu):
-    _, pools = pools_of(gpu, SHAPES[0])
-    one = second_window(gpu, pools, 0.95, False, truncate=2)
+    carry_after_a_truncated_window(gpu, SHAPES[0], 2)                 # two live steps, three past the window's end
+
+
+def carry_after_a_truncated_window(gpu, shape, tr):
+    _, pools = pools_of(gpu, shape)
+    one = second_window(gpu, pools, 0.95, False, shape, truncate=tr)
     one.learn(GAMMA, BETA, VCOEF, True)
     one.optimize(lr0=LR2, alpha=0.99, eps=0.1, clip=40.0, advance=True)
-    net = second_window(gpu, pools, 0.95, True, truncate=2)
+    net = second_window(gpu, pools, 0.95, True, shape, truncate=tr)
     hT, cT = two_epochs(net)
     live = net.ppo_planes()["ratio"] > 0
-    assert bool(live[:2].all()) and not bool(live[2:].any())          # two live steps, three past the window's end
+    assert bool(live[:tr].all()) and not bool(live[tr:].any())        # tr live steps, the rest past the window's end
     net.optimize(lr0=LR2, alpha=0.99, eps=0.1, clip=40.0, advance=True)
     torch.cuda.synchronize()
     for name in ("hbuf", "cbuf"):

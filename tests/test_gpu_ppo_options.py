@@ -24,7 +24,7 @@ GAMMA, BETA, VCOEF, EPS, VEPS = 0.99, 0.01, 0.5, 0.2, 0.1
 # test_gpu_ppo.py's three (a partial second block, the looped path past RW = 8, one env) and one whose 600 envs make
 # a thread of the single workgroup walk three envs, the last pass ragged (600 = 2 * 256 + 88); and T = 8, the last
 # length the one-workgroup kernels' register window (PO_RW) holds
-SHAPES = [(5, 75, 4), (9, 33, 6), (5, 1, 18), (4, 600, 4), (8, 33, 6)]
+SHAPES = [(5, 75, 4), (9, 33, 6), (5, 1, 18), (4, 600, 4), (8, 33, 6), (5, 33, 16)]   # the last: A at the 16-column edge
 VGRID = np.array([-0.3, -0.15, -0.05, 0.05, 0.15, 0.3], F32)
 
 _CASES = {}
@@ -256,15 +256,19 @@ def test_net_epoch_two(gpu):
     """Both options on; one RMSProp update at test_gpu_ppo.py's LR2 between the epochs, which moves the ratios to
     0.64 .. 1.76 there.  The workspace's dlogits / dv of epoch 2 against the restatement on the workspace's own v /
     probs / log_probs, the snapshot, v_old and the device's ratio; the record of epoch 2 likewise."""
-    N, T, A = G.N, G.T, G.A
-    pools = tuple(dev(x, gpu) for x in G.state_pools())
-    net = net_rollout(gpu, pools, 0.95, True, VEPS)
+    net_epoch_two(gpu, (G.N, G.T, G.A), G.LR2)
+
+
+def net_epoch_two(gpu, shape, lr):
+    N, T, A = shape
+    pools = tuple(dev(x, gpu) for x in G.state_pools(shape))
+    net = net_rollout(gpu, pools, 0.95, True, VEPS, shape)
     net.ppo_begin(GAMMA, True)
     net.ppo_learn(BETA, VCOEF)
     torch.cuda.synchronize()
     snap = {k: v.clone() for k, v in net.ppo_planes().items()}
     v_old = net.ppo_v_old.clone()
-    net.optimize(lr0=G.LR2, alpha=0.99, eps=0.1, clip=40.0)
+    net.optimize(lr0=lr, alpha=0.99, eps=0.1, clip=40.0)
     for t in range(T):
         net.act(t, mode=0)
     net.ppo_learn(BETA, VCOEF)

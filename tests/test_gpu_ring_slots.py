@@ -17,6 +17,7 @@ import torch
 import oracle as O
 from conftest import close_normscaled, grads_match
 from sim import make_pools, make_rgb_pools
+from stage_ref import ring_starts
 
 pytestmark = pytest.mark.gpu
 
@@ -50,24 +51,26 @@ def pools(layout):
     return obs, rewards, dones, planes
 
 
-def make_net(layout):
+def make_net(layout, T=T):
     from asyncrl_amd import A3CFF, DoomA3CFF
     if layout == "rgb":
         return DoomA3CFF(A, n_envs=N, t_max=T, seed=11, init_seed=3).net
     return A3CFF(A, n_envs=N, t_max=T, seed=11, init_seed=3, frames="stacks" if layout == "stack" else "pairs").net
 
 
-def dev_acts(net):
+def dev_acts(net, T=T):
     a1 = net.buffer("a1", torch.float32, (T + 1, N, 16, 20, 20))[:T].cpu().numpy()
     a2 = net.buffer("a2", torch.float32, (T + 1, N, 32, 9, 9))[:T].cpu().numpy()
     h = net.buffer("hfc", torch.float32, (T + 1, N, 256))[:T].cpu().numpy()
     return a1.reshape(T * N, 16, 20, 20), a2.reshape(T * N, 32, 9, 9), h.reshape(T * N, 256)
 
 
-def run_case(gpu, layout, start, P, windows=R + 1):
+def run_case(gpu, layout, start, P, windows=None, T=T):
+    R = T + 4
+    windows = R + 1 if windows is None else windows
     obs, rewards, dones, planes = pools(layout)
     arch = O.ARCH_FF | (O.ARCH_RGB if layout == "rgb" else 0)
-    net = make_net(layout)
+    net = make_net(layout, T)
     net.reset()
     ctl = net.buffer("ctl", torch.int64)
     ctl[CTL_STEP] = start
@@ -134,7 +137,7 @@ def run_case(gpu, layout, start, P, windows=R + 1):
             torch.cuda.synchronize()
             acts = net.buffer("actions", torch.int32, (T + 1, N))[:T].cpu().numpy()
             g, aux = O.ff_window_grads(params, xs, acts, rewards[idx], dones[idx], boot, arch=arch,
-                                       dev_acts=dev_acts(net))
+                                       dev_acts=dev_acts(net, T))
             want_l, want_v, want_b = aux["logits"], aux["v"], aux["vboot"]
             grads_match(net.state_dict(net.grads), g, aux["grad_mag"], rtol=RTOL, rtol_elem=RTOL)
         else:
@@ -156,6 +159,15 @@ def run_case(gpu, layout, start, P, windows=R + 1):
 @pytest.mark.parametrize("start", STARTS)
 def test_ring_slots_follow_the_counter(gpu, start, P):
     run_case(gpu, "ring", start, P)
+
+
+@pytest.mark.parametrize("start", ring_starts(33))
+def test_ring_slots_follow_the_counter_in_a_long_ring(gpu, start):
+    """t_max 33: a ring of R = 37 slots, its fd_make(37) residues with the counter at R - 1, 2^32 - 3 and a
+    multiple of T above 2^40 (stage_ref.ring_starts), pool length 7 (no divisor of 37; 33 steps wrap it four
+    times), two windows, the second across the ring's end."""
+    assert start % 37 and 37 % PMAX and 33 % PMAX
+    run_case(gpu, "ring", start, PMAX, windows=2, T=33)
 
 
 @pytest.mark.parametrize("layout", ["rgb", "stack"])

@@ -173,7 +173,9 @@ def test_conv_bwd_stage(gpu, n_envs, t_max):
     """Ring layout, S = 1, 255 (below the 256-workgroup cap), 257 (only workgroup 0
     loops), 260 (workgroups 0..3 loop), 603 (3 / 2 samples a workgroup; the ring of
     13 slots wraps), 2565 (11 / 10 samples a workgroup, the bench's accumulation
-    depth).  nvalid is drawn from 1..4 per (slot, env)."""
+    depth), and (3, 64): S = 192 samples of 64 steps in a ring of 68 slots (slot
+    addressing at t up to 63, step 0's planes in slots 65 .. 67).  nvalid is drawn
+    from 1..4 per (slot, env)."""
     _conv_bwd(n_envs, t_max, "ring")
 
 
@@ -264,18 +266,10 @@ def test_fc_fwd_lstm_gates_stages(gpu, n_envs):
 MASK_PREFILL = 0x5A5A5A5A
 
 
-@pytest.mark.parametrize("n_envs,layout", R.CONV_FWD_CASES)
-def test_conv_fwd_stage(gpu, n_envs, layout):
-    """conv_fwd at slots 0 and 1 (the bootstrap slot) of a t_max = 1 net against
-    conv_fwd_ref: 1, 5 envs (one env a workgroup), 512 and 513 (two a workgroup; 513:
-    the last workgroup's second slot idle), the ring, RGB and stack frame layouts.
-    a1 / a2 at 1e-5 of the scale and a1 within a third of the error a dropped low
-    split plane of W1 makes (stage_ref.conv1_split_model); outside the tie band
-    the ReLU decisions and the a2_mask bits are the reference's; a2_mask is the
-    packed device a2 exactly; the other slot keeps its prefill."""
+def _conv_fwd(n_envs, layout, t_max=1, slots=(0, 1)):
     from asyncrl_amd import A3CFF, DoomA3CFF
-    d = R.conv_fwd_data(n_envs, layout)
-    N, T = n_envs, 1
+    d = R.conv_fwd_data(n_envs, layout, t_max=t_max)
+    N, T = n_envs, t_max
     if layout == "rgb":
         net = DoomA3CFF(3, n_envs=N, t_max=T, init_seed=0).net
     else:
@@ -285,9 +279,9 @@ def test_conv_fwd_stage(gpu, n_envs, layout):
     put(net, "nvalid", d["nvalid"], torch.uint8)
     for name, key in (("0/0/W", "W1"), ("0/0/b", "b1"), ("0/1/W", "W2"), ("0/1/b", "b2")):
         put_param(net, name, d[key])
-    a1r, a2r, z1, z2 = R.conv_fwd_ref(d["x"], d["W1"], d["b1"], d["W2"], d["b2"])
-    for t in (0, 1):
+    for t in slots:
         sl = slice(t * N, (t + 1) * N)
+        a1r, a2r, z1, z2 = R.conv_fwd_ref(d["x"][sl], d["W1"], d["b1"], d["W2"], d["b2"])
         net.buffer("a1", f32).fill_(R.PREFILL)
         net.buffer("a2", f32).fill_(R.PREFILL)
         net.buffer("a2_mask", torch.int32).fill_(MASK_PREFILL)
@@ -296,20 +290,42 @@ def test_conv_fwd_stage(gpu, n_envs, layout):
         a1 = get(net, "a1", (T + 1, N, 16, 20, 20))
         a2 = get(net, "a2", (T + 1, N, 32, 9, 9))
         words = net.buffer("a2_mask", torch.int32, (T + 1, N, R.A2W)).cpu().numpy().view(np.uint32)
-        e2 = close_normscaled(R.conv1_split_model(d["xint"][sl], d["W1"], d["b1"], 2), a1r[sl], RTOL)[1]
-        e1d, e2d = close_normscaled(a1[t], a1r[sl], RTOL)[1], close_normscaled(a2[t], a2r[sl], RTOL)[1]
-        print(f"conv_fwd {layout} N={N} t={t}: a1 {e1d:.3g} a2 {e2d:.3g} of the scale; a1 against the two-plane "
+        e2 = close_normscaled(R.conv1_split_model(d["xint"][sl], d["W1"], d["b1"], 2), a1r, RTOL)[1]
+        e1d, e2d = close_normscaled(a1[t], a1r, RTOL)[1], close_normscaled(a2[t], a2r, RTOL)[1]
+        print(f"conv_fwd {layout} N={N} T={T} t={t}: a1 {e1d:.3g} a2 {e2d:.3g} of the scale; a1 against the two-plane "
               f"model's {e2:.3g}: {e1d / e2:.3g}")
-        for got, want, z, what in ((a1[t], a1r[sl], z1[sl], "a1"), (a2[t], a2r[sl], z2[sl], "a2")):
+        for got, want, z, what in ((a1[t], a1r, z1, "a1"), (a2[t], a2r, z2, "a2")):
             assert not (got == R.PREFILL).any(), (what, t)
             _close(got, want, (what, t))
             sure = ~R.tie_band(z)
             assert (got[sure & (z < 0)] == 0).all() and (got[sure & (z > 0)] > 0).all(), (what, t)
         assert e1d <= e2 / 3, (t, e1d, e2)
         assert np.array_equal(words[t], R.pack_a2_mask(a2[t].reshape(N, R.A2))), t
-        sure = ~R.tie_band(z2[sl]).reshape(N, R.A2)
-        assert np.array_equal(R.unpack_a2_mask(words[t])[sure], (z2[sl] > 0).reshape(N, R.A2)[sure]), t
-        assert (a1[1 - t] == R.PREFILL).all() and (a2[1 - t] == R.PREFILL).all() and (words[1 - t] == MASK_PREFILL).all(), t
+        sure = ~R.tie_band(z2).reshape(N, R.A2)
+        assert np.array_equal(R.unpack_a2_mask(words[t])[sure], (z2 > 0).reshape(N, R.A2)[sure]), t
+        assert (np.delete(a1, t, 0) == R.PREFILL).all() and (np.delete(a2, t, 0) == R.PREFILL).all(), t
+        assert (np.delete(words, t, 0) == MASK_PREFILL).all(), t
+
+
+@pytest.mark.parametrize("n_envs,layout", R.CONV_FWD_CASES)
+def test_conv_fwd_stage(gpu, n_envs, layout):
+    """conv_fwd at slots 0 and 1 (the bootstrap slot) of a t_max = 1 net against
+    conv_fwd_ref: 1, 5 envs (one env a workgroup), 512 and 513 (two a workgroup; 513:
+    the last workgroup's second slot idle), the ring, RGB and stack frame layouts.
+    a1 / a2 at 1e-5 of the scale and a1 within a third of the error a dropped low
+    split plane of W1 makes (stage_ref.conv1_split_model); outside the tie band
+    the ReLU decisions and the a2_mask bits are the reference's; a2_mask is the
+    packed device a2 exactly; the other slot keeps its prefill."""
+    _conv_fwd(n_envs, layout)
+
+
+def test_conv_fwd_stage_long_ring(gpu):
+    """The same checks on a t_max = 64 net, 3 envs, at slots 0, 63 and 64 (the bootstrap
+    slot): the output rows of slots past 9 and a ring of R = 68 slots, where slot 0's
+    three older planes sit in slots 65 .. 67.  Every other slot of a1 / a2 / a2_mask
+    keeps its prefill."""
+    n_envs, t_max, slots = R.CONV_FWD_LONG_CASE
+    _conv_fwd(n_envs, "ring", t_max, slots)
 
 
 # ------------------------------------------------------------------ lstm_bptt
@@ -353,10 +369,18 @@ def test_lstm_bptt_chain(gpu, n_envs, t_max):
     """The learner's trunk part on an LSTM net, T = 5, 37 envs and 1: the first cell
     launch (dhn / dcn hold the sentinel: it must ignore them) and the T - 1 BPTT
     launches against lstm_bptt_chain_ref over the whole dG, then the LSTM weight
-    gradients of the same run against lstm_wgrad_ref fed the reference dG."""
+    gradients of the same run against lstm_wgrad_ref fed the reference dG.
+    (3, 64) and (33, 33): 63 and 32 BPTT launches on crafted reset flags (env 0's
+    chain runs over the whole window; resets at step 0, at step T - 1 and past step
+    32), 33 envs a second 32-row tile and two sample ranges of the weight gradient.
+    The float32 restatement of the chain differs from the float64 reference by at
+    most 2.9e-7 of the scale on these cases (tests/test_long_windows_ref.py), so the
+    suite's 1e-5 holds here as it stands."""
     from asyncrl_amd import A3CLSTM
     from asyncrl_amd._lib import LEARN_TRUNK
     d = R.bptt_chain_data(n_envs, t_max)
+    if (n_envs, t_max) in R.BPTT_LONG_CASES:
+        assert R.crafted_flags_hold(d["reset"][:t_max]) and not d["reset"][:t_max, 0].any()
     fc = d["fc"]
     N, T, S = n_envs, t_max, d["S"]
     net = A3CLSTM(fc["A"], n_envs=N, t_max=T, init_seed=0, frames="pairs").net

@@ -125,11 +125,17 @@ def test_closed_loop_equals_host_driven_windows(gpu, kind, A, n, kw, length):
     a second net WITHOUT an env whose pools the host fills from the restatement's pairs, rewards and dones: the
     ring, the window buffers, the sampled actions and the parameters agree bit for bit after every window.  FF
     with A = 4 at 64 envs (and once more as two env groups on two streams), LSTM with A = 6 at 33."""
+    closed_loop(gpu, kind, A, n, kw, length)
+
+
+def closed_loop(gpu, kind, A, n, kw, length, T=5, windows=7):
+    """The body of the test above at a window length of T (pools of T + 2 entries: a window's T + 1 observations
+    fit, and the host's fill of window w + 1 does not reach back into them)."""
     import asyncrl_amd.a3c as a3c
-    T, Pl, windows = 5, 7, 7
+    Pl = T + 2
     agent, net, game, pools = make_agent(kind, A, n, T, Pl, gpu, length=length)
     host, hnet, _, hpools = make_agent(kind, A, n, T, Pl, gpu, length=length, env=False)
-    check = LoopCheck(n, length)
+    check = LoopCheck(n, length, keep=T + 3)
     init = net.params.clone()
     for w in range(windows):
         agent.run_window(*pools, Pl, first=(w == 0))
@@ -199,7 +205,10 @@ def test_direct_mode_equals_the_pairs_path(gpu, kind, A, n, length, graph):
     window: the frame ring, nvalid and the reset flags, the rewards, dones and actions rows, the control block,
     both env state halves, the parameters and the RMSProp state after the update (and the LSTM's rows), then the
     episode statistics.  Eagerly, and with window 0 eager and ONE captured direct window replayed."""
-    T, windows = 5, 7
+    direct_mode(gpu, kind, A, n, length, graph)
+
+
+def direct_mode(gpu, kind, A, n, length, graph, T=5, windows=7):
     pa, pnet, penv, ppools = build(kind, A, n, T, length, gpu, False)
     da, dnet, denv, dpools = build(kind, A, n, T, length, gpu, True)
     assert dpools[:3] == (None, None, None) and dnet.env_direct and not pnet.env_direct

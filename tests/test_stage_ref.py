@@ -578,6 +578,10 @@ def test_gemm_launch_geometry():
     assert R.slice_bounds(369, 3) == [(0, 128), (128, 256), (256, 369)] and R.slice_bounds(369, 2)[-1] == (192, 369)
     # tiles: the heads GEMM's M (A + 1 rows in tiles of 16), the FC forward's M (envs in tiles of 64), ragged edges
     assert R.ceil_div(18 + 1, 16) == 2 and R.ceil_div(4 + 1, 16) == 1 and R.ceil_div(R.NHID + 1, 64) == 9
+    # the heads GEMM at the tile edge: A = 15 is one exact 16-row tile, at A = 16 the second tile holds the value row alone
+    edge = {c: R.nature_plans(c[0] * c[1], c[2]) for c in R.NATURE_HEADS_EDGE_CASES}
+    assert [c[2] for c in edge] == [15, 16] and all(p == {"heads": 1, "fc": 1, "c3": 6, "c2": 10, "c1": 47} for p in edge.values())
+    assert (15 + 1) % 16 == 0 and R.ceil_div(15 + 1, 16) == 1 and R.ceil_div(16 + 1, 16) == 2 and (16 + 1) % 16 == 1
     assert R.ceil_div(67, 64) == 2 and 67 % 64 == 3 and R.ceil_div(33, 64) == 1
     assert 165 % 64 == 37 and (165 * 81) % 64 == 53 and (165 * 49) % 64 == 21 and (165 * 100) % 64 == 52
     assert (R.NA3 + 1) % 4 == 1 and (R.NHID + 1) % 4 == 1 and 257 % 4 == 1 and 577 % 64 == 1 and 513 % 64 == 1
