@@ -86,6 +86,8 @@ SIGNATURES = {
     "arl_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_double, c_double, c_double, c_double, c_i64,
                          c_double, c_void_p, c_double, c_void_p]),
     "arl_net_set_norm_fold": (c_int, [c_void_p, c_int]),
+    "arl_net_set_form": (c_int, [c_void_p, c_int, c_int]),
+    "arl_net_form": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_int)]),
     "arl_net_set_returns_fusion": (c_int, [c_void_p, c_int, c_double, c_double, c_double, c_int]),
     "arl_reset_state": (c_int, [c_void_p, c_i64, c_i64, c_void_p]),
     "arl_act": (c_int, [c_void_p, c_int, c_void_p]),
@@ -219,6 +221,9 @@ STAGE_NAMES = {1: "conv_fwd", 2: "fc_fwd", 3: "policy", 4: "fc_bwd", 5: "conv_bw
                8: "grad_sqnorm", 9: "lstm_gates", 10: "lstm_bptt", 11: "lstm_wgrad", 12: "phi", 13: "rmsprop",
                14: "lstm_cell", 15: "host", 16: "other"}
 STAGE_HOST = 15
+FORM_AUTO = -1         # ARL_FORM_AUTO: arl_net_set_form's value for "the library's rule"
+# DeviceNet.set_forms / form names -> ARL_FORM_* ids
+FORMS = {"conv_epw": 0, "fc_big": 1, "lstm_xred": 2, "conv_bwd_ws": 3}
 RESIZE_SCALAR = 0
 RESIZE_SIMD = 1
 RESIZE_CROP = 2      # flag, combine with SCALAR / SIMD: ale.py crop_or_scale='crop'
@@ -226,6 +231,29 @@ RESIZE_CROP = 2      # flag, combine with SCALAR / SIMD: ale.py crop_or_scale='c
 
 class ArlError(RuntimeError):
     pass
+
+
+def env_defaults() -> dict:
+    """Defaults of DeviceNet's kernel forms and A3C's window options from the
+    process environment, read when a DeviceNet or an A3C is constructed (not at
+    import); explicit constructor arguments and DeviceNet.set_forms win.
+
+    A benchmarking convenience of this Python mirror only: bench.py models and
+    labels its stages from the first four names and scripts/env_ab.sh drives it
+    by them, so the package follows the same names.  The C library never reads
+    the environment: there the forms are arl_net_set_form's per-net state.
+    Forms: a concrete value, or None (auto) when unset or not one of the
+    form's two values; window options: on unless set to "0"."""
+    env = os.environ.get
+
+    def form(name, values):
+        v = env(name, "")[:1]
+        return int(v) if v in values else None
+
+    return {"conv_epw": form("ARL_CONV_EPW", ("1", "2")), "fc_big": form("ARL_FC_BIG", ("0", "1")),
+            "lstm_xred": form("ARL_LSTM_XRED", ("0", "1")), "conv_bwd_ws": form("ARL_CB_WS", ("0", "1")),
+            "window_c": env("ARL_WINDOW_C", "1") != "0", "fuse_returns": env("ARL_FUSE_RETURNS", "1") != "0",
+            "overlap_allreduce": env("ARL_OVERLAP_ALLREDUCE", "1") != "0"}
 
 
 def check(rc: int, what: str = "") -> None:

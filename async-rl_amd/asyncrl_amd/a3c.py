@@ -45,7 +45,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import (ACT_AFTER_CONV, ACT_CONV_ONLY, ARCH_FF, ARCH_FF_NATURE, ARCH_LSTM, ARCH_RGB, ARCH_STACK,
-                   ARCH_STATES, LEARN_CONV, RESIZE_SCALAR)
+                   ARCH_STATES, LEARN_CONV, RESIZE_SCALAR, env_defaults)
 from .dqn_phi import dqn_phi as _device_dqn_phi
 from .distributed import (allreduce_grads, dist_initialized, gather_episode_stats, gather_window_stats,
                           merge_episode_stats, merge_window_stats, world_info)
@@ -53,16 +53,6 @@ from .net import DeviceNet, episode_stats_dict, init_like_torch, ppo_epoch_stats
 from . import serializers
 from .policy_output import SoftmaxPolicyOutput
 
-# > 1 rank: split the gradient all-reduce around the conv backward (ARL_OVERLAP_ALLREDUCE=0: one call,
-# the A arm of the 2-rank rehearsal)
-OVERLAP_ALLREDUCE = os.environ.get("ARL_OVERLAP_ALLREDUCE", "1") != "0"
-# a single-chain window without collectives as one C call (arl_run_window: the same launches without a
-# host round trip per step); ARL_WINDOW_C=0 issues them step by step from Python (the A arm)
-WINDOW_C = os.environ.get("ARL_WINDOW_C", "1") != "0"
-# the step-by-step FF window runs the learner's returns inside the bootstrap policy launch, as the C
-# window does; ARL_FUSE_RETURNS=0 keeps the separate returns launch (the bitwise arm of
-# test_conv_fwd_two_envs_identical)
-FUSE_RETURNS = os.environ.get("ARL_FUSE_RETURNS", "1") != "0"
 
 def _is_dqn_phi(phi) -> bool:
     """phi IS dqn_phi (dqn_phi.py:4-17): this package's function object, or the
@@ -212,8 +202,19 @@ class A3C:
                  v_loss_coef: float = 0.5, keep_loss_scale_same: bool = False, resize_mode: int = RESIZE_SCALAR,
                  process_group=None, batch_loss: str = "sum", collectives: bool | None = None,
                  gae_lambda: float = 1.0, ppo_epochs: int = 1, ppo_clip: float = 0.2, ppo_norm_adv: bool = False,
-                 ppo_vclip: float | None = None):
-        """ppo_norm_adv / ppo_vclip: options of the PPO epochs, off by default
+                 ppo_vclip: float | None = None, window_c: bool | None = None, fuse_returns: bool | None = None,
+                 overlap_allreduce: bool | None = None):
+        """window_c / fuse_returns / overlap_allreduce: how a window is issued,
+        all on by default (None: _lib.env_defaults) and bit-identical to off;
+        kept as attributes of the same names, read by every run_window.
+        window_c: a single-chain window without collectives runs as one C
+        call (arl_run_window: the same launches without a host round trip per
+        step); off issues them step by step from Python.  fuse_returns: the
+        step-by-step FF window runs the learner's returns inside the bootstrap
+        policy launch, as the C window does; off keeps the separate returns
+        launch.  overlap_allreduce: with > 1 rank, split the gradient
+        all-reduce around the conv backward; off makes it one call.
+        ppo_norm_adv / ppo_vclip: options of the PPO epochs, off by default
         (DeviceNet.set_ppo_options): normalise each window's advantages over
         its live samples; clip the value loss within ppo_vclip of the rollout's
         values.  Either also keeps a device-side record per epoch
@@ -297,6 +298,11 @@ class A3C:
             self.net.set_ppo_options(self.ppo_norm_adv, self.ppo_vclip)
         # no all-reduce between learn and update: the clip norm comes from the learner's conv reduce
         self.net.set_norm_fold(not self.collectives)
+        defaults = env_defaults()
+        self.window_c = defaults["window_c"] if window_c is None else bool(window_c)
+        self.fuse_returns = defaults["fuse_returns"] if fuse_returns is None else bool(fuse_returns)
+        self.overlap_allreduce = (defaults["overlap_allreduce"] if overlap_allreduce is None
+                                  else bool(overlap_allreduce))
         self.t = 0          # env-steps taken (per env)
         self.t_start = 0    # a3c.py:56,152 (reference-contract act)
         self._episode_start = True
@@ -353,7 +359,7 @@ class A3C:
         heads section (all but ~12k of the parameters) starts as soon as the
         FC reduce is done and runs on the collective stream while the conv
         backward computes; only the conv section waits for it."""
-        return self.collectives and OVERLAP_ALLREDUCE and self.net.arch != ARCH_FF_NATURE
+        return self.collectives and self.overlap_allreduce and self.net.arch != ARCH_FF_NATURE
 
     def _learn(self, stream=None):
         """The gradient part of the window; with the overlapped all-reduce it
@@ -563,7 +569,7 @@ class A3C:
         direct = net.env is not None and net.env_direct
         if not direct and pair_pool is None:
             raise ValueError("run_window: the pools may be None only with a direct env (set_env(env, direct=True))")
-        if (WINDOW_C and not ppo and len(groups) == 1 and not split_update and not self.collectives
+        if (self.window_c and not ppo and len(groups) == 1 and not split_update and not self.collectives
                 and net.arch == net.base_arch and net.base_arch in (ARCH_FF, ARCH_LSTM)):
             # one C call: T x (observe, act), bootstrap, learn, clip + RMSProp, advance (arl_run_window)
             net.run_window(pair_pool, reward_pool, done_pool, pool_len, first, self.resize_mode, self.gamma, self.beta,
@@ -575,7 +581,7 @@ class A3C:
             net.env_reset_observe(self.resize_mode, stream=stream)
         if len(groups) == 1:
             # FF: the learner's returns ride on the bootstrap policy launch (as arl_run_window does)
-            fuse = FUSE_RETURNS and not ppo and net.base_arch == ARCH_FF and net.arch != ARCH_FF_NATURE
+            fuse = self.fuse_returns and not ppo and net.base_arch == ARCH_FF and net.arch != ARCH_FF_NATURE
             if fuse:
                 net.set_returns_fusion(True, self.gamma, self.beta, self._vcoef, self.clip_reward)
             try:

@@ -17,9 +17,10 @@ import numpy as np
 import torch
 
 from ._lib import (ARCH_FF, ARCH_FF_NATURE, ARCH_LSTM, ARCH_RGB, ARCH_STACK, ARCH_STATES, CTL_ADAM_T, ENV_CATCH,
-                   ENV_GROUP_ALIGN, EPISODE_LOG, EPISODE_STAT_FIELDS, FWD_KEEP_STATE, POOL_DONES, POOL_FRAMES, POOL_REWARDS,
-                   PPO_AUX_DOUBLES, PPO_AUX_HEAD, PPO_LOG, PPO_STAT_FIELDS, PPO_STAT_NAMES, RESIZE_SCALAR, STAGE_HOST, STAGE_NAMES,
-                   WINDOW_LOG, WINDOW_STAT_FIELDS, WINDOW_STAT_NAMES, check, lib, ptr, stream_handle)
+                   ENV_GROUP_ALIGN, EPISODE_LOG, EPISODE_STAT_FIELDS, FORM_AUTO, FORMS, FWD_KEEP_STATE, POOL_DONES,
+                   POOL_FRAMES, POOL_REWARDS, PPO_AUX_DOUBLES, PPO_AUX_HEAD, PPO_LOG, PPO_STAT_FIELDS, PPO_STAT_NAMES,
+                   RESIZE_SCALAR, STAGE_HOST, STAGE_NAMES, WINDOW_LOG, WINDOW_STAT_FIELDS, WINDOW_STAT_NAMES, check,
+                   env_defaults, lib, ptr, stream_handle)
 
 
 def param_shapes(arch: int, n_actions: int):
@@ -164,6 +165,7 @@ class DeviceNet:
         check(lib.arl_net_create(ctypes.byref(h), arch, n_actions, n_envs, t_max, env_offset, seed),
               "arl_net_create")
         self._h = h
+        self.set_forms(**{k: v for k, v in env_defaults().items() if k in FORMS})
         P = lib.arl_net_param_floats(h)
         self.param_floats = P
         self._params = torch.zeros(P, dtype=torch.float32, device=self.device)
@@ -331,6 +333,26 @@ class DeviceNet:
         """Fold the clip norm into learn()'s conv reduce (arl_net_set_norm_fold):
         only when the gradient is not all-reduced between learn and update."""
         check(lib.arl_net_set_norm_fold(self._h, int(on)), "arl_net_set_norm_fold")
+
+    def set_forms(self, conv_epw=None, fc_big=None, lstm_xred=None, conv_bwd_ws=None):
+        """Choose between the bit-identical kernel forms of this net's launches
+        (arl_net_set_form): None leaves a form alone, "auto" restores the
+        library's rule, anything else is the concrete value (conv_epw 1 / 2,
+        the others 0 / 1).  Read when a launch is issued."""
+        for name, v in (("conv_epw", conv_epw), ("fc_big", fc_big), ("lstm_xred", lstm_xred),
+                        ("conv_bwd_ws", conv_bwd_ws)):
+            if v is not None:
+                check(lib.arl_net_set_form(self._h, FORMS[name], FORM_AUTO if v == "auto" else int(v)),
+                      "arl_net_set_form")
+
+    def form(self, name: str, launch_envs: int | None = None) -> int:
+        """The concrete form a launch over launch_envs envs (default: all of
+        the net's) would run now (arl_net_form): conv_epw 1 / 2, the others
+        0 / 1."""
+        v = ctypes.c_int()
+        check(lib.arl_net_form(self._h, FORMS[name], self.n_envs if launch_envs is None else launch_envs,
+                               ctypes.byref(v)), "arl_net_form")
+        return v.value
 
     def set_returns_fusion(self, on: bool, gamma: float = 0.99, beta: float = 0.01, v_loss_coef: float = 0.5,
                            clip_reward: bool = True):

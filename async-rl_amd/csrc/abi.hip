@@ -401,6 +401,43 @@ int arl_net_set_norm_fold(arl_net* h, int on) {
   return ARL_OK;
 }
 
+// the net's field of an ARL_FORM_* id (null: unknown) and its smallest concrete value (the other is lo + 1)
+static int* form_field(arl::Forms& f, int form, int* lo, const char** name) {
+  switch (form) {
+    case ARL_FORM_CONV_EPW: *lo = 1; *name = "ARL_FORM_CONV_EPW"; return &f.conv_epw;
+    case ARL_FORM_FC_BIG: *lo = 0; *name = "ARL_FORM_FC_BIG"; return &f.fc_big;
+    case ARL_FORM_LSTM_XRED: *lo = 0; *name = "ARL_FORM_LSTM_XRED"; return &f.lstm_xred;
+    case ARL_FORM_CONV_BWD_WS: *lo = 0; *name = "ARL_FORM_CONV_BWD_WS"; return &f.conv_bwd_ws;
+  }
+  return nullptr;
+}
+
+int arl_net_set_form(arl_net* h, int form, int value) {
+  if (!h) return fail(ARL_EINVAL, "null net");
+  int lo = 0;
+  const char* name = nullptr;
+  int* field = form_field(h->net.forms, form, &lo, &name);
+  if (!field) return fail(ARL_EINVAL, "net_set_form: unknown form " + std::to_string(form));
+  if (value != ARL_FORM_AUTO && value != lo && value != lo + 1)
+    return fail(ARL_EINVAL, std::string("net_set_form: ") + name + " takes ARL_FORM_AUTO, " + std::to_string(lo) +
+                                " or " + std::to_string(lo + 1) + ", not " + std::to_string(value));
+  *field = value;
+  return ARL_OK;
+}
+
+int arl_net_form(const arl_net* h, int form, int launch_envs, int* value) {
+  if (!h || !value) return fail(ARL_EINVAL, "net_form: null net / value");
+  if (launch_envs < 1) return fail(ARL_EINVAL, "net_form: launch_envs < 1");
+  const arl::Forms& f = h->net.forms;
+  switch (form) {
+    case ARL_FORM_CONV_EPW: *value = arl::conv_fwd_epw(f, h->net.N); return ARL_OK;
+    case ARL_FORM_FC_BIG: *value = arl::fc_fwd_big(f, launch_envs); return ARL_OK;
+    case ARL_FORM_LSTM_XRED: *value = arl::lstm_xred(f, launch_envs); return ARL_OK;
+    case ARL_FORM_CONV_BWD_WS: *value = arl::conv_bwd_ws(f); return ARL_OK;
+  }
+  return fail(ARL_EINVAL, "net_form: unknown form " + std::to_string(form));
+}
+
 int arl_net_set_returns_fusion(arl_net* h, int on, double gamma, double beta, double v_loss_coef, int clip_reward) {
   if (!h) return fail(ARL_EINVAL, "null net");
   arl::Net& n = h->net;

@@ -286,8 +286,37 @@ struct Stamps {
   int64_t calls = 0;          //   period, t = w mod period
 };
 
+// Kernel forms of a net (arl_net_set_form): ARL_FORM_AUTO or a concrete value each.  The resolvers below are the
+// only place a form is decided: the launches (conv_fwd.hip, fc.hip, net.hip, conv_bwd.hip) and arl_net_form call
+// them at issue time.  All forms of a launch are bit-identical (tests/test_gpu_parity.py).
+struct Forms {
+  int conv_epw = ARL_FORM_AUTO, fc_big = ARL_FORM_AUTO, lstm_xred = ARL_FORM_AUTO, conv_bwd_ws = ARL_FORM_AUTO;
+};
+// conv forward: two envs a workgroup (16 waves sharing the weight planes) in nets of >= 512 envs, whether the
+// launch covers all of them or one env group's range (C4 0.513 -> 0.503 ms, C3 1.227 -> 1.212 ms at two groups,
+// profiles/r03/r3k)
+inline int conv_fwd_epw(const Forms& f, int net_envs) {
+  return f.conv_epw != ARL_FORM_AUTO ? f.conv_epw : (net_envs >= 512 ? 2 : 1);
+}
+// FC forward: launches over >= 512 envs on the 64-row tiles (C4 0.503 -> 0.497 ms at one env group, C3 1.215 ->
+// 1.162 ms; at 256-env launches, 128 workgroups of them lose: profiles/r03/r3l)
+inline bool fc_fwd_big(const Forms& f, int launch_envs) {
+  return f.fc_big != ARL_FORM_AUTO ? f.fc_big == 1 : launch_envs >= 512;
+}
+// Where the LSTM step's FC split-K partials are reduced: in the gate kernel's staging (XRED) for launches under
+// 512 envs, by the FC's last-arriver ticket for 512 and more (fc_fwd_kernel's tail; the gate kernel then stages
+// hfc: every one of its 16 column-tile workgroups of a row block otherwise re-reads the block's 8 partial slabs
+// -- C3 1.185 -> 1.160 ms, profiles/r03/r3aa)
+inline bool lstm_xred(const Forms& f, int launch_envs) {
+  return f.lstm_xred != ARL_FORM_AUTO ? f.lstm_xred == 1 : launch_envs < 512;
+}
+// conv backward: the wave-specialised kernel; 0 = the 512-thread kernel it is bit-identical to (conv_bwd 106.7 ->
+// 89.1 us in the C4 window, profiles/r06/ws)
+inline bool conv_bwd_ws(const Forms& f) { return f.conv_bwd_ws != 0; }
+
 struct Net {
   int arch, A, N, T, R;
+  Forms forms;                // arl_net_set_form
   FastDiv dR, dN;             // R and N as device-side divisors (net_init)
   Stamps* stamps = nullptr;   // null / off: stamp() is a no-op
   bool rgb = false;        // ARCH_RGB: 3 planes per obs step in the ring, conv1 W (16, 3, 8, 8)
@@ -472,7 +501,8 @@ hipError_t launch_heads_bwd(const float* dl, const float* dv, const float* Wpi, 
 hipError_t launch_conv_fwd(const uint8_t* frames, const uint8_t* nvalid, const int64_t* ctl, int n, const FastDiv& R,
                            int t,
                            const float* W1, const float* b1, const float* W2, const float* b2, float* a1, float* a2,
-                           hipStream_t s, int layout = FRAMES_RING, int e0 = 0, int ne = -1, uint32_t* a2m = nullptr);
+                           hipStream_t s, const Forms& forms, int layout = FRAMES_RING, int e0 = 0, int ne = -1,
+                           uint32_t* a2m = nullptr);
 // the gradient's squared norm folded into the conv slab reduce (parts == null: not folded)
 struct NormFold {
   double* parts;            // NORM_SCRATCH f64: conv_norm_parts(rest_blocks) partials
@@ -484,8 +514,8 @@ int conv_norm_parts(int rest_blocks);
 hipError_t launch_conv_bwd(const uint8_t* frames, const uint8_t* nvalid, const int64_t* ctl, const FastDiv& n,
                            const FastDiv& R, int S,
                            const float* a1, const float* da2, const float* W2, float* slab, float* gW2, float* gb2,
-                           float* gW1, float* gb1, hipStream_t s, bool reduce = true, int layout = FRAMES_RING,
-                           const NormFold& nf = NormFold{});
+                           float* gW1, float* gb1, hipStream_t s, const Forms& forms, bool reduce = true,
+                           int layout = FRAMES_RING, const NormFold& nf = NormFold{});
 int64_t conv_bwd_slab_floats(int S);
 int conv_bwd_blocks(int S);       // workgroups (= slab slices) of launch_conv_bwd
 // the slab reduce launch_conv_bwd(reduce = true) ends with, alone
@@ -547,11 +577,11 @@ __device__ inline void fc_planes_store(uint16_t* planes, int e, float4 w) {
 }
 hipError_t launch_fc_planes(const float* W, uint16_t* planes, hipStream_t s);
 int fc_fwd_tiles(int n);      // tickets needed for n envs
-bool fc_fwd_big(int n);       // launches over n envs run fc_fwd_big_kernel's 64-row tiles
 // Wp: the FC weight's split planes (FC_PLANE_LD above); tickets == null: split-K partials only (the
-// consumer reduces them); else the last-arriver reduce + bias + relu -> hfc in the same launch
+// consumer reduces them); else the last-arriver reduce + bias + relu -> hfc in the same launch; 64- or 32-row
+// tiles by fc_fwd_big(forms, n)
 hipError_t launch_fc_fwd(const float* a2, int n, const uint16_t* Wp, const float* b, float* slab, int* tickets,
-                         float* hfc, hipStream_t s);
+                         float* hfc, hipStream_t s, const Forms& forms);
 // FC backward (fc_bwd.hip): dW / db straight into the gradient, da2 = (dfc W) * (a2 > 0)
 // weight gradients of the policy / value heads (a3c.py:126-130 through
 // policy.py / v_function.py Linear layers): rows a < A from dlogits, row A

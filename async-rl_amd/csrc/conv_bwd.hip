@@ -13,7 +13,7 @@
 // (152 KB).  Workgroup b handles samples b, b + G, ...  Two forms, bit-identical:
 // * conv_bwd_ws_kernel (the default, below): 1,024 threads; waves 0-7 run (2)
 //   and (3), waves 8-15 run (1) and the commits, two barriers a sample;
-// * conv_bwd_kernel (ARL_CB_WS=0, the test arm): 512 threads (8 waves, 2 per
+// * conv_bwd_kernel (ARL_FORM_CONV_BWD_WS 0, the test arm): 512 threads (8 waves, 2 per
 //   SIMD), a sample in four barrier-separated phases: commit, (1) + mask, (2),
 //   (3); the next sample's a1 / da2 / screens are loaded into registers
 //   (unconditional loads from clamped addresses: no load waits for another)
@@ -515,7 +515,7 @@ conv_bwd_kernel(ConvBwdArgs a) {
 // W2 is staged once through LDS by coalesced loads (the fragment-order global loads touched one 64-byte
 // segment a lane: 64 L2 requests an instruction, ~20k cycles of prologue).  Every accumulator sees the
 // same products in the same order as conv_bwd_kernel (per-wave tiles unchanged), so the slabs are
-// bit-identical to it (ARL_CB_WS=0 runs conv_bwd_kernel: the bitwise test arm).
+// bit-identical to it (ARL_FORM_CONV_BWD_WS 0 runs conv_bwd_kernel: the bitwise test arm).
 namespace {
 constexpr int NT2 = 1024;
 constexpr int A1W = 2 * A1C * 4;                 // bytes of one Y wave's two a1 channels (3,840)
@@ -977,16 +977,16 @@ int64_t conv_bwd_slab_floats(int S) { return (int64_t)conv_bwd_blocks(S) * SLAB;
 
 hipError_t launch_conv_bwd(const uint8_t* frames, const uint8_t* nvalid, const int64_t* ctl, const FastDiv& n,
                            const FastDiv& R, int S, const float* a1, const float* da2, const float* W2, float* slab, float* gW2, float* gb2,
-                           float* gW1, float* gb1, hipStream_t s, bool reduce, int layout, const NormFold& nf) {
+                           float* gW1, float* gb1, hipStream_t s, const Forms& forms, bool reduce, int layout,
+                           const NormFold& nf) {
   if (S <= 0) return hipSuccess;
   const int G = conv_bwd_blocks(S);
   const int ni = (int)n.d;
   ConvBwdArgs a{frames, nvalid, ctl, ni, (int)R.d, n, R, a1, da2, W2, S, G, S / G, S % G, G / ni, G % ni, slab, layout};
-  static const char* ws = getenv("ARL_CB_WS");   // "0": the 512-thread kernel (the bitwise test arm)
-  if (ws != nullptr && ws[0] == '0')
-    hipLaunchKernelGGL(conv_bwd_kernel, dim3(G), dim3(NT), 0, s, a);
-  else
+  if (conv_bwd_ws(forms))
     hipLaunchKernelGGL(conv_bwd_ws_kernel, dim3(G), dim3(NT2), 0, s, a);
+  else   // the 512-thread kernel (the bitwise test arm)
+    hipLaunchKernelGGL(conv_bwd_kernel, dim3(G), dim3(NT), 0, s, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !reduce) return e;
   return launch_conv_reduce(slab, S, gW2, gb2, gW1, gb1, s, layout, nf);

@@ -372,17 +372,13 @@ conv_fwd_kernel(ConvFwdArgs a) {
 
 hipError_t launch_conv_fwd(const uint8_t* frames, const uint8_t* nvalid, const int64_t* ctl, int n, const FastDiv& R,
                            int t, const float* W1, const float* b1, const float* W2, const float* b2, float* a1, float* a2,
-                           hipStream_t s, int layout, int e0, int ne, uint32_t* a2m) {
+                           hipStream_t s, const Forms& forms, int layout, int e0, int ne, uint32_t* a2m) {
   if (n <= 0) return hipSuccess;
   if (ne < 0) ne = n;
   if (ne <= 0) return hipSuccess;
   ConvFwdArgs a{frames, nvalid, ctl, n, t, R, W1, b1, W2, b2, a1, a2, layout, e0, e0 + ne, a2m};
-  // two envs a workgroup (16 waves sharing the weight planes) in nets of >= 512 envs, whether the
-  // launch covers all of them or one env group's range (C4 0.513 -> 0.503 ms, C3 1.227 -> 1.212 ms at
-  // two groups, profiles/r03/r3k); ARL_CONV_EPW=1 / 2 forces one form (A/B timing)
-  static const char* epw = getenv("ARL_CONV_EPW");
-  const int k = (epw && (epw[0] == '1' || epw[0] == '2')) ? epw[0] - '0' : (n >= 512 ? 2 : 1);
-  if (k == 2) hipLaunchKernelGGL((conv_fwd_kernel<2>), dim3((ne + 1) / 2), dim3(2 * NT), 0, s, a);
+  // one or two envs a workgroup, by the net's env count n whatever range the launch covers
+  if (conv_fwd_epw(forms, n) == 2) hipLaunchKernelGGL((conv_fwd_kernel<2>), dim3((ne + 1) / 2), dim3(2 * NT), 0, s, a);
   else hipLaunchKernelGGL((conv_fwd_kernel<1>), dim3(ne), dim3(NT), 0, s, a);
   return hipGetLastError();
 }

@@ -31,8 +31,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstdlib>
-
 #include "arl_internal.hpp"
 #include "bf16split.hpp"
 
@@ -246,23 +244,15 @@ __global__ void __launch_bounds__(256) fc_planes_kernel(const float* __restrict_
 
 int fc_fwd_tiles(int n) { return ((n + 31) / 32) * (HID / FBN); }
 
-bool fc_fwd_big(int n) {
-  // launches over >= 512 envs on the 64-row tiles (C4 0.503 -> 0.497 ms at one env group, C3 1.215 -> 1.162
-  // ms; at 256-env launches, 128 workgroups of them lose: profiles/r03/r3l); ARL_FC_BIG=0 / 1 forces one
-  // form (the bitwise arm of test_conv_fwd_two_envs_identical)
-  static const char* big = getenv("ARL_FC_BIG");
-  return (big && (big[0] == '0' || big[0] == '1')) ? big[0] == '1' : n >= 512;
-}
-
 hipError_t launch_fc_planes(const float* W, uint16_t* planes, hipStream_t s) {
   hipLaunchKernelGGL(fc_planes_kernel, dim3((HID * A2 / 4 + 255) / 256), dim3(256), 0, s, W, planes);
   return hipGetLastError();
 }
 
 hipError_t launch_fc_fwd(const float* a2, int n, const uint16_t* Wp, const float* b, float* slab, int* tickets,
-                         float* hfc, hipStream_t s) {
+                         float* hfc, hipStream_t s, const Forms& forms) {
   if (n <= 0) return hipSuccess;
-  if (fc_fwd_big(n)) {   // its 64-row tiles use the first half of the 32-row tiles' tickets
+  if (fc_fwd_big(forms, n)) {   // its 64-row tiles use the first half of the 32-row tiles' tickets
     const int tiles = ((n + 63) / 64) * (HID / FBN);
     hipLaunchKernelGGL(fc_fwd_kernel<64>, dim3((unsigned)(tiles * FSPLIT)), dim3(FcLay<64>::NT), 0, s, a2, n, Wp, b,
                        slab, tickets, hfc);

@@ -19,7 +19,6 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "arl_internal.hpp"
 #include "gemm.hpp"
@@ -49,17 +48,6 @@ struct Conv2A {         // A(m, k) = a1[s][ic][2oy+ky][2ox+kx], m = s*81 + p, k 
     return a1[(int64_t)s * A1 + ic * C1_P + (2 * oy + ky) * 20 + 2 * ox + kx];
   }
 };
-
-// Where the LSTM step's FC split-K partials are reduced: in the gate kernel's staging (XRED) for
-// launches under 512 envs, by the FC's last-arriver ticket for 512 and more (fc_fwd_big_kernel's
-// tail; the gate kernel then stages hfc: every one of its 16 column-tile workgroups of a row block
-// otherwise re-reads the block's 8 partial slabs -- C3 1.185 -> 1.160 ms, profiles/r03/r3aa).
-// ARL_LSTM_XRED=1 / 0 forces one form (the bitwise arm of test_lstm_fc_ticket_big_tiles_identical).
-static const int LSTM_XRED_ENV = [] {
-  const char* e = getenv("ARL_LSTM_XRED");
-  return e == nullptr ? -1 : (e[0] != '0' ? 1 : 0);
-}();
-static bool lstm_xred(int launch_envs) { return LSTM_XRED_ENV >= 0 ? LSTM_XRED_ENV == 1 : launch_envs < 512; }
 
 // ---------------------------------------------------------------- elementwise
 __device__ inline float sigm(float x) { return __fdiv_rn(1.f, __fadd_rn(1.f, expf(-x))); }
@@ -319,7 +307,7 @@ static const uint16_t* fc_planes(const Net& net) { return net.at<uint16_t>(net.w
 // head after conv1 (conv2 -> fc) for n rows, activations at a1/a2/hfc
 static hipError_t fc_forward(const Net& net, int n, const float* a2, float* hfc, hipStream_t s) {
   return launch_fc_fwd(a2, n, fc_planes(net), net.p + net.o_fcb, net.at<float>(net.w_slab), net.at<int>(net.w_tick),
-                       hfc, s);
+                       hfc, s, net.forms);
 }
 
 // policy / value heads of window slot t (rows of env e0, e0 + 1, ..) reading h
@@ -344,7 +332,7 @@ static hipError_t conv_fwd_slot(const Net& net, int t, int e0, int ne, bool bwd_
   return launch_conv_fwd(net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid), net.at<int64_t>(net.w_ctl), n,
                          net.dR, t, P + net.o_c1W, P + net.o_c1b, P + net.o_c2W, P + net.o_c2b,
                          bwd_outputs ? net.at<float>(net.w_a1) + (int64_t)t * n * A1 : nullptr,
-                         net.at<float>(net.w_a2) + (int64_t)t * n * A2, s, net.layout, e0, ne,
+                         net.at<float>(net.w_a2) + (int64_t)t * n * A2, s, net.forms, net.layout, e0, ne,
                          bwd_outputs ? a2_mask(net, t) : nullptr);
 }
 
@@ -354,7 +342,7 @@ static hipError_t conv_fwd_slot(const Net& net, int t, int e0, int ne, bool bwd_
 static hipError_t lstm_gates_step(const Net& net, int t, int e0, int ne, hipStream_t s) {
   const float* P = net.p;
   const int n = net.N;
-  const bool xred = lstm_xred(ne);
+  const bool xred = lstm_xred(net.forms, ne);
   const int64_t r0 = (int64_t)t * n + e0;
   float* hfc = net.at<float>(net.w_hfc) + r0 * HID;
   return launch_lstm_gates(xred ? nullptr : hfc, net.at<float>(net.w_hbuf) + r0 * HID,
@@ -383,7 +371,7 @@ static hipError_t conv_bwd_slabs(const Net& net, hipStream_t s) {
   return launch_conv_bwd(net.at<uint8_t>(net.w_frames), net.at<uint8_t>(net.w_nvalid), net.at<int64_t>(net.w_ctl),
                          net.dN, net.dR, net.T * net.N, net.at<float>(net.w_a1), net.at<float>(net.w_da2),
                          net.p + net.o_c2W, net.at<float>(net.w_slab), net.g + net.o_c2W, net.g + net.o_c2b,
-                         net.g + net.o_c1W, net.g + net.o_c1b, s, /*reduce=*/false, net.layout);
+                         net.g + net.o_c1W, net.g + net.o_c1b, s, net.forms, /*reduce=*/false, net.layout);
 }
 // and that reduce, with the folded clip norm's partials when nf.parts is set
 static hipError_t conv_bwd_reduce(const Net& net, const NormFold& nf, hipStream_t s) {
@@ -463,7 +451,8 @@ hipError_t net_act(Net& net, int t, int mode, hipStream_t s, int e0, int ne) {
   float* fc_slab = net.at<float>(net.w_slab) + (int64_t)FC_SPLIT * e0 * HID;
   const PolicyArgs pa = slot_policy_args(net, t, t < net.T ? mode : 0, e0);
   if (net.arch != ARCH_LSTM) {   // FF: split-K partials, reduce + relu + heads in one policy_fc launch
-    ARL_TRY(launch_fc_fwd(a2 + (int64_t)e0 * A2, ne, fc_planes(net), P + net.o_fcb, fc_slab, nullptr, nullptr, s));
+    ARL_TRY(launch_fc_fwd(a2 + (int64_t)e0 * A2, ne, fc_planes(net), P + net.o_fcb, fc_slab, nullptr, nullptr, s,
+                          net.forms));
     ARL_TRY(stamp(net, STAGE_FC_FWD, s));
     // + the learner's returns (one env group); not while the update runs as PPO epochs (arl_ppo_begin / arl_ppo_learn)
     if (t == net.T && net.fuse_returns && net.ppo_snap == nullptr && e0 == 0 && ne == n) {
@@ -481,9 +470,10 @@ hipError_t net_act(Net& net, int t, int mode, hipStream_t s, int e0, int ne) {
   }
   // LSTM: the FC's split-K partials, reduced + bias + relu either in the gate kernel's staging (XRED) or
   // by the FC's last-arriver ticket (lstm_xred); then the gates with the cell in their epilogue
-  const bool xred = lstm_xred(ne);
+  const bool xred = lstm_xred(net.forms, ne);
   ARL_TRY(launch_fc_fwd(a2 + (int64_t)e0 * A2, ne, fc_planes(net), P + net.o_fcb, fc_slab,
-                        xred ? nullptr : net.at<int>(net.w_tick) + fc_fwd_tiles(e0), xred ? nullptr : hfc, s));
+                        xred ? nullptr : net.at<int>(net.w_tick) + fc_fwd_tiles(e0), xred ? nullptr : hfc, s,
+                        net.forms));
   ARL_TRY(stamp(net, STAGE_FC_FWD, s));
   ARL_TRY(lstm_gates_step(net, t, e0, ne, s));
   ARL_TRY(stamp(net, STAGE_LSTM_GATES, s));
@@ -731,8 +721,9 @@ hipError_t net_stage(Net& net, int stage, int t, hipStream_t s) {
       return conv_fwd_slot(net, t, 0, -1, true, s);
     case STAGE_FC_FWD:   // as in net_act: FF (and the LSTM's XRED gate kernel) reduce the partials downstream
       ARL_TRY(ensure_fc_planes(net, s));
-      if (net.arch != ARCH_LSTM || lstm_xred(n))
-        return launch_fc_fwd(a2 + (int64_t)t * n * A2, n, fc_planes(net), P + net.o_fcb, slab, nullptr, nullptr, s);
+      if (net.arch != ARCH_LSTM || lstm_xred(net.forms, n))
+        return launch_fc_fwd(a2 + (int64_t)t * n * A2, n, fc_planes(net), P + net.o_fcb, slab, nullptr, nullptr, s,
+                             net.forms);
       return fc_forward(net, n, a2 + (int64_t)t * n * A2, hfc + (int64_t)t * n * HID, s);
     case STAGE_POLICY: {
       const int64_t o = (int64_t)t * n;

@@ -24,7 +24,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstdlib>
 #include <type_traits>
 
 #include "arl_internal.hpp"

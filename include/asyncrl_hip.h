@@ -454,6 +454,39 @@ int arl_net_set_ppo_options(arl_net* net, int norm_adv, double vclip_eps, float*
  * all-reduced across ranks); arl_learn_part never folds.  Default off. */
 int arl_net_set_norm_fold(arl_net* net, int on);
 
+/* Kernel forms.  Four launches have two bit-identical kernels each, and the net
+ * picks between them per launch:
+ *   ARL_FORM_CONV_EPW     envs per conv forward workgroup: 1 or 2.  Auto: 2 in nets
+ *                         of >= 512 envs (the net's count, whatever the launch covers)
+ *   ARL_FORM_FC_BIG       1 = the FC forward's 64-row tiles, 0 = its 32-row tiles.
+ *                         Auto: 1 for launches over >= 512 envs
+ *   ARL_FORM_LSTM_XRED    1 = the LSTM gate kernel reduces the FC's split-K partials
+ *                         in its staging, 0 = the FC's last-arriver ticket does.
+ *                         Auto: 1 for launches over < 512 envs
+ *   ARL_FORM_CONV_BWD_WS  1 = the wave-specialised conv backward, 0 = the 512-thread
+ *                         kernel.  Auto: 1
+ * arl_net_set_form sets one of them to a concrete value or back to ARL_FORM_AUTO
+ * (the default).  It sets host state of the handle only (no bind needed), and is
+ * accepted without effect where the net never runs that kernel (the Nature head;
+ * ARL_FORM_LSTM_XRED on FF nets).  arl_net_form returns in *value the concrete form
+ * a launch over launch_envs envs of this net would run now (ARL_FORM_CONV_EPW
+ * ignores launch_envs), through the rule the launches themselves use.
+ *
+ * A form is read when a launch is issued: a captured graph keeps the forms it was
+ * captured with, and changing a form between windows of a bound net is allowed.
+ * All combinations share one workspace layout (the ticket buffer is sized by the
+ * 32-row tiling and the kernels reset it), so nothing is reallocated.
+ *
+ * ARL_EINVAL: a null net or value pointer, an unknown form, launch_envs < 1, or a
+ * value that is neither ARL_FORM_AUTO nor one of the form's two. */
+#define ARL_FORM_AUTO (-1)
+#define ARL_FORM_CONV_EPW 0
+#define ARL_FORM_FC_BIG 1
+#define ARL_FORM_LSTM_XRED 2
+#define ARL_FORM_CONV_BWD_WS 3
+int arl_net_set_form(arl_net* net, int form, int value);
+int arl_net_form(const arl_net* net, int form, int launch_envs, int* value);
+
 /* The learner's returns + loss gradient + heads backward (arl_learn_part
  * ARL_LEARN_RETURNS, a3c.py:82-130) folded into the bootstrap step's policy
  * launch: with on != 0, the next arl_act / arl_act_mode at t == t_max over all

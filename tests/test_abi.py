@@ -228,3 +228,81 @@ def test_param_generation_without_device():
         assert b"arl_net_prepare" in lib.arl_last_error()
     finally:
         lib.arl_net_destroy(h)
+
+
+def test_kernel_forms_without_device(monkeypatch):
+    """arl_net_set_form / arl_net_form on unbound handles (host state only): the auto forms are the
+    512-env rules, every concrete value round-trips, ARL_FORM_AUTO restores the rule, anything else is
+    ARL_EINVAL with a message; and bench.py's byte / kernel-name model follows the same rule."""
+    import sys
+    from asyncrl_amd._lib import ARCH_FF, ARCH_LSTM, FORM_AUTO, FORMS, lib
+    EPW, BIG, XRED, WS = (FORMS[k] for k in ("conv_epw", "fc_big", "lstm_xred", "conv_bwd_ws"))
+    LAUNCHES = (1, 511, 512, 1024)
+    EINVAL = 1
+
+    def form(h, f, launch):
+        v = ctypes.c_int(-7)
+        assert lib.arl_net_form(h, f, launch, ctypes.byref(v)) == 0
+        return v.value
+
+    def rule(n_envs, f, launch):   # today's thresholds
+        return {EPW: 2 if n_envs >= 512 else 1, BIG: int(launch >= 512), XRED: int(launch < 512), WS: 1}[f]
+
+    nets = [(ARCH_FF, 4, n) for n in (16, 511, 512, 1024)] + [(ARCH_LSTM, 6, n) for n in (72, 512)]
+    sys.path.insert(0, ROOT)
+    import bench
+    for name in ("ARL_CONV_EPW", "ARL_FC_BIG", "ARL_LSTM_XRED", "ARL_CB_WS"):
+        monkeypatch.delenv(name, raising=False)
+    for arch, A, n in nets:
+        h = ctypes.c_void_p()
+        assert lib.arl_net_create(ctypes.byref(h), arch, A, n, 5, 0, 0) == 0
+        try:
+            def auto_everywhere():
+                for f in (EPW, BIG, XRED, WS):
+                    for launch in LAUNCHES:
+                        assert form(h, f, launch) == rule(n, f, launch), (arch, n, f, launch)
+            auto_everywhere()
+            for launch in LAUNCHES:                      # the benchmark's model of the same decisions
+                assert bench.conv_epw(n) == form(h, EPW, launch)
+                assert bench.fc_big(launch) == bool(form(h, BIG, launch))
+                assert bench.lstm_xred(launch) == bool(form(h, XRED, launch))
+            for f, values in ((EPW, (1, 2)), (BIG, (0, 1)), (XRED, (0, 1)), (WS, (0, 1))):
+                for v in values:
+                    assert lib.arl_net_set_form(h, f, v) == 0
+                    assert [form(h, f, launch) for launch in LAUNCHES] == [v] * len(LAUNCHES)
+                    for g in (EPW, BIG, XRED, WS):       # the other forms stay on the rule
+                        assert g == f or all(form(h, g, launch) == rule(n, g, launch) for launch in LAUNCHES)
+                for bad in (values[1] + 1, 7, -2) + ((0,) if f == EPW else ()):
+                    assert lib.arl_net_set_form(h, f, bad) == EINVAL and lib.arl_last_error(), (f, bad)
+                    assert form(h, f, 512) == values[1]   # a refused value changes nothing
+                assert lib.arl_net_set_form(h, f, FORM_AUTO) == 0
+                auto_everywhere()
+            for bad_form in (-1, 4, 99):
+                assert lib.arl_net_set_form(h, bad_form, FORM_AUTO) == EINVAL and lib.arl_last_error()
+                v = ctypes.c_int()
+                assert lib.arl_net_form(h, bad_form, 1, ctypes.byref(v)) == EINVAL and lib.arl_last_error()
+            v = ctypes.c_int()
+            assert lib.arl_net_form(h, BIG, 0, ctypes.byref(v)) == EINVAL and lib.arl_last_error()
+            assert lib.arl_net_form(h, BIG, 1, None) == EINVAL and lib.arl_last_error()
+            assert lib.arl_net_set_form(h, EPW, 0) == EINVAL       # the message names the form and its values
+            assert all(s in lib.arl_last_error() for s in (b"ARL_FORM_CONV_EPW", b"ARL_FORM_AUTO", b"1 or 2"))
+        finally:
+            lib.arl_net_destroy(h)
+
+
+def test_env_defaults_are_read_at_construction(monkeypatch):
+    """The seven ARL_* names are defaults of the Python mirror only (_lib.env_defaults), read per call."""
+    from asyncrl_amd._lib import env_defaults
+    names = ("ARL_CONV_EPW", "ARL_FC_BIG", "ARL_LSTM_XRED", "ARL_CB_WS", "ARL_WINDOW_C", "ARL_FUSE_RETURNS",
+             "ARL_OVERLAP_ALLREDUCE")
+    for name in names:
+        monkeypatch.delenv(name, raising=False)
+    assert env_defaults() == dict(conv_epw=None, fc_big=None, lstm_xred=None, conv_bwd_ws=None, window_c=True,
+                                  fuse_returns=True, overlap_allreduce=True)
+    for name, v in zip(names, ("2", "1", "0", "0", "0", "0", "0")):
+        monkeypatch.setenv(name, v)
+    assert env_defaults() == dict(conv_epw=2, fc_big=1, lstm_xred=0, conv_bwd_ws=0, window_c=False,
+                                  fuse_returns=False, overlap_allreduce=False)
+    monkeypatch.setenv("ARL_CONV_EPW", "3")
+    monkeypatch.setenv("ARL_FC_BIG", "yes")
+    assert env_defaults()["conv_epw"] is None and env_defaults()["fc_big"] is None

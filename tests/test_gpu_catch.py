@@ -74,18 +74,17 @@ def test_closed_loop_window_one_call(gpu):
 
 
 @pytest.mark.parametrize("kind,A,n,P,kw", [("ff", 4, 64, 7, dict(env_groups=2)), ("lstm", 6, 33, 7, {})])
-def test_closed_loop_python_chains(gpu, monkeypatch, kind, A, n, P, kw):
+def test_closed_loop_python_chains(gpu, kind, A, n, P, kw):
     """The Python chains (_chain_steps): two env groups on two streams at 64 envs, and an LSTM net
     (A = 6) on the single chain; the parameters after 6 windows equal the one-call path's bit for bit."""
-    import asyncrl_amd.a3c as a3c
     T = 5
     one, one_net, _, one_pools = make_agent(kind, A, n, T, P, gpu)
     check = LoopCheck(n)
     run_windows(one, one_pools, P, 6, check if kind == "lstm" else None)
     if kind == "lstm":
         check.end(one_net, one_net.env, one_pools, P)
-    monkeypatch.setattr(a3c, "WINDOW_C", False)               # (the single chain from Python)
     agent, net, catch, pools = make_agent(kind, A, n, T, P, gpu)
+    agent.window_c = False                                    # (the single chain from Python)
     init = net.params.clone()
     check = LoopCheck(n)
     run_windows(agent, pools, P, 6, check, **kw)

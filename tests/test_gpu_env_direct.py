@@ -71,7 +71,7 @@ def test_step_screen_equals_step_then_current_screen(gpu, game, mode):
 
 
 # ---------------------------------------------------------------- 2 - 4. the closed loop
-def build(game, kind, n, T, gpu, direct, seed=5, P=3, ppo=1, window_stats=False):
+def build(game, kind, n, T, gpu, direct, seed=5, P=3, ppo=1, window_stats=False, window_c=None):
     """An agent at the reference's hyperparameters with `game` attached: over pools of P entries, reset -- or direct,
     with no pools at all.  The window that follows runs with first=True."""
     from asyncrl_amd import A3C, A3CFF, A3CFFNature, A3CLSTM, GradientClipping, RMSpropAsync
@@ -79,7 +79,7 @@ def build(game, kind, n, T, gpu, direct, seed=5, P=3, ppo=1, window_stats=False)
     model = cls(4, n_envs=n, t_max=T, seed=seed, init_seed=1, device=gpu, frames="pairs")
     opt = RMSpropAsync(lr=7e-4, eps=1e-1, alpha=0.99).setup(model)
     opt.add_hook(GradientClipping(40))
-    agent = A3C(model, opt, T, 0.99, ppo_epochs=ppo)
+    agent = A3C(model, opt, T, 0.99, ppo_epochs=ppo, window_c=window_c)
     net = model.net
     net.set_episode_stats(True)
     if window_stats:
@@ -115,7 +115,7 @@ def assert_same(pairs_side, direct_side, kind, where):
 def lockstep(game, kind, n, T, windows, gpu, **run_kw):
     """`windows` windows of a pairs agent and a direct agent side by side, compared after each; returns both
     (agent, net, env) and the dones of the whole run."""
-    build_kw = {k: run_kw.pop(k) for k in ("ppo", "window_stats") if k in run_kw}
+    build_kw = {k: run_kw.pop(k) for k in ("ppo", "window_stats", "window_c") if k in run_kw}
     pa, pnet, penv, ppools = build(game, kind, n, T, gpu, False, **build_kw)
     da, dnet, denv, dpools = build(game, kind, n, T, gpu, True, **build_kw)
     assert dpools[:3] == (None, None, None) and dnet.env_direct and not pnet.env_direct
@@ -132,13 +132,12 @@ def lockstep(game, kind, n, T, windows, gpu, **run_kw):
 
 @pytest.mark.parametrize("path", ["chain", "one_call", "groups"])
 @pytest.mark.parametrize("game", GAMES)
-def test_closed_loop_bitwise(gpu, monkeypatch, game, path):
+def test_closed_loop_bitwise(gpu, game, path):
     """FF, N = 35, t_max = 2, 16 windows (the ring of 6 slots wraps five times; test_env_direct.py checks the
     terminals): the single chain from Python, the one-C-call window (arl_run_window with null pools), and two env
     groups on two streams (ranges (0, 32) and (32, 3))."""
-    import asyncrl_amd.a3c as a3c
-    monkeypatch.setattr(a3c, "WINDOW_C", path == "one_call")
     kw = dict(env_groups=2) if path == "groups" else {}
+    kw["window_c"] = path == "one_call"
     (_, pnet, _), (_, dnet, _), dones = lockstep(game, "ff", CLOSED_N, CLOSED_T, CLOSED_WINDOWS, gpu, **kw)
     if path == "groups":
         assert dnet.env_groups(2) == [(0, 32), (32, 3)]

@@ -6,9 +6,6 @@ Tolerances: 1e-5 norm-scaled (and componentwise for the gradients), as test_gpu_
 test_gpu_configs hold the same quantities to on the n-step path; everything the feature must leave
 alone (dv, v_loss, the lambda = 1 path, fused against unfused, a graph against eager) bit for bit."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -202,21 +199,44 @@ def test_lstm_window_matches_the_replay(gpu):
     agent.finish_window()
 
 
-def test_fused_bootstrap_launch_equals_the_separate_one(gpu, tmp_path):
-    """The window as one C call (the returns in policy_fc_returns_kernel) in this process against the window issued
-    step by step with the separate returns_heads_kernel launch in a child, four shapes (one at T = 33, the 32-row forms'
-    second pass), lambda 0.95, bit for bit."""
-    import gae_worker
-    from asyncrl_amd import a3c
-    assert a3c.WINDOW_C and a3c.FUSE_RETURNS
-    here = os.path.dirname(os.path.abspath(__file__))
-    f0, f1 = str(tmp_path / "fused.npz"), str(tmp_path / "separate.npz")
-    gae_worker.main(f0, 0.95)
-    subprocess.run([sys.executable, os.path.join(here, "gae_worker.py"), f1, "0.95"],
-                   env=dict(os.environ, ARL_WINDOW_C="0", ARL_FUSE_RETURNS="0"), check=True, timeout=240)
-    a, b = np.load(f0), np.load(f1)
-    assert sorted(a.files) == sorted(b.files) and len(a.files) == len(gae_worker.CASES) * 7 == 4 * 7
-    for k in a.files:
+FUSED_CASES = [(33, 5, 4), (33, 9, 6), (5, 5, 18), (5, 33, 6)]   # (n, T, A); T = 33: a second pass over rows
+FUSED_KEYS = ("dlogits", "dv", "loss", "dfc", "v")
+
+
+def fused_case_windows(gpu, lam, pools, **window):
+    """One FF window per case of FUSED_CASES with A3C(gae_lambda=lam, **window) through A3C.run_window (one env
+    group); the agents' (window_c, fuse_returns) and what the learner's first kernel and the learner left."""
+    from asyncrl_amd import A3C, A3CFF, GradientClipping, RMSpropAsync
+    res, issued = {}, set()
+    for (n, T, A), pool in zip(FUSED_CASES, pools):
+        m = A3CFF(A, n_envs=n, t_max=T, seed=9, init_seed=10, frames="pairs", device=gpu)
+        o = RMSpropAsync(lr=7e-4, eps=0.1, alpha=0.99).setup(m)
+        o.add_hook(GradientClipping(40))
+        ag = A3C(m, o, T, 0.99, gae_lambda=lam, **window)
+        issued.add((ag.window_c, ag.fuse_returns))
+        ag.run_window(*pool, T + 1, first=True, env_groups=1)
+        torch.cuda.synchronize()
+        net = ag.net
+        pre = f"{n}_{T}_{A}_"
+        for k in FUSED_KEYS:
+            res[pre + k] = net.buffer(k, torch.float32).cpu().numpy()
+        res[pre + "grads"] = net.grads.detach().cpu().numpy()
+        res[pre + "params"] = net.params.detach().cpu().numpy()
+    return res, issued
+
+
+def test_fused_bootstrap_launch_equals_the_separate_one(gpu):
+    """The window as one C call (the returns in policy_fc_returns_kernel), A3C's default, against the window issued
+    step by step with the separate returns_heads_kernel launch (window_c and fuse_returns off), four shapes (one at
+    T = 33, the 32-row forms' second pass), lambda 0.95, bit for bit."""
+    pools = [tuple(dev(x, gpu) for x in make_pools(np.random.default_rng(n * 100 + T), T + 1, n, "uniform", p_done=0.2))
+             for n, T, _ in FUSED_CASES]
+    a, issued = fused_case_windows(gpu, 0.95, pools)
+    assert issued == {(True, True)}
+    b, issued = fused_case_windows(gpu, 0.95, pools, window_c=False, fuse_returns=False)
+    assert issued == {(False, False)}
+    assert sorted(a) == sorted(b) and len(a) == len(FUSED_CASES) * 7 == 4 * 7
+    for k in a:
         assert bits_equal(a[k], b[k]), k
         assert np.isfinite(a[k]).all() and (np.abs(a[k]).max() > 0 or k.endswith("dfc")), k
 

@@ -4,8 +4,6 @@ reference-generated golden fixtures.
 Tolerances (stated per test): integer / byte / index work is bit-exact;
 fp32 contractions |gpu - oracle| <= 1e-5 * max(|oracle|, ||oracle||_inf)
 (norm-scaled); the RMSProp kernel is bit-exact vs the reference."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -717,26 +715,66 @@ def test_learn_parts_identical(gpu, arch):
     assert torch.equal(got[0], got[1]) and torch.equal(got[0], got[2])
 
 
-def test_lstm_fc_reduce_forms_identical(gpu, tmp_path):
+def lstm_form_arm(gpu, N, pools, lstm_xred, fc_big_whole):
+    """One arm of the LSTM form tests: three eager LSTM windows (two env groups, one, a side stream), a
+    graph-captured one and one pi_and_v call at N envs with the lstm_xred form as given ("auto" / 0 / 1); the
+    actions, values, hidden states, gradients and parameters they leave.  Before anything launches, the forms are
+    read back through net.form: lstm_xred as intended at every launch size, the whole-net FC launch on
+    fc_big_whole's tiles."""
+    from asyncrl_amd import A3C, A3CLSTM, GradientClipping, RMSpropAsync
+    T, P = 5, 7
+    dp, dr, dd = pools
+    m = A3CLSTM(6, n_envs=N, t_max=T, seed=5, init_seed=6, frames="pairs", device=gpu)
+    o = RMSpropAsync(lr=7e-4, eps=0.1, alpha=0.99).setup(m)
+    o.add_hook(GradientClipping(40))
+    ag = A3C(m, o, T, 0.99)
+    net = ag.net
+    net.set_forms(conv_epw="auto", fc_big="auto", lstm_xred=lstm_xred, conv_bwd_ws="auto")
+    want = int(N < 512) if lstm_xred == "auto" else lstm_xred      # (no launch here is over more than N envs)
+    assert [net.form("lstm_xred", n) for n in (1, N // 2, N)] == [want] * 3
+    assert net.form("fc_big", N) == fc_big_whole
+    ag.run_window(dp, dr, dd, P, first=True, env_groups=2)
+    ag.run_window(dp, dr, dd, P, env_groups=1)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        ag.run_window(dp, dr, dd, P, stream=s)
+    s.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        ag.run_window(dp, dr, dd, P, stream=s, split_update=True)
+    g.replay()
+    torch.cuda.synchronize()
+    x = torch.rand((N, 4, 84, 84), generator=torch.Generator().manual_seed(3)).to(gpu)
+    pout, v = m.pi_and_v(x, deterministic=True)
+    res = {"actions": net.buffer("actions", torch.int32, (T + 1, N)), "v": net.buffer("v", torch.float32, (T + 1, N)),
+           "hbuf": net.buffer("hbuf", torch.float32), "cbuf": net.buffer("cbuf", torch.float32),
+           "gates": net.buffer("gates", torch.float32), "grads": net.grads, "params": net.params, "ms": net.ms,
+           "eval_v": v, "eval_probs": pout.probs}
+    return {k: r.detach().cpu().numpy() for k, r in res.items()}, want
+
+
+def lstm_form_arms(gpu, N, arms, fc_big_whole):
+    """lstm_form_arm per entry of arms on one set of pools; the arms must differ in the lstm_xred they ran."""
+    pairs, rewards, dones = make_pools(np.random.default_rng(123), 7, N, "uniform", p_done=0.15)
+    pools = dev(pairs, gpu), dev(rewards, gpu), dev(dones, gpu)
+    outs, forms = zip(*(lstm_form_arm(gpu, N, pools, x, fc_big_whole) for x in arms))
+    assert len(set(forms)) == len(arms)
+    return outs
+
+
+def test_lstm_fc_reduce_forms_identical(gpu):
     """LSTM windows (two env groups, eager and graph-captured) with the FC
     forward's split-K partials reduced in the gate kernel's staging (the
     default under 512 envs a launch) and by the FC's last-arriver ticket
-    (ARL_LSTM_XRED=0): the same partials summed in the same order, so hidden /
+    (lstm_xred 0): the same partials summed in the same order, so hidden /
     cell states, gates, actions, values, gradients and parameters match bit
     for bit."""
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    outs = []
-    for extra in ({}, {"ARL_LSTM_XRED": "0"}):
-        f = str(tmp_path / f"lstm_{len(outs)}.npz")
-        env = dict(os.environ, **extra)
-        subprocess.run([sys.executable, os.path.join(here, "lstm_split_worker.py"), f], env=env, check=True,
-                       timeout=240)
-        outs.append(np.load(f))
+    outs = lstm_form_arms(gpu, 72, ("auto", 0), fc_big_whole=0)
     assert int((outs[0]["hbuf"] != 0).sum()) > 0
     for o in outs[1:]:
-        for k in outs[0].files:
+        assert sorted(o) == sorted(outs[0])
+        for k in outs[0]:
             assert np.array_equal(outs[0][k], o[k]), k
 
 
@@ -770,8 +808,43 @@ def test_norm_fold_matches_grad_sqnorm(gpu):
     assert ok, err
 
 
+def conv_form_arm(gpu, N, pools, sets, runs):
+    """One arm of test_conv_fwd_two_envs_identical: two FF windows (the second graph-captured) at N envs with one
+    env group, under the forms and A3C window options of `sets` (everything else auto / on); a1, a2, the actions,
+    the window-1 gradient, the parameters and the policy / learner buffers they leave.  Before anything launches,
+    the whole state the arm is about to run is read back (net.form, the agent's attributes) against `runs`."""
+    from asyncrl_amd import A3C, A3CFF, GradientClipping, RMSpropAsync
+    T, P = 5, 7
+    dp, dr, dd = pools
+    m = A3CFF(4, n_envs=N, t_max=T, seed=9, init_seed=10, frames="pairs", device=gpu)
+    o = RMSpropAsync(lr=7e-4, eps=0.1, alpha=0.99).setup(m)
+    o.add_hook(GradientClipping(40))
+    ag = A3C(m, o, T, 0.99, window_c=sets.get("window_c", True), fuse_returns=sets.get("fuse_returns", True))
+    net = ag.net
+    net.set_forms(**{k: sets.get(k, "auto") for k in ("conv_epw", "fc_big", "lstm_xred", "conv_bwd_ws")})
+    assert dict(conv_epw=net.form("conv_epw"), fc_big=net.form("fc_big", N), conv_bwd_ws=net.form("conv_bwd_ws"),
+                window_c=ag.window_c, fuse_returns=ag.fuse_returns) == runs
+    ag.run_window(dp, dr, dd, P, first=True, env_groups=1)
+    torch.cuda.synchronize()
+    g1 = net.grads.detach().cpu().numpy().copy()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        ag.run_window(dp, dr, dd, P, stream=s, env_groups=1)
+    g.replay()
+    torch.cuda.synchronize()
+    return dict(grads1=g1, params=net.params.detach().cpu().numpy(),
+                a1=net.buffer("a1", torch.float32).cpu().numpy(), a2=net.buffer("a2", torch.float32).cpu().numpy(),
+                frames=net.buffer("frames").cpu().numpy(),
+                actions=net.buffer("actions", torch.int32, (T + 1, N)).cpu().numpy(),
+                **{k: net.buffer(k, torch.float32).cpu().numpy() for k in ("hfc", "logits", "probs", "logp", "v",
+                                                                          "entropy", "logp_a", "dlogits", "dv",
+                                                                          "loss", "dfc")})
+
+
 @pytest.mark.parametrize("n_envs", [1, 33, 75, 200, 512])
-def test_conv_fwd_two_envs_identical(gpu, tmp_path, n_envs):
+def test_conv_fwd_two_envs_identical(gpu, n_envs):
     """The large-launch forms against the 256-env ones: conv_fwd.hip with two
     envs a workgroup (EPW = 2: 16 waves sharing the weight planes) and fc.hip's
     64-row tiles (fc_fwd_big_kernel), the defaults from 512 envs a launch.  The
@@ -780,30 +853,35 @@ def test_conv_fwd_two_envs_identical(gpu, tmp_path, n_envs):
     -- at an odd env count (the last conv workgroup's second slot idle, a
     partial FC tile), at 200 (a partial 64-row block) and at 512.  And the
     window as one C call (arl_run_window) against its launches issued step by
-    step from Python (ARL_WINDOW_C=0): the C window runs the learner's returns
+    step from Python (window_c off): the C window runs the learner's returns
     and heads backward inside the bootstrap policy launch
     (policy_fc_returns_kernel), so dlogits / dv / the losses / dfc are compared
     too -- also at 1 and 33 envs; the last arm issues the window step by step
-    with the fusion off (ARL_FUSE_RETURNS=0: the separate returns_heads_kernel
+    with the fusion off (fuse_returns off: the separate returns_heads_kernel
     launch), so the fused launch is checked bitwise against the unfused one.
-    ARL_CB_WS=0: conv_bwd.hip's 512-thread kernel against the default
+    conv_bwd_ws 0: conv_bwd.hip's 512-thread kernel against the default
     wave-specialised one (1,024 threads, (1) beside (2) and (3) on the other
     half of each SIMD's waves)."""
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
+    pairs, rewards, dones = make_pools(np.random.default_rng(77), 7, n_envs, "uniform", p_done=0.1)
+    pools = dev(pairs, gpu), dev(rewards, gpu), dev(dones, gpu)
+    auto = dict(conv_epw=2 if n_envs >= 512 else 1, fc_big=int(n_envs >= 512))   # the library's rule at one env group
+    base = dict(conv_epw=1, fc_big=0, conv_bwd_ws=1, window_c=True, fuse_returns=True)
+    # (what the arm sets, the whole state it then runs, the fields in which it is meant to differ from arm 0)
+    arms = ((dict(conv_epw=1, fc_big=0), base, ()),
+            (dict(conv_epw=2, fc_big=0), dict(base, conv_epw=2), ("conv_epw",)),
+            (dict(conv_epw=1, fc_big=1), dict(base, fc_big=1), ("fc_big",)),
+            (dict(window_c=False), dict(base, **auto, window_c=False), ("window_c",)),
+            (dict(window_c=False, fuse_returns=False), dict(base, **auto, window_c=False, fuse_returns=False),
+             ("window_c", "fuse_returns")),
+            (dict(conv_bwd_ws=0), dict(base, **auto, conv_bwd_ws=0), ("conv_bwd_ws",)))
     outs = []
-    for i, arm in enumerate(({"ARL_CONV_EPW": "1", "ARL_FC_BIG": "0"}, {"ARL_CONV_EPW": "2", "ARL_FC_BIG": "0"},
-                             {"ARL_CONV_EPW": "1", "ARL_FC_BIG": "1"}, {"ARL_WINDOW_C": "0"},
-                             {"ARL_WINDOW_C": "0", "ARL_FUSE_RETURNS": "0"}, {"ARL_CB_WS": "0"})):
-        f = str(tmp_path / f"arm_{i}.npz")
-        env = dict(os.environ, **arm)
-        subprocess.run([sys.executable, os.path.join(here, "conv_epw_worker.py"), f, str(n_envs)], env=env,
-                       check=True, timeout=240)
-        outs.append(np.load(f))
+    for sets, runs, differs in arms:
+        assert all(runs[k] != base[k] for k in differs)
+        outs.append(conv_form_arm(gpu, n_envs, pools, sets, runs))
     assert float(np.abs(outs[0]["a2"]).max()) > 0
     for o in outs[1:]:
-        for k in outs[0].files:
+        assert sorted(o) == sorted(outs[0])
+        for k in outs[0]:
             assert np.array_equal(outs[0][k], o[k]), k
 
 
@@ -830,22 +908,14 @@ def test_a2_mask_bits_match_a2(gpu, arch, N):
     assert float(np.abs(a2[T]).max()) > 0
 
 
-def test_lstm_fc_ticket_big_tiles_identical(gpu, tmp_path):
+def test_lstm_fc_ticket_big_tiles_identical(gpu):
     """512 LSTM envs (fc.hip's 64-row tiles): the FC forward's last-arriver
     ticket reduce (fc_fwd_big_kernel's tail, the default from 512-env
     launches) and the reduce in the gate kernel's staging sum the same partials in the same
     order, so hidden / cell states, gates, actions, gradients and parameters
     match bit for bit."""
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    outs = []
-    for extra in ({"ARL_LSTM_XRED": "1"}, {"ARL_LSTM_XRED": "0"}):
-        f = str(tmp_path / f"lstm512_{len(outs)}.npz")
-        env = dict(os.environ, LSTM_WORKER_N="512", **extra)
-        subprocess.run([sys.executable, os.path.join(here, "lstm_split_worker.py"), f], env=env, check=True,
-                       timeout=240)
-        outs.append(np.load(f))
+    outs = lstm_form_arms(gpu, 512, (1, 0), fc_big_whole=1)
     assert int((outs[0]["hbuf"] != 0).sum()) > 0
-    for k in outs[0].files:
+    assert sorted(outs[1]) == sorted(outs[0])
+    for k in outs[0]:
         assert np.array_equal(outs[0][k], outs[1][k]), k

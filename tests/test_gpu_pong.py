@@ -117,19 +117,18 @@ def test_closed_loop_window_one_call(gpu):
 
 
 @pytest.mark.parametrize("kind,A,n,Pl,kw", [("ff", 4, 64, 7, dict(env_groups=2)), ("lstm", 6, 33, 7, {})])
-def test_closed_loop_python_chains(gpu, monkeypatch, kind, A, n, Pl, kw):
+def test_closed_loop_python_chains(gpu, kind, A, n, Pl, kw):
     """The Python chains (_chain_steps): two env groups on two streams at 64 envs, and an LSTM net
     (A = 6: actions 4 and 5 are sampled and move the paddle) on the single chain; the parameters after 6
     windows equal the one-call path's bit for bit."""
-    import asyncrl_amd.a3c as a3c
     T = 5
     one, one_net, _, one_pools = make_agent(kind, A, n, T, Pl, gpu)
     check = LoopCheck(n)
     run_windows(one, one_pools, Pl, 6, check if kind == "lstm" else None)
     if kind == "lstm":
         check.end(one_net, one_net.env, one_pools, Pl)
-    monkeypatch.setattr(a3c, "WINDOW_C", False)               # (the single chain from Python)
     agent, net, game, pools = make_agent(kind, A, n, T, Pl, gpu)
+    agent.window_c = False                                    # (the single chain from Python)
     init = net.params.clone()
     check = LoopCheck(n)
     run_windows(agent, pools, Pl, 6, check, **kw)

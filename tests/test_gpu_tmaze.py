@@ -131,7 +131,6 @@ def test_closed_loop_equals_host_driven_windows(gpu, kind, A, n, kw, length):
 def closed_loop(gpu, kind, A, n, kw, length, T=5, windows=7):
     """The body of the test above at a window length of T (pools of T + 2 entries: a window's T + 1 observations
     fit, and the host's fill of window w + 1 does not reach back into them)."""
-    import asyncrl_amd.a3c as a3c
     Pl = T + 2
     agent, net, game, pools = make_agent(kind, A, n, T, Pl, gpu, length=length)
     host, hnet, _, hpools = make_agent(kind, A, n, T, Pl, gpu, length=length, env=False)
@@ -158,14 +157,13 @@ def closed_loop(gpu, kind, A, n, kw, length, T=5, windows=7):
     rew = np.concatenate(check.rewards)
     assert set(np.unique(rew)) <= {-1.0, 0.0, 1.0} and (rew != 0).any() and (rew[don == 0] == 0).all()
     if kw:                                                    # the same windows as env-group chains from Python
-        with pytest.MonkeyPatch.context() as mp:
-            mp.setattr(a3c, "WINDOW_C", False)
-            chains, cnet, cgame, cpools = make_agent(kind, A, n, T, Pl, gpu, length=length)
-            run_windows(chains, cpools, Pl, windows, **kw)
-            torch.cuda.synchronize()
-            assert cnet.env_groups(2) == [(0, 32), (32, 32)]
-            assert torch.equal(cnet.params.view(torch.int32), net.params.view(torch.int32))
-            assert torch.equal(cgame.state, game.state)
+        chains, cnet, cgame, cpools = make_agent(kind, A, n, T, Pl, gpu, length=length)
+        chains.window_c = False
+        run_windows(chains, cpools, Pl, windows, **kw)
+        torch.cuda.synchronize()
+        assert cnet.env_groups(2) == [(0, 32), (32, 32)]
+        assert torch.equal(cnet.params.view(torch.int32), net.params.view(torch.int32))
+        assert torch.equal(cgame.state, game.state)
 
 
 def build(kind, A, n, T, length, gpu, direct, seed=5, P=3):
