@@ -144,6 +144,11 @@ SIGNATURES = {
     "arl_tmaze_reset": (c_int, [c_void_p, c_i64, c_int, c_u64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "arl_tmaze_step": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_int, c_u64, c_int, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
+    "arl_maze_state_bytes": (c_i64, [c_i64]),
+    "arl_maze_reset": (c_int, [c_void_p, c_i64, c_int, c_u64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
+    "arl_maze_step": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_int, c_u64, c_int, c_int, c_int, c_void_p, c_void_p,
+                              c_void_p, c_void_p]),
     "arl_net_set_env": (c_int, [c_void_p, c_int, c_void_p]),
     "arl_env_reset": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "arl_env_step": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
@@ -188,6 +193,9 @@ PONG_POINTS_MAX = 21
 ENV_TMAZE = 8                # ARL_ENV_TMAZE: the device-resident T-maze; its kind carries the corridor's length
 TMAZE_STATE_INTS = 8         # [pos, cue, length, steps_in_episode, episode, hits, misses, lapses]
 TMAZE_LENGTH_MAX = 8
+ENV_MAZE = 32                # ARL_ENV_MAZE: the device-resident maze; its kind carries rooms, view and levels
+MAZE_STATE_INTS = 8          # [pos | goal << 8, bits, steps_in_episode, episode, wins, timeouts, level, cfg]
+MAZE_ROOMS_MIN, MAZE_ROOMS_MAX, MAZE_VIEW_MAX, MAZE_LEVELS_MAX = 2, 4, 2, 1023
 
 
 def env_pong_points(points: int) -> int:
@@ -198,6 +206,12 @@ def env_pong_points(points: int) -> int:
 def env_tmaze_length(length: int) -> int:
     """ARL_ENV_TMAZE_LENGTH(length): or'ed into ENV_TMAZE; 1..8, and 0 means 4."""
     return length << 16
+
+
+def env_maze_fields(rooms: int, view: int, levels: int) -> int:
+    """ARL_ENV_MAZE_ROOMS(rooms) | ARL_ENV_MAZE_VIEW(view) | ARL_ENV_MAZE_LEVELS(levels): or'ed into ENV_MAZE;
+    rooms 2..4 (0 means 3), view 0..2, levels 0..1023."""
+    return rooms << 16 | view << 19 | levels << 21
 
 
 CTL_ADAM_T = 3         # ARL_CTL_ADAM_T: the control block's count of Adam updates made (buffer "ctl", int64[16])

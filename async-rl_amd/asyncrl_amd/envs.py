@@ -25,7 +25,10 @@ phi pre-stage is the GPU kernel, so the adapter stops at the raw frame pair:
                  background that is not black;
   DeviceTMaze    and for a cue-recall T-maze (csrc/tmaze.hip): the cue is on
                  an episode's first screen alone and is asked for `length`
-                 steps later -- the one env here the FF model cannot solve.
+                 steps later -- the one env here the FF model cannot solve;
+  DeviceMaze     and for a grid maze (csrc/maze.hip) whose layout, start and
+                 goal are drawn per episode from a numbered set of levels:
+                 train on `levels` tasks, score on all of them.
 
 Batched convention: a step whose action ends the episode returns
 done = 1, the reward of that step, and the FIRST pair of the next episode
@@ -39,9 +42,10 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from ._lib import (BREAKOUT_STATE_INTS, CATCH_STATE_INTS, ENV_BREAKOUT, ENV_CATCH, ENV_GAME_OVER_ONLY, ENV_PONG,
-                   ENV_TMAZE, PONG_POINTS_MAX, PONG_STATE_INTS, TMAZE_LENGTH_MAX, TMAZE_STATE_INTS, check,
-                   env_pong_points, env_tmaze_length, lib, ptr, stream_handle)
+from ._lib import (BREAKOUT_STATE_INTS, CATCH_STATE_INTS, ENV_BREAKOUT, ENV_CATCH, ENV_GAME_OVER_ONLY, ENV_MAZE,
+                   ENV_PONG, ENV_TMAZE, MAZE_LEVELS_MAX, MAZE_ROOMS_MAX, MAZE_ROOMS_MIN, MAZE_STATE_INTS,
+                   MAZE_VIEW_MAX, PONG_POINTS_MAX, PONG_STATE_INTS, TMAZE_LENGTH_MAX, TMAZE_STATE_INTS, check,
+                   env_maze_fields, env_pong_points, env_tmaze_length, lib, ptr, stream_handle)
 
 SCREEN = (210, 160, 3)
 
@@ -401,6 +405,47 @@ class DeviceTMaze(_DeviceEnv):
 
     def _step(self, state, parity, actions, n, env_offset, seed, *out):   # the length goes before the outputs
         check(lib.arl_tmaze_step(state, parity, actions, n, env_offset, seed, self.length, *out), "arl_tmaze_step")
+
+
+class DeviceMaze(_DeviceEnv):
+    """A grid maze with procedurally generated levels on the device
+    (include/asyncrl_hip.h, "device environment"; the rules are there):
+    DeviceCatch's surface over a family of tasks.  The maze is (2 rooms + 1)^2
+    tiles, a binary-tree maze over rooms x rooms rooms (rooms in 2..4); its
+    carving, the start room and the goal room are a function of (seed,
+    level).  Every episode draws a level: from 0..levels-1 with levels in
+    1..1023, from all 2^32 with levels = 0 -- train on `levels` tasks, score
+    on all of them, and the difference is a generalisation gap.  Actions
+    a & 3: 0 up, 1 down, 2 right, 3 left (n_actions >= 4); a move into a wall
+    is a bump.  Reward 1 on reaching the goal, which ends the episode; an
+    episode also ends, with reward 0, after 8 rooms env-steps.  Every level
+    can be solved in 8 rooms - 10, so the optimum is 1.  With view = V in
+    1..2 only the tiles within V of the agent are drawn, the goal's included:
+    an exploration task under partial observability.  The state is (2, n, 8)
+    int32; `wins` and `timeouts` are columns 4 and 5."""
+
+    STATE_INTS = MAZE_STATE_INTS
+    _state_bytes = staticmethod(lib.arl_maze_state_bytes)
+
+    def __init__(self, n_envs: int, device=None, seed: int = 0, env_offset: int = 0, rooms: int = 3, view: int = 0,
+                 levels: int = 0):
+        if not MAZE_ROOMS_MIN <= rooms <= MAZE_ROOMS_MAX:
+            raise ValueError(f"DeviceMaze: rooms must be in {MAZE_ROOMS_MIN}..{MAZE_ROOMS_MAX}")
+        if not 0 <= view <= MAZE_VIEW_MAX:
+            raise ValueError(f"DeviceMaze: view must be in 0..{MAZE_VIEW_MAX}")
+        if not 0 <= levels <= MAZE_LEVELS_MAX:
+            raise ValueError(f"DeviceMaze: levels must be in 0..{MAZE_LEVELS_MAX}")
+        super().__init__(n_envs, device, seed, env_offset)
+        self.rooms, self.view, self.levels = int(rooms), int(view), int(levels)
+        self.kind = ENV_MAZE | env_maze_fields(self.rooms, self.view, self.levels)
+
+    def _reset(self, state, n, env_offset, seed, *rest):   # the fields go before the parity
+        check(lib.arl_maze_reset(state, n, env_offset, seed, self.rooms, self.view, self.levels, *rest),
+              "arl_maze_reset")
+
+    def _step(self, state, parity, actions, n, env_offset, seed, *out):   # the fields go before the outputs
+        check(lib.arl_maze_step(state, parity, actions, n, env_offset, seed, self.rooms, self.view, self.levels, *out),
+              "arl_maze_step")
 
 
 class _null:

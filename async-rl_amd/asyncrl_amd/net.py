@@ -579,12 +579,12 @@ class DeviceNet:
         return [window_stats_dict(r) for r in self.window_stats_raw(last, stream)]
 
     # ------------------------------------------------------------ device environment
-    env = None        # the attached DeviceCatch / DeviceBreakout / DevicePong / DeviceTMaze (set_env), else None
+    env = None        # the attached DeviceCatch / DeviceBreakout / DevicePong / DeviceTMaze / DeviceMaze (set_env), else None
     env_direct = False   # set_env(env, direct=True): the env renders straight into the frame ring, no pools
 
     def set_env(self, env=None, direct: bool = False):
         """Attach a device-resident env (envs.DeviceCatch, envs.DeviceBreakout,
-        envs.DevicePong or envs.DeviceTMaze, by its `kind`; arl_net_set_env) built
+        envs.DevicePong, envs.DeviceTMaze or envs.DeviceMaze, by its `kind`; arl_net_set_env) built
         for this net's n_envs, seed and env_offset, or detach with None.  While
         attached, run_window steps it after every act(t), t < t_max, and the
         pools handed to the window are written.  A captured window keeps the

@@ -669,12 +669,40 @@ int arl_tmaze_step(int32_t* state, int parity_in, const int32_t* actions, int64_
                       env_offset, seed, pair_out, reward_out, done_out, s);
 }
 
+int64_t arl_maze_state_bytes(int64_t n_envs) { return env_state_bytes(ARL_ENV_MAZE, n_envs); }
+
+// the kind of a maze call from its explicit fields, or -1 with the error set
+static int maze_kind(const char* who, int rooms, int view, int levels) {
+  if (!arl::maze_fields_ok(rooms, view, levels)) {
+    fail(ARL_EINVAL, std::string(who) + ": rooms out of [2, 4], view out of [0, 2] or levels out of [0, 1023]");
+    return -1;
+  }
+  return ARL_ENV_MAZE | ARL_ENV_MAZE_ROOMS(rooms) | ARL_ENV_MAZE_VIEW(view) | ARL_ENV_MAZE_LEVELS(levels);
+}
+
+int arl_maze_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, int rooms, int view, int levels, int parity,
+                   uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* s) {
+  const int kind = maze_kind("maze_reset", rooms, view, levels);
+  if (kind < 0) return ARL_EINVAL;
+  return env_granular("maze_reset", kind, state, parity, nullptr, false, n, env_offset, seed, pair_out, reward_out,
+                      done_out, s);
+}
+
+int arl_maze_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
+                  int rooms, int view, int levels, uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* s) {
+  const int kind = maze_kind("maze_step", rooms, view, levels);
+  if (kind < 0) return ARL_EINVAL;
+  return env_granular("maze_step", kind, state, parity_in, actions, true, n, env_offset, seed, pair_out, reward_out,
+                      done_out, s);
+}
+
 int arl_net_set_env(arl_net* h, int kind, int32_t* state) {
   if (!h) return fail(ARL_EINVAL, "null net");
   if (!arl::env_kind_ok(kind))
     return fail(ARL_EINVAL,
                 "set_env: unknown env kind (ARL_ENV_CATCH, ARL_ENV_BREAKOUT [| ARL_ENV_GAME_OVER_ONLY], "
-                "ARL_ENV_PONG | ARL_ENV_PONG_POINTS(0..21), or ARL_ENV_TMAZE | ARL_ENV_TMAZE_LENGTH(0..8))");
+                "ARL_ENV_PONG | ARL_ENV_PONG_POINTS(0..21), ARL_ENV_TMAZE | ARL_ENV_TMAZE_LENGTH(0..8), or ARL_ENV_MAZE | "
+                "ARL_ENV_MAZE_ROOMS(0, 2..4) | ARL_ENV_MAZE_VIEW(0..2) | ARL_ENV_MAZE_LEVELS(0..1023))");
   if (!state) {   // detach
     h->net.env_state = nullptr;
     h->net.env_direct = false;
@@ -686,7 +714,7 @@ int arl_net_set_env(arl_net* h, int kind, int32_t* state) {
   if (n.A < 4)
     return fail(ARL_EINVAL,
                 "set_env: the env needs n_actions >= 4 (NOOP / FIRE / RIGHT / LEFT; Pong and the T-maze: NOOP / FIRE / "
-                "UP / DOWN)");
+                "UP / DOWN; the maze: UP / DOWN / RIGHT / LEFT)");
   if (!aligned(state, 16)) return fail(ARL_EINVAL, "set_env: state must be 16-byte aligned");
   h->net.env_state = state;
   h->net.env_kind = kind;
@@ -868,7 +896,8 @@ int arl_env_step_screen(int kind, int32_t* state, int parity_in, const int32_t* 
   if (!arl::env_kind_ok(kind))
     return fail(ARL_EINVAL,
                 "env_step_screen: unknown env kind (ARL_ENV_CATCH, ARL_ENV_BREAKOUT [| ARL_ENV_GAME_OVER_ONLY], "
-                "ARL_ENV_PONG | ARL_ENV_PONG_POINTS(0..21), or ARL_ENV_TMAZE | ARL_ENV_TMAZE_LENGTH(0..8))");
+                "ARL_ENV_PONG | ARL_ENV_PONG_POINTS(0..21), ARL_ENV_TMAZE | ARL_ENV_TMAZE_LENGTH(0..8), or ARL_ENV_MAZE | "
+                "ARL_ENV_MAZE_ROOMS(0, 2..4) | ARL_ENV_MAZE_VIEW(0..2) | ARL_ENV_MAZE_LEVELS(0..1023))");
   if (n < 0 || n > 65535) return fail(ARL_EINVAL, "env_step_screen: n out of [0, 65535]");
   if (parity_in != 0 && parity_in != 1) return fail(ARL_EINVAL, "env_step_screen: parity must be 0 or 1");
   if (int rc = bad_resize_mode(resize_mode)) return rc;

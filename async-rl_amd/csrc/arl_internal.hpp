@@ -138,7 +138,7 @@ hipError_t launch_episode_reset(char* block, int n, hipStream_t s);
 // envs in a fixed order (phi.hip episode_reduce_kernel); clear: also zero the cumulative per-env arrays
 hipError_t launch_episode_reduce(char* block, int n, double* out8, int clear, hipStream_t s);
 
-// Device-resident envs (env_kernel.hpp, with the games in catch.hip, breakout.hip, pong.hip and tmaze.hip; the header's "device
+// Device-resident envs (env_kernel.hpp, with the games in catch.hip, breakout.hip, pong.hip, tmaze.hip and maze.hip; the header's "device
 // environment"): one launch = one env-step (or the reset) of envs [e0, e0 + ne): transition + render into pool
 // entry (k + 1) % pool_len (reset: k % pool_len), k = ctl[CTL_STEP] + t read on the device; the state half read
 // is k & 1, the half written (k + 1) & 1.
@@ -148,6 +148,7 @@ constexpr int BREAKOUT_STATE_INTS = 16;   // [bx, by, vx, vy, px, lives, serves,
 constexpr int PONG_STATE_INTS = 12;       // [bx, by, vx, vy, py, oy, serves, steps_in_episode, game, game_steps,
                                           //  score_agent, score_opp]
 constexpr int TMAZE_STATE_INTS = 8;       // [pos, cue, length, steps_in_episode, episode, hits, misses, lapses]
+constexpr int MAZE_STATE_INTS = 8;        // [pos | goal << 8, bits, steps_in_episode, episode, wins, timeouts, level, cfg]
 struct EnvArgs {
   int32_t* state;            // (2, n, the game's STATE_INTS), 16-byte aligned
   const int32_t* actions;    // (n): the actions of observation k; null: reset (episode 0 into half k & 1)
@@ -162,21 +163,24 @@ struct EnvArgs {
   int env_offset = 0;
   uint32_t seed_lo = 0, seed_hi = 0;
   int flags = 0;             // filled by launch_env from the kind: Breakout's ARL_ENV_GAME_OVER_ONLY or 0, Pong's
-                             // points (1..21), the T-maze's length (1..8); Catch ignores it
+                             // points (1..21), the T-maze's length (1..8), the maze's packed (rooms, view, levels); Catch ignores it
 };
-struct Catch;      // the games: catch.hip, breakout.hip, pong.hip and tmaze.hip each instantiate their launch_game
+struct Catch;      // the games: catch.hip, breakout.hip, pong.hip, tmaze.hip and maze.hip each instantiate their launch_game
 struct Breakout;
 struct Pong;
 struct TMaze;
+struct Maze;
 template <class Game> hipError_t launch_game(const EnvArgs& a, hipStream_t s);   // env_kernel.hpp
 extern template hipError_t launch_game<Catch>(const EnvArgs&, hipStream_t);
 extern template hipError_t launch_game<Breakout>(const EnvArgs&, hipStream_t);
 extern template hipError_t launch_game<Pong>(const EnvArgs&, hipStream_t);
 extern template hipError_t launch_game<TMaze>(const EnvArgs&, hipStream_t);
+extern template hipError_t launch_game<Maze>(const EnvArgs&, hipStream_t);
 
 // The library's only look at an env kind (ARL_ENV_*, a Breakout's with an optional ARL_ENV_GAME_OVER_ONLY, a
-// Pong's with its points in bits 16 and up: 1..21, 0 = 21, a T-maze's with its length there: 1..8, 0 = 4; no other
-// bit).
+// Pong's with its points in bits 16 and up: 1..21, 0 = 21, a T-maze's with its length there: 1..8, 0 = 4, a
+// maze's with its rooms in bits 16..18: 2..4, 0 = 3, its view in bits 19..20: 0..2, and its levels in bits 21..30;
+// no other bit).
 constexpr int PONG_POINTS_MAX = 21;
 constexpr int TMAZE_LENGTH_MAX = 8, TMAZE_LENGTH_DEFAULT = 4;
 constexpr bool env_is_breakout(int kind) { return (kind & ~ARL_ENV_GAME_OVER_ONLY) == ARL_ENV_BREAKOUT; }
@@ -188,17 +192,33 @@ constexpr bool env_is_tmaze(int kind) {
   return kind >= 0 && (kind & 0xffff) == ARL_ENV_TMAZE && (kind >> 16) <= TMAZE_LENGTH_MAX;
 }
 constexpr int tmaze_length(int kind) { return (kind >> 16) ? (kind >> 16) : TMAZE_LENGTH_DEFAULT; }
+constexpr int MAZE_ROOMS_MIN = 2, MAZE_ROOMS_MAX = 4, MAZE_ROOMS_DEFAULT = 3, MAZE_VIEW_MAX = 2, MAZE_LEVELS_MAX = 1023;
+constexpr bool maze_fields_ok(int rooms, int view, int levels) {
+  return rooms >= MAZE_ROOMS_MIN && rooms <= MAZE_ROOMS_MAX && view >= 0 && view <= MAZE_VIEW_MAX && levels >= 0 &&
+         levels <= MAZE_LEVELS_MAX;
+}
+constexpr int maze_rooms(int kind) { return ((kind >> 16) & 7) ? ((kind >> 16) & 7) : MAZE_ROOMS_DEFAULT; }
+constexpr bool env_is_maze(int kind) {
+  return kind >= 0 && (kind & 0xffff) == ARL_ENV_MAZE && maze_fields_ok(maze_rooms(kind), (kind >> 19) & 3, kind >> 21);
+}
+// what the kernel takes as its flags and keeps in the state row: rooms | view << 3 | levels << 5
+constexpr int maze_cfg(int kind) { return ((kind >> 16) & ~7) | maze_rooms(kind); }
 constexpr bool env_kind_ok(int kind) {
-  return kind == ARL_ENV_CATCH || env_is_breakout(kind) || env_is_pong(kind) || env_is_tmaze(kind);
+  return kind == ARL_ENV_CATCH || env_is_breakout(kind) || env_is_pong(kind) || env_is_tmaze(kind) || env_is_maze(kind);
 }
 constexpr int env_state_ints(int kind) {
-  return env_is_tmaze(kind)      ? TMAZE_STATE_INTS
+  return env_is_maze(kind)       ? MAZE_STATE_INTS
+         : env_is_tmaze(kind)    ? TMAZE_STATE_INTS
          : env_is_pong(kind)     ? PONG_STATE_INTS
          : env_is_breakout(kind) ? BREAKOUT_STATE_INTS
                                  : CATCH_STATE_INTS;
 }
 inline hipError_t launch_env(int kind, const EnvArgs& a, hipStream_t s) {
   EnvArgs f = a;
+  if (env_is_maze(kind)) {
+    f.flags = maze_cfg(kind);
+    return launch_game<Maze>(f, s);
+  }
   if (env_is_tmaze(kind)) {
     f.flags = tmaze_length(kind);
     return launch_game<TMaze>(f, s);
@@ -227,8 +247,13 @@ extern template hipError_t launch_game_direct<Catch>(const DirectArgs&, hipStrea
 extern template hipError_t launch_game_direct<Breakout>(const DirectArgs&, hipStream_t);
 extern template hipError_t launch_game_direct<Pong>(const DirectArgs&, hipStream_t);
 extern template hipError_t launch_game_direct<TMaze>(const DirectArgs&, hipStream_t);
+extern template hipError_t launch_game_direct<Maze>(const DirectArgs&, hipStream_t);
 inline hipError_t launch_env_direct(int kind, const DirectArgs& a, hipStream_t s) {
   DirectArgs f = a;
+  if (env_is_maze(kind)) {
+    f.env.flags = maze_cfg(kind);
+    return launch_game_direct<Maze>(f, s);
+  }
   if (env_is_tmaze(kind)) {
     f.env.flags = tmaze_length(kind);
     return launch_game_direct<TMaze>(f, s);

@@ -1023,11 +1023,87 @@ int arl_tmaze_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, in
 int arl_tmaze_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
                    int length, uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* stream);
 
+/* A device-resident grid maze with procedurally generated levels, the fifth
+ * device environment.  The other four are single tasks: a policy is trained on
+ * the very episodes it is scored on.  Here the layout, the start and the goal
+ * are drawn per episode from a numbered set of levels: levels = L trains on L
+ * fixed tasks, levels = 0 draws from all of them, and the difference between
+ * the two scores is a generalisation gap.  A view knob hides everything
+ * outside a small window around the agent, which makes the same game an
+ * exploration task under partial observability.  Same launch shape, pools and
+ * state protocol as Catch; additions to ABI 4.
+ *
+ * The game (exact in integer arithmetic; tests/maze_ref.py restates it).
+ * Screen 210 rows x 160 columns, RGB uint8, HWC, background (0,0,0).
+ * Geometry: rooms = R in 2..4; the maze is G x G tiles, G = 2R + 1, a tile 16
+ *   x 16 pixels: tile (ty, tx) covers rows 32 + 16 ty .. + 15 and columns
+ *   16 tx .. + 15 (16 x 11 exceeds 160 columns, hence R <= 4).
+ * Rooms and carving (a binary-tree maze): the rooms are the tiles (2i + 1,
+ *   2j + 1), i, j in 0..R-1, i = 0 the top row.  Room (0, R-1) carves nothing;
+ *   the other rooms of row 0 carve east; the other rooms of column R-1 carve
+ *   north; every other room carves north if bit k = (i - 1)(R - 1) + j of
+ *   `bits` is set, else east.  North opens tile (2i, 2j + 1), east opens tile
+ *   (2i + 1, 2j + 2); everything else is wall.  That is 2 R^2 - 1 open tiles
+ *   and a spanning tree of the rooms: every goal is reachable.
+ * Level to task: with (w0, w1, w2, .) = philox4x32_10(counter = (level, 0, 1,
+ *   6), key = (seed & 0xffffffff, seed >> 32)) and mulhi(a, b) = (uint64(a) *
+ *   b) >> 32: bits = w0 & (2^((R-1)^2) - 1); start room s = mulhi(w1, R^2);
+ *   goal room g = s + 1 + mulhi(w2, R^2 - 1), minus R^2 if that is >= R^2 (so
+ *   g != s).  Room index = i R + j.
+ * Episode to level: with w0 of philox4x32_10(counter = (env_offset + e,
+ *   episode, 0, 6), same key): level = levels ? mulhi(w0, levels) : w0, levels
+ *   in 0..1023.  Counter word 3 = 6 is a stream beside 0 (window draws), 1
+ *   (pi_and_v draws), 2 (Catch), 3 (Breakout), 4 (Pong) and 5 (T-maze).
+ *   episode starts at 0 and advances at every terminal.
+ * Episode start: the agent on the start room's tile, steps_in_episode = 0.
+ * Actions: a & 3: 0 up, 1 down, 2 right, 3 left (any n_actions >= 4).
+ * One env-step: steps_in_episode += 1.  If the target tile is open the agent
+ *   moves there in four frames of 4 px: pair[0] shows it on the target tile,
+ *   pair[1] 4 px short of it.  If the target is a wall both screens show the
+ *   unmoved agent.  If the agent is now on the goal: reward 1, done.  Else if
+ *   steps_in_episode == 8R: reward 0, done.  On done, wins or timeouts
+ *   advances, episode += 1, and the next episode starts at once: both frames
+ *   of the pair are its first screen (Catch's rule: the terminal screen is
+ *   never shown).
+ * Drawing: open tile (40,40,40), wall tile (96,96,96), goal tile
+ *   (236,236,120), agent (92,186,92): 8 x 8 at offset (4, 4) inside its tile,
+ *   drawn over the tile.  view = V in 0..2; V = 0 shows the whole maze.  With
+ *   V >= 1 a tile whose Chebyshev distance from the agent's tile after the
+ *   step exceeds V is black on both screens of the pair, the goal's included;
+ *   the agent is always drawn.
+ * The longest shortest path from a start to a goal is 8R - 10 env-steps, so
+ * every level is solvable within the cap of 8R and the optimum return is 1.
+ *
+ * Env state: caller-owned device memory, (2, n_envs, 8) int32, 16-byte
+ * aligned, [pos | goal << 8, bits, steps_in_episode, episode, wins, timeouts,
+ * level, cfg] per env, pos and goal as 16 ty + tx, double-buffered by the
+ * parity of the observation index exactly as Catch's.  cfg = R | V << 3 |
+ * levels << 5: the reset stores it in the row; a step keeps the one of its
+ * call there.
+ *
+ * The kind is ARL_ENV_MAZE | ARL_ENV_MAZE_ROOMS(r) | ARL_ENV_MAZE_VIEW(v) |
+ * ARL_ENV_MAZE_LEVELS(l): r in 2..4, r = 0 means 3; v in 0..2; l in 0..1023.
+ * Any other bit (0x100 included), r = 1 or 5..7, v = 3: ARL_EINVAL.
+ * Granular calls: Catch's trio; arl_maze_reset and arl_maze_step take rooms
+ * (2..4), view (0..2) and levels (0..1023), anything else: ARL_EINVAL, the
+ * same in both. */
+#define ARL_ENV_MAZE 32
+#define ARL_ENV_MAZE_ROOMS(r) ((r) << 16)
+#define ARL_ENV_MAZE_VIEW(v) ((v) << 19)
+#define ARL_ENV_MAZE_LEVELS(l) ((l) << 21)
+int64_t arl_maze_state_bytes(int64_t n_envs);
+int arl_maze_reset(int32_t* state, int64_t n, int env_offset, uint64_t seed, int rooms, int view, int levels,
+                   int parity, uint8_t* pair_out, float* reward_out, uint8_t* done_out, void* stream);
+int arl_maze_step(int32_t* state, int parity_in, const int32_t* actions, int64_t n, int env_offset, uint64_t seed,
+                  int rooms, int view, int levels, uint8_t* pair_out, float* reward_out, uint8_t* done_out,
+                  void* stream);
+
 /* Attached to a net (host state of the handle, like arl_net_set_adam; works on
  * an unbound handle): arl_net_set_env(net, kind, state) with kind =
  * ARL_ENV_CATCH, ARL_ENV_BREAKOUT, ARL_ENV_BREAKOUT | ARL_ENV_GAME_OVER_ONLY,
- * ARL_ENV_PONG | ARL_ENV_PONG_POINTS(p) or ARL_ENV_TMAZE |
- * ARL_ENV_TMAZE_LENGTH(l)
+ * ARL_ENV_PONG | ARL_ENV_PONG_POINTS(p), ARL_ENV_TMAZE |
+ * ARL_ENV_TMAZE_LENGTH(l) or ARL_ENV_MAZE | ARL_ENV_MAZE_ROOMS(r) |
+ * ARL_ENV_MAZE_VIEW(v) | ARL_ENV_MAZE_LEVELS(l)
  * (any other value, the flag on Catch included: ARL_EINVAL) and state as above
  * for that env, the net's n_envs, its env_offset and seed; state == NULL
  * detaches.  arl_env_reset, arl_env_step and arl_run_window launch the
@@ -1058,7 +1134,7 @@ int arl_env_step(arl_net* net, int t, int e0, int ne, uint8_t* pair_pool, float*
 
 /* Direct-to-ring device env: the env-step and the observation that follows it
  * as ONE launch that never materialises the frame pair.  Every screen of the
- * four games is a function of the env's handful of integers, so the launch
+ * five games is a function of the env's handful of integers, so the launch
  * evaluates arl_observe's arithmetic (max of the two screens, float64
  * luminance, the fixed-point resize of resize_mode) on bytes it produces in
  * registers and stores the 84 x 84 plane into the frame ring, with the
@@ -1099,7 +1175,7 @@ int arl_env_step(arl_net* net, int t, int e0, int ne, uint8_t* pair_pool, float*
  * arl_current_screen on the pair it would have written: one env-step from
  * actions (n,) and half parity_in into half 1 - parity_in, screen_out (n, 84,
  * 84) uint8, the raw rewards (n,) and dones (n,).  kind as arl_net_set_env
- * takes it (Breakout's flag, Pong's points, the T-maze's length).  n <=
+ * takes it (Breakout's flag, Pong's points, the T-maze's length, the maze's fields).  n <=
  * 65535; ARL_EINVAL for an unknown kind, a parity other than 0 / 1, a bad
  * resize_mode, a null or misaligned pointer (state 16 bytes; screens,
  * rewards, actions 4). */

@@ -3,8 +3,8 @@
 
 Three measurements, arms interleaved within every round (one process, one device):
   step     arl_env_step alone, Catch's ("env_step"), Breakout's ("breakout_step", from the reset state: all 120
-           bricks to render), Pong's ("pong_step", from the reset state) and the T-maze's ("tmaze_step") at 512
-           envs (C4, FF) and 1,024 envs (C3's frames, LSTM): microseconds per launch
+           bricks to render), Pong's ("pong_step", from the reset state), the T-maze's ("tmaze_step") and the maze's ("maze_step",
+           rooms 3, view 0) at 512 envs (C4, FF) and 1,024 envs (C3's frames, LSTM): microseconds per launch
            over back-to-back launches between two events, and the store rate on the 201,600 x n bytes it writes;
            beside it arl_stream_copy of the same byte count, every mode, whose best is the yardstick
            (a copy moves each byte twice, so its rate is quoted on bytes written, as the env's is);
@@ -14,11 +14,11 @@ Three measurements, arms interleaved within every round (one process, one device
            observation's share.  Run once per library build (ASYNCRL_HIP_LIB), processes alternating, to A/B a
            change of the render's stores with the launch that reads them timed in both arms (how plain stores
            were chosen over non-temporal ones: DESIGN.md, "Device environment").
---env breakout / --env pong / --env tmaze attach DeviceBreakout / DevicePong / DeviceTMaze instead of DeviceCatch
+--env breakout / --env pong / --env tmaze / --env maze attach DeviceBreakout / DevicePong / DeviceTMaze / DeviceMaze instead of DeviceCatch
 in the window and handoff measurements.
 One JSON line (and --out FILE).
 
-    python scripts/device_env_cost.py [--env catch|breakout|pong|tmaze] [--rounds 5] [--launches 40] [--windows 200]
+    python scripts/device_env_cost.py [--env catch|breakout|pong|tmaze|maze] [--rounds 5] [--launches 40] [--windows 200]
                                       [--only step,window,handoff]
 """
 import argparse
@@ -61,7 +61,7 @@ def setup(kind, n, dev, stream, P=2, game="catch"):
     opt.anneal_total_steps, opt.n_total_envs = 8 * 10 ** 7, n
     agent = pkg.A3C(model, opt, T, 0.99, beta=1e-2, collectives=False)
     game_cls = {"catch": pkg.DeviceCatch, "breakout": pkg.DeviceBreakout, "pong": pkg.DevicePong,
-                "tmaze": pkg.DeviceTMaze}[game]
+                "tmaze": pkg.DeviceTMaze, "maze": pkg.DeviceMaze}[game]
     env = game_cls(n, device=dev, seed=1234)
     pools = env.make_pools(P)
     net = model.net
@@ -82,10 +82,12 @@ def measure_step(kind, n, dev, stream, rounds, launches):
     _, bnet, benv, bpools = setup(kind, n, dev, stream, game="breakout")
     _, pnet, penv, ppools = setup(kind, n, dev, stream, game="pong")
     _, tnet, tenv, tpools = setup(kind, n, dev, stream, game="tmaze")
+    _, mnet, menv, mpools = setup(kind, n, dev, stream, game="maze")
     arms = {"env_step": lambda: net.env_step(0, *pools, 2, stream=stream),
             "breakout_step": lambda: bnet.env_step(0, *bpools, 2, stream=stream),
             "pong_step": lambda: pnet.env_step(0, *ppools, 2, stream=stream),
-            "tmaze_step": lambda: tnet.env_step(0, *tpools, 2, stream=stream)}
+            "tmaze_step": lambda: tnet.env_step(0, *tpools, 2, stream=stream),
+            "maze_step": lambda: mnet.env_step(0, *mpools, 2, stream=stream)}
     for mode, blocks in ((0, 2048), (1, 2048), (2, 1), (3, 1)):
         arms["copy_mode%d" % mode] = (lambda m=mode, b=blocks: check(
             lib.arl_stream_copy(ptr(src), ptr(dst), nbytes, b, m, h), "arl_stream_copy"))
@@ -105,6 +107,8 @@ def measure_step(kind, n, dev, stream, rounds, launches):
             "pong_over_catch_time": round(med["pong_step"] / med["env_step"], 3),
             "tmaze_over_best_copy_rate": round(rate["tmaze_step"] / rate[best], 3),
             "tmaze_over_catch_time": round(med["tmaze_step"] / med["env_step"], 3),
+            "maze_over_best_copy_rate": round(rate["maze_step"] / rate[best], 3),
+            "maze_over_catch_time": round(med["maze_step"] / med["env_step"], 3),
             "us": {k: [round(x, 2) for x in v] for k, v in us.items()}}
 
 
@@ -160,7 +164,7 @@ def measure_handoff(dev, stream, rounds, launches, game="catch"):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--env", choices=("catch", "breakout", "pong", "tmaze"), default="catch")
+    ap.add_argument("--env", choices=("catch", "breakout", "pong", "tmaze", "maze"), default="catch")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--launches", type=int, default=40)
     ap.add_argument("--windows", type=int, default=200)

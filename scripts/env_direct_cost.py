@@ -32,7 +32,8 @@ sys.path.insert(0, os.path.join(ROOT, "async-rl_amd"))
 import asyncrl_amd as pkg  # noqa: E402
 
 SHAPES = {"c4": ("ff", 512), "c3": ("lstm", 1024)}
-GAMES = {"catch": pkg.DeviceCatch, "breakout": pkg.DeviceBreakout, "pong": pkg.DevicePong, "tmaze": pkg.DeviceTMaze}
+GAMES = {"catch": pkg.DeviceCatch, "breakout": pkg.DeviceBreakout, "pong": pkg.DevicePong, "tmaze": pkg.DeviceTMaze,
+         "maze": pkg.DeviceMaze}
 P = 2
 
 

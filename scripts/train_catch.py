@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Closed-loop training on a device-resident env (asyncrl_amd.DeviceCatch, DeviceBreakout with --env breakout,
-DevicePong with --env pong --points P, or DeviceTMaze with --env tmaze --length L): the learner has to learn.
+DevicePong with --env pong --points P, DeviceTMaze with --env tmaze --length L, or DeviceMaze with --env maze
+--rooms R --view V --levels L): the learner has to learn.
 
 env -> phi -> forward -> sample -> env -> ... -> update runs on the device with no host work per step: window 0
 eagerly (first=True), then one captured window replayed.  Every --report windows the learning curve is read
@@ -13,7 +14,13 @@ the return is the agent's points minus the opponent's, and a uniform random poli
 and about -17 at 21.  With --env tmaze an episode is one cue, a corridor of --length steps and one choice (+1 for the
 cue's arm, -1 for the other, 0 for none): any policy that does not remember the cue scores 0 on average, which from
 --length 4 on is every policy of the FF model; --arch lstm can reach +1.  --t-max sets the window (default 5: with
---length 4 an episode is one window; a longer corridor needs memory across a window boundary).
+--length 4 an episode is one window; a longer corridor needs memory across a window boundary).  With --env maze an
+episode is one level of a grid maze over --rooms x --rooms rooms: +1 for reaching the goal within 8 rooms steps, else
+0, so the mean return is the success rate; a uniform random policy scores 0.368 / 0.211 / 0.144 at --rooms 2 / 3 / 4.
+--view 1 or 2 hides all but the tiles around the agent.  --levels L > 0 trains on levels 0..L-1 only; after training
+the parameters are copied into an evaluation model that plays 2,048 sampled runs on DeviceMaze(levels=L) and on
+DeviceMaze(levels=0), same seed: the two success rates ("eval_trained_levels", "eval_all_levels") are printed and
+added to the JSON line, and their difference is the generalisation gap.
 
 Defaults are the reference's hyperparameters (RMSpropAsync lr 7e-4, alpha 0.99, eps 0.1, clip 40, beta 0.01,
 gamma 0.99) on the FF model with 256 envs; the batched learner sums the gradient of all envs, so --batch-loss
@@ -24,7 +31,8 @@ device-side record, A3C.ppo_epoch_stats) are there to try.  --direct runs the en
 (DeviceNet.set_env(env, direct=True)): no frame pools are allocated, the curve is bit-identical.  One JSON line at
 the end (and --out FILE).
 
-    python scripts/train_catch.py [--env catch|breakout|pong|tmaze] [--points 21] [--length 4] [--t-max 5]
+    python scripts/train_catch.py [--env catch|breakout|pong|tmaze|maze] [--points 21] [--length 4] [--t-max 5]
+                                  [--rooms 3] [--view 0] [--levels 0]
                                   [--windows 4000] [--report 200]
                                   [--envs 256] [--seed 0]
                                   [--lr 7e-4] [--opt rmsprop|adam] [--batch-loss sum|mean] [--gae-lambda 1.0]
@@ -47,9 +55,11 @@ import asyncrl_amd as pkg  # noqa: E402
 
 def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", batch_loss="sum", gae_lambda=1.0,
           arch="ff", beta=1e-2, eps=None, device="cuda:0", log=print, env="catch", ppo_epochs=1, ppo_clip=0.2, ppo_norm_adv=False,
-          ppo_vclip=None, points=21, direct=False, length=4, t_max=5):
+          ppo_vclip=None, points=21, direct=False, length=4, t_max=5, rooms=3, view=0, levels=0, evaluation=None):
     """Returns the curve: one dict per report with the window count, the episodes completed since the last
-    report and their mean return, and the newest window record's entropy / value / gradient norm."""
+    report and their mean return, and the newest window record's entropy / value / gradient norm.  evaluation: a
+    dict that, with env="maze" and levels > 0, receives the trained model's success rates on the trained levels
+    and on all levels (evaluate_maze)."""
     dev = torch.device(device)
     T, A, P = t_max, 4, 2
     model = (pkg.A3CFF if arch == "ff" else pkg.A3CLSTM)(A, n_envs=envs, t_max=T, seed=seed, init_seed=seed,
@@ -69,6 +79,8 @@ def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", ba
         game = pkg.DevicePong(envs, device=dev, seed=seed, points=points)
     elif env == "tmaze":
         game = pkg.DeviceTMaze(envs, device=dev, seed=seed, length=length)
+    elif env == "maze":
+        game = pkg.DeviceMaze(envs, device=dev, seed=seed, rooms=rooms, view=view, levels=levels)
     else:
         game = (pkg.DeviceBreakout if env == "breakout" else pkg.DeviceCatch)(envs, device=dev, seed=seed)
     pools = (None, None, None) if direct else game.make_pools(P)   # direct: the frame pairs never exist
@@ -109,15 +121,41 @@ def train(envs=256, windows=4000, report=200, seed=0, lr=7e-4, opt="rmsprop", ba
             + ("  vclip %.3f  adv %+.3f +- %.3f" % tuple(row["ppo_epoch"][k] for k in ("vclip_fraction", "adv_mean",
                                                                                           "adv_std"))
                if "ppo_epoch" in row else ""))
+    if env == "maze" and levels > 0 and evaluation is not None:
+        with torch.cuda.stream(stream):
+            evaluation.update(evaluate_maze(model, arch, dev, seed, rooms, view, levels, T, stream))
+        log("success on the %d trained levels %.4f, on all levels %.4f (%d sampled runs each)"
+            % (levels, evaluation["eval_trained_levels"], evaluation["eval_all_levels"], EVAL_RUNS))
     return curve
+
+
+EVAL_RUNS, EVAL_ENVS = 2048, 256
+
+
+def evaluate_maze(model, arch, dev, seed, rooms, view, levels, t_max, stream=None):
+    """The trained parameters in an evaluation model of its own (the learner's games go on), EVAL_RUNS runs of the
+    sampled policy through evaluation.run_episodes on the trained levels and on all of them, same seed: a run's
+    score is 1 or 0, so the mean is the success rate."""
+    ev = (pkg.A3CFF if arch == "ff" else pkg.A3CLSTM)(4, n_envs=EVAL_ENVS, t_max=t_max, seed=seed, init_seed=seed,
+                                                      device=dev, frames="pairs")
+    ev.net.copy_params_from(model.net)
+    out = {}
+    for key, lv in (("eval_trained_levels", levels), ("eval_all_levels", 0)):
+        game = pkg.DeviceMaze(EVAL_ENVS, device=dev, seed=seed, rooms=rooms, view=view, levels=lv)
+        scores, _ = pkg.run_episodes(ev, game, EVAL_RUNS, deterministic=False, stream=stream)
+        out[key] = float(scores.mean())
+    return out
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--env", choices=("catch", "breakout", "pong", "tmaze"), default="catch")
+    ap.add_argument("--env", choices=("catch", "breakout", "pong", "tmaze", "maze"), default="catch")
     ap.add_argument("--points", type=int, default=21)
     ap.add_argument("--length", type=int, default=4)
     ap.add_argument("--t-max", type=int, default=5)
+    ap.add_argument("--rooms", type=int, default=3)
+    ap.add_argument("--view", type=int, default=0)
+    ap.add_argument("--levels", type=int, default=0)
     ap.add_argument("--envs", type=int, default=256)
     ap.add_argument("--windows", type=int, default=4000)
     ap.add_argument("--report", type=int, default=200)
@@ -137,8 +175,10 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     cfg = {k: v for k, v in vars(a).items() if k != "out"}
-    curve = train(**cfg)
+    evaluation = {}
+    curve = train(evaluation=evaluation, **cfg)
     out = {"config": cfg, "curve": curve, "final_mean_return": curve[-1]["mean_return"] if curve else None}
+    out.update(evaluation)
     print(json.dumps(out), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
